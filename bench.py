@@ -16,8 +16,14 @@ pt_comm_init_all, one host thread per device, pt_comm_gather_all — the form th
 .NET host's HipRendererGroup uses (Renderer.cs:257-333 spreads one frame over the
 whole machine from one process).
 
-Rank 0 prints one JSON line (driver contract), with `roofline` for the closest-hit
-kernel and `cpu_baseline` (the oracle port timed on this host).
+Rank 0 prints one JSON line (driver contract).  A plain run does only what that line's headline
+needs: scene setup, warm-up, the timed steps (with their per-kernel hipEvent times), the line.
+--dump-outputs DIR then writes what the last timed step left, rank 0's Welford Buffer {M, V, N}, as
+DIR/<name>.npy (float64; a fixed seeded sample of the pixels, listed in pixels.npy, when the whole
+Buffer would pass 64 MB), so that two builds can be compared output for output: the same arguments
+give the same inputs.  --full adds everything that takes runs of its own: the counted pass and the
+`roofline` it prices for the closest-hit kernel, the OBJ round-trip check, `cpu_baseline` (the
+oracle port timed on this host) and the `parity` sample against it.
 
 --workload c3 / c2 measure the other GPU configs of BASELINE.json the same way (not the
 driver's line): C3 = the 69,451-triangle mesh in the same frame (L2 roofline of its dominant
@@ -116,6 +122,30 @@ def library_id(path=None):
             return hashlib.sha256(f.read()).hexdigest()[:16]
     except OSError:
         return None
+
+
+DUMP_MAX_BYTES = 48 << 20   # of --dump-outputs' files together (the limit is 64 MB)
+DUMP_PIXEL_BYTES = 8 * 8    # per pixel: M and V (3 float64 each), N and the pixel's index (as float64)
+
+
+def dump_pixels(n_pixels):
+    """The pixels --dump-outputs writes, as sorted flat indices (y * W + x): all of them while M, V, N
+    and the index list fit in DUMP_MAX_BYTES, otherwise a sample of that size drawn without
+    replacement from a generator seeded with 0 (the same pixels for the same frame size, every run)."""
+    k = DUMP_MAX_BYTES // DUMP_PIXEL_BYTES
+    if n_pixels <= k:
+        return np.arange(n_pixels, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n_pixels, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(d, buf):
+    """Writes a Buffer's {M [n, 3], V [n, 3], N [n]} at dump_pixels' pixels [n] to d/<name>.npy, float64."""
+    os.makedirs(d, exist_ok=True)
+    idx = dump_pixels(buf.N.size)
+    arrays = {"M": buf.M.reshape(-1, 3)[idx], "V": buf.V.reshape(-1, 3)[idx], "N": buf.N.reshape(-1)[idx], "pixels": idx}
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    return {"dir": d, "pixels": int(len(idx)), "of": int(buf.N.size), "arrays": sorted(arrays)}
 
 
 def scale_block(contexts, gather_ms, elapsed_s):
@@ -218,8 +248,14 @@ def parse(argv=None):
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--mesh-source", choices=["obj", "generator"], default="obj",
                    help="c3/c4 mesh: written as OBJ and loaded through pt_obj_load (default), or in memory")
-    p.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline sample budget (0 = skip)")
-    p.add_argument("--no-parity", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the counted pass and the roofline, the OBJ "
+                        "round-trip check, the CPU baseline and the parity sample (off: set up, warm up, time, print)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write rank 0's Buffer as they left it to DIR/{M,V,N,pixels}.npy (float64; "
+                        "a fixed seeded sample of the pixels when the whole Buffer would pass 64 MB)")
+    p.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU-baseline sample budget (0 = skip)")
+    p.add_argument("--no-parity", action="store_true", help="--full: skip the parity sample")
     p.add_argument("--engine", choices=["auto", "mega", "wave"], default="auto")
     p.add_argument("--json-out", default=None)
     p.add_argument("--passes-per-call", type=int, default=0,
@@ -327,13 +363,14 @@ def main(argv=None):
                 tl = time.perf_counter() - tl
             obj_info = {"obj_bytes": size, "obj_write_s": round(tw, 3), "obj_load_s": round(tl, 3),
                    "obj_triangles": len(mesh.v1)}
-            raw = {k: getattr(mesh, k).copy() for k in ("v1", "v2", "v3", "n1", "n2", "n3", "t1", "t2", "t3")}
+            raw = ({k: getattr(mesh, k).copy() for k in ("v1", "v2", "v3", "n1", "n2", "n3", "t1", "t2", "t3")}
+                   if a.full else None)
             scene, camera, sampler = frame(a.tris, seed=a.seed, mesh=mesh)
         else:
             scene, camera, sampler = frame(a.tris, seed=a.seed)
     scene.Compile()
     t_scene = time.perf_counter() - t_scene
-    if obj_info is not None:   # the OBJ round trip is exact: the loaded Triangle[] is the generator's, bit for bit
+    if obj_info is not None and a.full:   # the OBJ round trip is exact: the loaded Triangle[] is the generator's, bit for bit
         gen = scenes.blob_mesh(a.tris, a.seed)
         obj_info["obj_equals_generator"] = all(np.array_equal(raw[k].view(np.uint32), getattr(gen, k).view(np.uint32))
                                           for k in raw)
@@ -438,15 +475,17 @@ def main(argv=None):
 
     # warm-up includes one full batch (its accumulators)
     _each(rs, lambda i, x: run_passes(x, max(a.warmup, ppc if a.warmup else 0)))
-    # one instrumented (untimed) pass on rank 0's context: traversal counters → algorithmic bytes per
-    # ray, per kernel (every rank's share is the same mix of rays)
-    ctr = r.RenderCounted()
-    ext_rays = ctr.rays - ctr.shadow_rays
-    ext_nodes = ctr.nodes_visited - ctr.shadow_nodes
-    ext_prims = ctr.prims_tested - ctr.shadow_prims
-    bytes_ext = B_NODE * ext_nodes + B_PRIM * ext_prims + B_RAY * ext_rays
-    bytes_sh = B_NODE * ctr.shadow_nodes + B_PRIM * ctr.shadow_prims + B_RAY * ctr.shadow_rays
-    bytes_all = bytes_ext + bytes_sh + B_SHADE * ctr.shading_fetches
+    # --full: one instrumented (untimed) pass on rank 0's context: traversal counters → algorithmic bytes
+    # per ray, per kernel (every rank's share is the same mix of rays)
+    ctr = r.RenderCounted() if a.full else None
+    if ctr is not None:
+        ext_rays = ctr.rays - ctr.shadow_rays
+        ext_nodes = ctr.nodes_visited - ctr.shadow_nodes
+        ext_prims = ctr.prims_tested - ctr.shadow_prims
+        bytes_ext = B_NODE * ext_nodes + B_PRIM * ext_prims + B_RAY * ext_rays
+        bytes_sh = B_NODE * ctr.shadow_nodes + B_PRIM * ctr.shadow_prims + B_RAY * ctr.shadow_rays
+        bytes_all = bytes_ext + bytes_sh + B_SHADE * ctr.shading_fetches
+    # the timed steps start from an empty Buffer at pass 1, whatever ran before them
     _each(rs, lambda i, x: x.ResetBuffer())
 
     def timing_on(i, x):
@@ -541,6 +580,8 @@ def main(argv=None):
         return
     for x in rs[1:]:
         x.close()
+    # what the timed steps computed (after the gather: every rank's tiles), before anything else renders
+    dumped = dump_outputs(a.dump_outputs, r.ReadBuffer()) if a.dump_outputs else None
 
     value = total_rays / elapsed / 1e6
     lib_id = library_id()
@@ -552,35 +593,60 @@ def main(argv=None):
     # closest-hit class is k_wf_trace_lanes<COUNT> on triangle scenes)
     names = ["k_wf_camera", trace_name, shade_name, shadow_name,
              "k_wf_finalize", "k_render_pass<false, false>", "k_wf_nee_accum", "-"]
-    # the closest-hit kernel is the dominant one by design (on a multi-GPU shard the shadow
-    # passes run beside it on a second stream, so their event spans overlap it)
-    # (C3 / C2: the kernel with the most time)
-    dom = _abi.K_TRACE if klaunch[_abi.K_TRACE] and a.workload == "c4" else int(np.argmax(kms))
-    # algorithmic bytes of the dominant kernel over the timed region: the counted pass' bytes per
-    # ray of that kernel's ray class × the rays it traced (same scene/seed/spp → same ray mix)
-    if dom == _abi.K_TRACE:
-        per_ray, kind_rays = bytes_ext / max(ext_rays, 1), ext_rays
-    elif dom == _abi.K_SHADOW:
-        per_ray, kind_rays = bytes_sh / max(ctr.shadow_rays, 1), ctr.shadow_rays
-    else:
-        per_ray, kind_rays = bytes_all / max(ctr.rays, 1), ctr.rays
-    frac_rays = kind_rays / max(ctr.rays, 1)
-    dom_bytes = per_ray * rays * frac_rays
-    avg_launch_ms = kms[dom] / max(klaunch[dom], 1)
-    achieved_gbs = dom_bytes / (kms[dom] * 1e-3) / 1e9
-    rays_per_launch = rays * frac_rays / max(klaunch[dom], 1)
-    traffic, traffic_src = None, None
-    pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json" if a.workload == "c4" else f"pmc_traffic_{a.workload}.json")
-    if os.path.exists(pmc):
-        with open(pmc) as f:
-            tj = json.load(f)
-        if tj.get("kernel") == names[dom] and tj.get("workload_tris") == scene.Compile().num_triangles:
-            traffic = round(tj["traffic_bytes_per_ray"] * rays_per_launch)
-            traffic_src = {"tag": tj.get("tag"), "library": tj.get("library"),
-                           "same_library": tj.get("library") is not None and tj.get("library") == library_id()}
-    # compulsory bytes of one launch: each ray's queue entry (origin, direction: 32 B) read and its
-    # hit (16 B) written once, the traversal footprint (BVH nodes + leaf chunks) read once
-    compulsory = rays_per_launch * 48 + st.traversal_bytes
+
+    def l2_roofline():   # --full: the dominant kernel's algorithmic bytes (counted pass) over its timed launches
+        # the closest-hit kernel is the dominant one by design (on a multi-GPU shard the shadow
+        # passes run beside it on a second stream, so their event spans overlap it)
+        # (C3 / C2: the kernel with the most time)
+        dom = _abi.K_TRACE if klaunch[_abi.K_TRACE] and a.workload == "c4" else int(np.argmax(kms))
+        # algorithmic bytes of the dominant kernel over the timed region: the counted pass' bytes per
+        # ray of that kernel's ray class × the rays it traced (same scene/seed/spp → same ray mix)
+        if dom == _abi.K_TRACE:
+            per_ray, kind_rays = bytes_ext / max(ext_rays, 1), ext_rays
+        elif dom == _abi.K_SHADOW:
+            per_ray, kind_rays = bytes_sh / max(ctr.shadow_rays, 1), ctr.shadow_rays
+        else:
+            per_ray, kind_rays = bytes_all / max(ctr.rays, 1), ctr.rays
+        frac_rays = kind_rays / max(ctr.rays, 1)
+        dom_bytes = per_ray * rays * frac_rays
+        avg_launch_ms = kms[dom] / max(klaunch[dom], 1)
+        achieved_gbs = dom_bytes / (kms[dom] * 1e-3) / 1e9
+        rays_per_launch = rays * frac_rays / max(klaunch[dom], 1)
+        traffic, traffic_src = None, None
+        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json" if a.workload == "c4" else f"pmc_traffic_{a.workload}.json")
+        if os.path.exists(pmc):
+            with open(pmc) as f:
+                tj = json.load(f)
+            if tj.get("kernel") == names[dom] and tj.get("workload_tris") == scene.Compile().num_triangles:
+                traffic = round(tj["traffic_bytes_per_ray"] * rays_per_launch)
+                traffic_src = {"tag": tj.get("tag"), "library": tj.get("library"),
+                               "same_library": tj.get("library") is not None and tj.get("library") == library_id()}
+        # compulsory bytes of one launch: each ray's queue entry (origin, direction: 32 B) read and its
+        # hit (16 B) written once, the traversal footprint (BVH nodes + leaf chunks) read once
+        compulsory = rays_per_launch * 48 + st.traversal_bytes
+        return {
+            "bound": "l2", "kernel": names[dom],
+            "achieved": round(achieved_gbs, 2), "peak": L2_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved_gbs / L2_PEAK_GBS, 5), "traffic": traffic,
+            "traffic_kind": "L2-fabric bytes per launch (FETCH_SIZE x2 + WRITE_SIZE; Infinity-Cache hits included), "
+                            "profiles/pmc_traffic.json, same workload",
+            "traffic_source": traffic_src,
+            "compulsory_bytes_per_launch": round(compulsory),
+            "traffic_over_compulsory": None if traffic is None else round(traffic / compulsory, 3),
+            "traffic_frac_of_hbm_peak": None if traffic is None else
+            round(traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            "avg_launch_ms": round(float(avg_launch_ms), 4), "launches": int(klaunch[dom]),
+            "bytes_per_launch": round(dom_bytes / max(klaunch[dom], 1)),
+            "bytes_per_ray": round(per_ray, 2),
+            "rays_per_launch": round(rays_per_launch),
+            "nodes_per_ray": round((ext_nodes if dom == _abi.K_TRACE else ctr.nodes_visited) /
+                                   max(ext_rays if dom == _abi.K_TRACE else ctr.rays, 1), 3),
+            "prims_per_ray": round((ext_prims if dom == _abi.K_TRACE else ctr.prims_tested) /
+                                   max(ext_rays if dom == _abi.K_TRACE else ctr.rays, 1), 3),
+            "all_kernels_bytes_per_ray": round(bytes_all / max(ctr.rays, 1), 2),
+            "pass_achieved_gbs": round(bytes_all / max(ctr.rays, 1) * rays / (kernel_ms * 1e-3) / 1e9, 2),
+        }
+
     out = {
         "metric": METRIC,
         "value": round(value, 3),
@@ -611,8 +677,9 @@ def main(argv=None):
             "passes_per_call": ppc,
             "camera_samples_per_s": round(W * H * cam_spp * a.steps / elapsed, 1),
             "rays_per_camera_sample": round(total_rays / (W * H * cam_spp * a.steps), 3),
-            "shadow_ray_fraction": round(ctr.shadow_rays / max(ctr.rays, 1), 4),
-            "lit_shadow_rays_per_step": int(ctr.lit_shadow_rays), "accum_runs_per_step": int(ctr.accum_runs),
+            **({"shadow_ray_fraction": round(ctr.shadow_rays / max(ctr.rays, 1), 4),
+                "lit_shadow_rays_per_step": int(ctr.lit_shadow_rays), "accum_runs_per_step": int(ctr.accum_runs)}
+               if ctr is not None else {}),
             "engine": a.engine, "scene_build_s": round(t_scene, 3), "bvh_build_ms": round(build_ms, 1),
             "scene_upload_s": round(t_up, 3), "contexts_upload_ms": upload_ms,
             "mesh_source": None if a.workload == "c2" else a.mesh_source, **(obj_info or {}),
@@ -623,28 +690,9 @@ def main(argv=None):
         "scale_detail": scale_block(contexts, gather_ms if mode != "dist" else
                                     max((c["gather_ms"] or 0.0) for c in contexts) if gather else None, elapsed),
         "library": lib_id,
-        "roofline": {
-            "bound": "l2", "kernel": names[dom],
-            "achieved": round(achieved_gbs, 2), "peak": L2_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved_gbs / L2_PEAK_GBS, 5), "traffic": traffic,
-            "traffic_kind": "L2-fabric bytes per launch (FETCH_SIZE x2 + WRITE_SIZE; Infinity-Cache hits included), "
-                            "profiles/pmc_traffic.json, same workload",
-            "traffic_source": traffic_src,
-            "compulsory_bytes_per_launch": round(compulsory),
-            "traffic_over_compulsory": None if traffic is None else round(traffic / compulsory, 3),
-            "traffic_frac_of_hbm_peak": None if traffic is None else
-            round(traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            "avg_launch_ms": round(float(avg_launch_ms), 4), "launches": int(klaunch[dom]),
-            "bytes_per_launch": round(dom_bytes / max(klaunch[dom], 1)),
-            "bytes_per_ray": round(per_ray, 2),
-            "rays_per_launch": round(rays_per_launch),
-            "nodes_per_ray": round((ext_nodes if dom == _abi.K_TRACE else ctr.nodes_visited) /
-                                   max(ext_rays if dom == _abi.K_TRACE else ctr.rays, 1), 3),
-            "prims_per_ray": round((ext_prims if dom == _abi.K_TRACE else ctr.prims_tested) /
-                                   max(ext_rays if dom == _abi.K_TRACE else ctr.rays, 1), 3),
-            "all_kernels_bytes_per_ray": round(bytes_all / max(ctr.rays, 1), 2),
-            "pass_achieved_gbs": round(bytes_all / max(ctr.rays, 1) * rays / (kernel_ms * 1e-3) / 1e9, 2),
-        },
+        "full": bool(a.full),
+        **({"roofline": l2_roofline()} if a.full else {}),
+        **({"dumped": dumped} if dumped else {}),
     }
 
     def whole_traffic(rays_timed):   # C2 / C5 (kernel "whole pass"): L2-fabric bytes per step, all kernels
@@ -755,7 +803,7 @@ def main(argv=None):
                 blk["mix_library"] = vm.get("library")
         return blk
 
-    if a.workload == "c4":
+    if a.full and a.workload == "c4":
         out["roofline"]["shade"] = shade_roofline()
         # the same pass priced by VALU issue (the C2 / C5 lines' bound): the closest-hit kernel is bound by its
         # dependent loads and by VALU issue together (profiles/r06q_wave_states.txt), so both fractions are shown
@@ -765,7 +813,7 @@ def main(argv=None):
             "dominant_kernel_valu_issue_frac_under_counters", "pass_valu_issue_frac_under_counters", "mix_source",
             "mix_stale", "note") if k in vi}
 
-    if a.workload in ("c2", "c5"):
+    if a.full and a.workload in ("c2", "c5"):
         # C2 (fp64 sampler math, 16 children per camera hit) and C5 (the fp64 Volume / SDF marches) are
         # bound by VALU issue, not by bytes: the pass' measured VALU issue cycles per ray (instruction mix
         # by kind from PMC counters, priced at each kind's issue cost) over the pass' kernel time, against
@@ -781,7 +829,8 @@ def main(argv=None):
     # full frame at the bench's own spp per pass (one chunk, as each timed step runs it), pass index 1 (the
     # first timed step's), against the oracle on a strided pixel set sized to ~cpu_seconds of CPU work
     # (C3 and C2 too: the same leg on their frames; C5's adaptive phase is checked by the GPU tests)
-    if world == 1 and a.workload in ("c4", "c3", "c2") and a.adaptive == 0 and (a.cpu_seconds > 0 or not a.no_parity):
+    if (a.full and world == 1 and a.workload in ("c4", "c3", "c2") and a.adaptive == 0
+            and (a.cpu_seconds > 0 or not a.no_parity)):
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         osc = O.OracleScene(scene)

@@ -36,6 +36,39 @@ def test_parse_defaults_and_gpus_bound():
         bench.parse(["--gpus", "0"])
 
 
+def test_full_and_dump_options():
+    """A plain run is lean: --full is off unless given; --dump-outputs names a folder."""
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "d", "--steps", "3"])
+    assert a.full is True and a.dump_outputs == "d" and a.steps == 3
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs' files: float64 M, V, N at the listed pixels; every pixel of a small frame, and of
+    a frame too large for the size limit a fixed sample (the same on every call) that stays below it."""
+    import numpy as np
+    from ptsharp_amd.renderer import Buffer
+    w, h = 40, 24
+    b = Buffer(w, h)
+    rng = np.random.default_rng(5)
+    b.M[...] = rng.random(b.M.shape)
+    b.V[...] = rng.random(b.V.shape)
+    b.N[...] = rng.integers(0, 100, b.N.shape)
+    info = bench.dump_outputs(str(tmp_path / "out"), b)
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("M", "V", "N", "pixels")}
+    assert info["pixels"] == info["of"] == w * h and info["arrays"] == ["M", "N", "V", "pixels"]
+    assert all(x.dtype == np.float64 for x in got.values())
+    assert np.array_equal(got["pixels"], np.arange(w * h))
+    assert np.array_equal(got["M"], b.M.reshape(-1, 3)) and np.array_equal(got["V"], b.V.reshape(-1, 3))
+    assert np.array_equal(got["N"], b.N.reshape(-1))
+    n = 3840 * 2160
+    idx = bench.dump_pixels(n)
+    assert len(idx) * bench.DUMP_PIXEL_BYTES <= bench.DUMP_MAX_BYTES < 64 * 10**6
+    assert len(idx) < n and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(idx, bench.dump_pixels(n))
+
+
 def test_each_runs_every_context_and_raises():
     import threading
     together = threading.Barrier(4, timeout=30)   # passes only if the four calls run concurrently

@@ -201,6 +201,35 @@ def test_bench_group_form_one_gpu(gpu, tmp_path):
     assert j["value"] > 0
 
 
+def test_bench_plain_and_full_dump_the_same_outputs(gpu, tmp_path):
+    """A plain `bench.py` run prints the headline line without the roofline / CPU-baseline legs and
+    --dump-outputs writes the Buffer its timed steps left (one Welford sample per step, the pass' mean of
+    its spp camera samples, on every pixel: the warm-up's are gone); the same
+    arguments with --full add the roofline and dump the same arrays, bit for bit."""
+    import json
+
+    import numpy as np
+
+    import bench
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "2", "--width", "256", "--height", "128",
+              "--tris", "20000", "--mesh-source", "generator"]
+    lines, dumps = [], []
+    for name, extra in (("plain", []), ("full", ["--full", "--cpu-seconds", "0", "--no-parity"])):
+        out = tmp_path / f"{name}.json"
+        bench.main(common + extra + ["--dump-outputs", str(tmp_path / name), "--json-out", str(out)])
+        lines.append(json.loads(out.read_text()))
+        dumps.append({n: np.load(tmp_path / name / f"{n}.npy") for n in ("M", "V", "N", "pixels")})
+    plain, full = lines
+    for j in lines:
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "Msamples/s"
+        assert j["config"]["kernel_ms_per_step"]
+    assert plain["full"] is False and not {"roofline", "cpu_baseline", "parity"} & set(plain)
+    assert full["full"] is True and full["roofline"]["bytes_per_ray"] > 0
+    assert len(dumps[0]["pixels"]) == 256 * 128 and (dumps[0]["N"] == 2).all() and dumps[0]["M"].sum() > 0
+    for n in dumps[0]:
+        assert dumps[0][n].dtype == np.float64 and np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def test_group_pass_equals_plain_pass(gpu):
     """The group form's render (pt_comm_init_all over one context, passes issued from a worker thread,
     pt_comm_gather_all) leaves the Buffer a plain context leaves, bit for bit."""

@@ -15,10 +15,10 @@ for V in "${VS[@]}"; do
   if [ "$PARITY" != "none" ]; then
     timeout -k 10 600 python -u -m pytest $PARITY -x -q -m gpu --timeout 240 --timeout-method thread > $D/tests_$NAME.log 2>&1 || exit 1
   fi
-  [ -z "$NOBENCH" ] && { timeout -k 10 300 python -u bench.py --steps ${STEPS:-16} --warmup 2 --cpu-seconds 0 --no-parity --json-out $D/c4_$NAME.json > $D/c4_$NAME.log 2>&1 || exit 1; }
-  [ -n "$C2" ] && { timeout -k 10 300 python -u bench.py --workload c2 --steps 6 --warmup 1 --cpu-seconds 0 --no-parity --json-out $D/c2_$NAME.json > $D/c2_$NAME.log 2>&1 || exit 1; }
-  [ -n "$SHARD" ] && { timeout -k 10 300 python -u bench.py --shard 0/8 --steps 32 --warmup 2 --cpu-seconds 0 --no-parity --json-out $D/shard8_$NAME.json > $D/shard8_$NAME.log 2>&1 || exit 1; }
-  [ -n "$C5" ] && { timeout -k 10 400 python -u bench.py --workload c5 --steps 1 --warmup 1 --cpu-seconds 0 --no-parity --json-out $D/c5_$NAME.json > $D/c5_$NAME.log 2>&1 || exit 1; }
+  [ -z "$NOBENCH" ] && { timeout -k 10 300 python -u bench.py --full --steps ${STEPS:-16} --warmup 2 --cpu-seconds 0 --no-parity --json-out $D/c4_$NAME.json > $D/c4_$NAME.log 2>&1 || exit 1; }
+  [ -n "$C2" ] && { timeout -k 10 300 python -u bench.py --full --workload c2 --steps 6 --warmup 1 --cpu-seconds 0 --no-parity --json-out $D/c2_$NAME.json > $D/c2_$NAME.log 2>&1 || exit 1; }
+  [ -n "$SHARD" ] && { timeout -k 10 300 python -u bench.py --full --shard 0/8 --steps 32 --warmup 2 --cpu-seconds 0 --no-parity --json-out $D/shard8_$NAME.json > $D/shard8_$NAME.log 2>&1 || exit 1; }
+  [ -n "$C5" ] && { timeout -k 10 400 python -u bench.py --full --workload c5 --steps 1 --warmup 1 --cpu-seconds 0 --no-parity --json-out $D/c5_$NAME.json > $D/c5_$NAME.log 2>&1 || exit 1; }
 done
 make -s -C ptsharp_amd/csrc clean >/dev/null && make -s -j16 -C ptsharp_amd/csrc > $D/build_final.log 2>&1
 exit 0

@@ -15,7 +15,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for L in "${LS[@]}"; do
     N=${L%%:*}; P=${L#*:}
     cp $P $CUR || { restore; exit 1; }
-    timeout -k 10 400 python -u bench.py $A --cpu-seconds 0 --no-parity --json-out $D/c5_${N}_$r.json > $D/c5_${N}_$r.log 2>&1 || { restore; exit 1; }
+    timeout -k 10 400 python -u bench.py --full $A --cpu-seconds 0 --no-parity --json-out $D/c5_${N}_$r.json > $D/c5_${N}_$r.log 2>&1 || { restore; exit 1; }
     echo "$N round $r: $(python -c "import json;j=json.load(open('$D/c5_${N}_$r.json'));print(j['value'],j['config']['kernel_ms_per_step'],j['roofline'].get('volume_march_clock',{}).get('share'))")" >> $D/summary.txt
   done
 done
@@ -23,7 +23,7 @@ if [ "${TRACE:-0}" = 1 ]; then
   for L in "${LS[@]}"; do
     N=${L%%:*}; P=${L#*:}
     cp $P $CUR || { restore; exit 1; }
-    timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/kt_$N -o kt -- python3 bench.py $A --cpu-seconds 0 --no-parity --json-out $D/c5_${N}_trace.json > $D/c5_${N}_trace.log 2>&1 || { restore; exit 1; }
+    timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/kt_$N -o kt -- python3 bench.py --full $A --cpu-seconds 0 --no-parity --json-out $D/c5_${N}_trace.json > $D/c5_${N}_trace.log 2>&1 || { restore; exit 1; }
     find $D/kt_$N -name '*kernel_stats.csv' -exec cp {} $D/kt_${N}_kernel_stats.csv \;
   done
 fi

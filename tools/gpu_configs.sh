@@ -8,8 +8,8 @@ export TMPDIR=/tmp
 T=${1:-cfg}
 D=gpurun_out/$T
 mkdir -p $D
-C3="--workload c3 --steps 8 --warmup 1 --cpu-seconds 0 --no-parity"
-C2="--workload c2 --steps 4 --warmup 1 --spp 16 --cpu-seconds 0 --no-parity"
+C3="--full --workload c3 --steps 8 --warmup 1 --cpu-seconds 0 --no-parity"
+C2="--full --workload c2 --steps 4 --warmup 1 --spp 16 --cpu-seconds 0 --no-parity"
 timeout -k 10 300 python bench.py $C3 --json-out $D/bench_c3.json > $D/bench_c3.log 2>&1 && \
 timeout -k 10 300 python bench.py $C2 --json-out $D/bench_c2.json > $D/bench_c2.log 2>&1 && \
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d $D/trace_c3 -o t --output-format csv -- python3 bench.py $C3 --json-out $D/bench_c3_trace.json > $D/trace_c3.log 2>&1 && \

@@ -11,5 +11,5 @@ rc=$?
 echo "pytest rc=$rc" >> $D/tests.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.log 2>&1 || exit 1
-timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 --json-out $D/bench.json > $D/bench.log 2>&1 || exit 1
+timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 --json-out $D/bench.json > $D/bench.log 2>&1 || exit 1
 exit 0

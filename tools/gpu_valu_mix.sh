@@ -12,7 +12,7 @@ D=gpurun_out/$T; mkdir -p $D
 PA="SQ_INSTS_VALU SQ_INSTS_VALU_FLOPS_FP32 SQ_INSTS_VALU_FLOPS_FP64 SQ_INSTS_VALU_FLOPS_FP32_TRANS SQ_INSTS_VALU_FLOPS_FP64_TRANS SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 GRBM_GUI_ACTIVE"
 PB="SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT GRBM_GUI_ACTIVE"
 for W in $WL; do
-  A="--workload $W --steps 1 --warmup 0 --cpu-seconds 0 --no-parity"
+  A="--full --workload $W --steps 1 --warmup 0 --cpu-seconds 0 --no-parity"
   [ "$W" = c2 ] && A="$A --spp 16"
   timeout -k 10 400 python3 bench.py $A --json-out $D/bench_$W.json > $D/bench_$W.log 2>&1 || exit 1
   timeout -s KILL 400 rocprofv3 --pmc $PA --kernel-trace -d $D/${W}_a -o p --output-format csv -- python3 bench.py $A --json-out $D/bench_${W}_a.json > $D/${W}_a.log 2>&1 || exit 1
