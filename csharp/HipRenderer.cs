@@ -27,6 +27,7 @@ namespace PTSharpCore
         public const int PT_ERR_UNSUPPORTED = -4;
         public const int PT_PASS_KERNEL_TIMING = 1, PT_PASS_SERIAL = 2;
         public const int PT_MARCH_LANE = 1, PT_MARCH_WAVE = 2;   // pt_intersect / pt_occluded flags
+        public const int PT_IMAGE_RGB8 = 0, PT_IMAGE_RGBA8 = 1;  // pt_image_format (pt_read_image)
         public const int SHAPE_SPHERE = 0, SHAPE_CUBE = 1, SHAPE_PLANE = 2, SHAPE_TRIANGLE = 3, SHAPE_MESH = 4;
         public const int SHAPE_SDF = 5, SHAPE_VOLUME = 6, SHAPE_TRANSFORMED = 7;
 
@@ -168,6 +169,8 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_synchronize(IntPtr ctx);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_buffer(IntPtr ctx, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_buffer(IntPtr ctx, double[] m, double[] v, int[] n);
+        // channel: (int)Channel (Buffer.cs:8-16 = pt_channel); format: PT_IMAGE_RGB8 / PT_IMAGE_RGBA8 (ABI 10)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_image(IntPtr ctx, int channel, int format, byte[] rgb);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_reset_buffer(IntPtr ctx);
@@ -213,6 +216,10 @@ namespace PTSharpCore
         /// <summary>32x32 tiles this renderer draws (tile id = ty * ceil(W/32) + tx); null = the whole
         /// image.  A multi-GPU rank draws TilesForRank(W, H, rank, world) (SURVEY.md §8e).</summary>
         public int[] Tiles = null;
+        /// <summary>IterativeRender takes each pass' image from ReadImage (pt_read_image: the channel resolved
+        /// on the device, 4 B per pixel copied back instead of 52) and fills Renderer.PBuffer once, after
+        /// the last pass.  False keeps the ReadBuffer + Buffer.Image path after every pass.</summary>
+        public bool DeviceImages = false;
         internal IntPtr ctx;
         int W, H, pass;
         internal int Width => W;
@@ -518,12 +525,37 @@ namespace PTSharpCore
             {
                 Console.WriteLine("Iteration " + i + " of " + iter);
                 if (NumCPU == 1) Render(); else RenderParallel();   // Renderer.cs:712-719
-                ReadBuffer();
-                colour = Renderer.PBuffer.Image(Channel.ColorChannel);
+                if (DeviceImages) colour = ReadBitmap(Channel.ColorChannel);
+                else
+                {
+                    ReadBuffer();
+                    colour = Renderer.PBuffer.Image(Channel.ColorChannel);
+                }
                 using var stream = System.IO.File.OpenWrite(string.Format(pathTemplate, i));
                 colour.Encode(SKEncodedImageFormat.Png, 100).SaveTo(stream);
             }
+            if (DeviceImages) ReadBuffer();   // Renderer.PBuffer once, after the last pass
             return colour;
+        }
+
+        /// <summary>Buffer.Image(channel) (Buffer.cs:134-202) resolved on the device (pt_read_image): row-major
+        /// [H][W][3] bytes, or [H][W][4] with A = 255 when rgba.  The Buffer is the context's as it stands: this
+        /// renderer's tiles, or the whole frame on the root after a gather.</summary>
+        public byte[] ReadImage(Channel channel, bool rgba)
+        {
+            var px = new byte[W * H * (rgba ? 4 : 3)];
+            PtHip.Check(PtHip.pt_read_image(ctx, (int)channel, rgba ? PtHip.PT_IMAGE_RGBA8 : PtHip.PT_IMAGE_RGB8, px), "pt_read_image");
+            return px;
+        }
+
+        /// <summary>ReadImage as the SKBitmap Buffer.Image returns (SKColor(r, g, b, 255), Buffer.cs:160).</summary>
+        public SKBitmap ReadBitmap(Channel channel)
+        {
+            var px = ReadImage(channel, true);
+            var bmp = new SKBitmap(new SKImageInfo(W, H, SKColorType.Rgba8888, SKAlphaType.Opaque));
+            for (int y = 0; y < H; y++)   // row by row: a bitmap's RowBytes may exceed 4 W
+                Marshal.Copy(px, y * W * 4, IntPtr.Add(bmp.GetPixels(), y * bmp.RowBytes), W * 4);
+            return bmp;
         }
 
         public void Dispose() { if (ctx != IntPtr.Zero) { PtHip.pt_destroy(ctx); ctx = IntPtr.Zero; } }
@@ -569,6 +601,8 @@ namespace PTSharpCore
         public bool StratifiedSampling { set { foreach (var r in parts) r.StratifiedSampling = value; } }
         public ulong Seed { set { foreach (var r in parts) r.Seed = value; } }
         public int NumCPU { get => parts[0].NumCPU; set { foreach (var r in parts) r.NumCPU = value; } }
+        /// <summary>As HipRenderer.DeviceImages: gather, resolve on device 0, one ReadBuffer after the last pass.</summary>
+        public bool DeviceImages = false;
 
         /// <summary>One RenderParallel pass on every GPU, one host thread per context.</summary>
         public void RenderParallel() => Parallel.For(0, parts.Length, new ParallelOptions { MaxDegreeOfParallelism = parts.Length },
@@ -582,10 +616,19 @@ namespace PTSharpCore
         /// <summary>Sum the ranks' disjoint tiles onto device 0 and copy them into Renderer.PBuffer.</summary>
         public void ReadBuffer()
         {
-            // device 0 then holds every rank's tiles; its next pass clears the others' pixels again
-            // (ptsharp_hip.h "Multi-GPU"), so the gather can follow every pass
-            PtHip.Check(PtHip.pt_comm_gather_all(ctxs, ctxs.Length, 0), "pt_comm_gather_all");
+            Gather();
             parts[0].ReadBuffer();
+        }
+
+        // device 0 then holds every rank's tiles; its next pass clears the others' pixels again
+        // (ptsharp_hip.h "Multi-GPU"), so the gather can follow every pass
+        void Gather() => PtHip.Check(PtHip.pt_comm_gather_all(ctxs, ctxs.Length, 0), "pt_comm_gather_all");
+
+        /// <summary>The whole frame's Buffer.Image(channel), gathered onto device 0 and resolved there.</summary>
+        public byte[] ReadImage(Channel channel, bool rgba)
+        {
+            Gather();
+            return parts[0].ReadImage(channel, rgba);
         }
 
         public SKBitmap IterativeRender(string pathTemplate, int iter)
@@ -595,11 +638,21 @@ namespace PTSharpCore
             {
                 Console.WriteLine("Iteration " + i + " of " + iter);
                 if (NumCPU == 1) Render(); else RenderParallel();   // Renderer.cs:712-719
-                ReadBuffer();
-                colour = Renderer.PBuffer.Image(Channel.ColorChannel);
+                if (DeviceImages)
+                {
+                    Gather();   // device 0 holds the whole frame and resolves it
+                    colour = parts[0].ReadBitmap(Channel.ColorChannel);
+                }
+                else
+                {
+                    ReadBuffer();
+                    colour = Renderer.PBuffer.Image(Channel.ColorChannel);
+                }
                 using var stream = System.IO.File.OpenWrite(string.Format(pathTemplate, i));
                 colour.Encode(SKEncodedImageFormat.Png, 100).SaveTo(stream);
             }
+            // Renderer.PBuffer once: the last pass' gather left the whole frame on device 0
+            if (DeviceImages) { if (iter >= 1) parts[0].ReadBuffer(); else ReadBuffer(); }
             return colour;
         }
 

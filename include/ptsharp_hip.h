@@ -20,6 +20,8 @@
  *                        → Scene.Intersect → Tree/IShape.Intersect        Scene.cs:75-79, Tree.cs:31-128
  *                        → Buffer.AddSample (Welford)                     Buffer.cs:33-44,94-97
  *   pt_read_buffer     reading Renderer.PBuffer pixels {Samples, M, V}     Buffer.cs:18-58, Renderer.cs:20
+ *   pt_read_image      Renderer.PBuffer.Image(channel), resolved on the    Buffer.cs:134-282
+ *                      device to 8-bit RGB / RGBA
  *   pt_reset_buffer    Renderer.PBuffer = new Buffer(w,h)                  Renderer.cs:41
  *   pt_write_buffer    resuming IterativeRender from a saved PBuffer       Renderer.cs:702-765
  *   pt_read_tiles /    (new) a tile list's pixels, packed: progressive    SURVEY.md §8e
@@ -51,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 9
+#define PT_ABI_VERSION 10
 
 typedef enum pt_status {
     PT_OK = 0,
@@ -283,6 +285,9 @@ typedef enum pt_kernel_class {
     PT_K_COUNT = 7
 } pt_kernel_class;
 #define PT_K_SLOTS 8           /* length of pt_stats.kernel_ms / kernel_launches */
+/* Slot 7 is not a pass' kernel class: the last pt_read_image's kernels (device time between two
+ * hipEvents, always taken, and their launches).  Like the other slots it is cleared by the next pass. */
+#define PT_K_IMAGE 7
 
 /* Both engines compute identical per-ray arithmetic; they differ in scheduling. */
 typedef enum pt_engine {
@@ -328,6 +333,20 @@ int pt_read_buffer(void* ctx, double* out_m, double* out_v, int32_t* out_n);
  * IterativeRender from a saved Buffer (Renderer.cs:702-765 keeps accumulating into
  * Renderer.PBuffer pass after pass; a checkpoint is that Buffer). */
 int pt_write_buffer(void* ctx, const double* m, const double* v, const int32_t* n);
+
+/* Buffer.Image(channel) (Buffer.cs:134-282) resolved on the device: the context's Buffer as it
+ * stands (a tile-sharded context: its own tiles, zero pixels elsewhere; the root after a gather:
+ * the whole frame) as 8-bit colour, row-major, into the caller's `out`: [H][W][3] (PT_IMAGE_RGB8)
+ * or [H][W][4] with A = 255 (PT_IMAGE_RGBA8, the SKColor(r, g, b, 255) of Buffer.cs:160).  Every
+ * channel ends in (byte)Math.Clamp(c·255, 0, 255) with a NaN mapped to 0; the arithmetic is fp64 in
+ * the reference's order (ptsharp_amd/csrc/pt_image.h).  Runs on the context's stream after every
+ * pass issued before it and synchronises before returning; it changes neither the Buffer nor any
+ * pass state, and needs no scene.  A NULL ctx or out, or a channel or format outside the enums:
+ * PT_ERR_INVALID_ARG, nothing launched. */
+typedef enum pt_channel { PT_CHANNEL_COLOR = 0, PT_CHANNEL_VARIANCE = 1, PT_CHANNEL_STDDEV = 2,
+                          PT_CHANNEL_SAMPLES = 3, PT_CHANNEL_ALBEDO = 4, PT_CHANNEL_NORMAL = 5 } pt_channel;  /* Buffer.cs:8-16 */
+typedef enum pt_image_format { PT_IMAGE_RGB8 = 0, PT_IMAGE_RGBA8 = 1 } pt_image_format;
+int pt_read_image(void* ctx, int32_t channel, int32_t format, uint8_t* out);
 
 /* The Buffer pixels of `num_tiles` 32x32 tiles, packed: m, v [num_tiles][32][32][3], n
  * [num_tiles][32][32], row-major inside a tile (entry (t, r, c) = pixel (32·(tiles[t] mod

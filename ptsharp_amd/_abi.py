@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libptsharp_hip.so")
 
-ABI_VERSION = 9   # PT_ABI_VERSION
+ABI_VERSION = 10   # PT_ABI_VERSION
 PT_OK = 0
 PT_ERR_INVALID_ARG = -1
 PT_ERR_HIP = -2
@@ -27,6 +27,8 @@ PASS_KERNEL_TIMING = 1
 PASS_SERIAL = 2  # Renderer.Render semantics (Renderer.cs:80-198)
 K_CAMERA, K_TRACE, K_SHADE, K_SHADOW, K_FINALIZE, K_MEGAKERNEL, K_ACCUM = range(7)
 K_SLOTS = 8   # PT_K_SLOTS
+K_IMAGE = 7   # PT_K_IMAGE: the last pt_read_image's kernels
+IMAGE_RGB8, IMAGE_RGBA8 = 0, 1   # pt_image_format (pt_channel is renderer.Channel)
 
 SHAPE_SPHERE, SHAPE_CUBE, SHAPE_PLANE, SHAPE_TRIANGLE, SHAPE_MESH = 0, 1, 2, 3, 4
 SHAPE_SDF, SHAPE_VOLUME, SHAPE_TRANSFORMED = 5, 6, 7
@@ -148,6 +150,7 @@ SIGNATURES = {
     "pt_reset_buffer": (C.c_int, [C.c_void_p]),
     "pt_read_buffer": (C.c_int, [C.c_void_p, _d, _d, _i]),
     "pt_write_buffer": (C.c_int, [C.c_void_p, _d, _d, _i]),
+    "pt_read_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "pt_read_tiles": (C.c_int, [C.c_void_p, _i, C.c_int32, _d, _d, _i]),
     "pt_write_tiles": (C.c_int, [C.c_void_p, _i, C.c_int32, _d, _d, _i]),
     "pt_stats_get": (C.c_int, [C.c_void_p, C.POINTER(pt_stats)]),

@@ -76,6 +76,10 @@ hipError_t launch_render_pass(const DevScene& S, const DevCamera& cam, const Dev
                               const DevBuffer& B, int num_tiles, bool count, hipStream_t stream);
 hipError_t launch_intersect(const DevScene& S, uint32_t n, const float* o3, const float* d3, const double* tl,
                             double* out_t, int32_t* out_kind, hipStream_t stream);
+// pt_image.hip
+size_t image_staging_bytes(int32_t W, int32_t H);
+hipError_t launch_image_resolve(int channel, int format, const double* m, const double* v, const int32_t* n,
+                                int32_t* max_n, uint32_t* out, int32_t W, int32_t H, hipStream_t stream);
 }
 
 namespace {
@@ -148,6 +152,7 @@ struct Ctx {
     int32_t* d_n = nullptr;
     unsigned long long* d_counters = nullptr;   // [pt::kCounterAllocWords] the pass' counters (pt::DevBuffer::counters)
     unsigned long long* h_counters = nullptr;   // [pt::kCounterAllocWords] pinned: their read-back
+    uint8_t* d_image = nullptr;                 // pt_read_image's staging image, then its max-N word (first use)
     int32_t* d_tiles = nullptr;
     int32_t tiles_cap = 0;
     std::vector<int32_t> h_tiles;               // the tile list in d_tiles (uploaded when it changes)
@@ -865,7 +870,10 @@ int pt_device_count(int32_t* out_count) {
 int pt_create(const pt_device_opts* opts, void** out_ctx) {
     if (!opts || !out_ctx) return fail(PT_ERR_INVALID_ARG, "NULL argument");
     *out_ctx = nullptr;
-    if (opts->width <= 1 || opts->height <= 1) return fail(PT_ERR_INVALID_ARG, "width/height must be > 1");
+    // A Buffer one pixel wide or high can be loaded and resolved to an image, not rendered into
+    // (render_pass_impl); a single pixel is no image.
+    if (opts->width < 1 || opts->height < 1 || (opts->width == 1 && opts->height == 1))
+        return fail(PT_ERR_INVALID_ARG, "width/height must be >= 1 and not both 1");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PT_ERR_NO_DEVICE, "no HIP device");
     if (opts->device < 0 || opts->device >= ndev) return fail(PT_ERR_INVALID_ARG, "device ordinal out of range");
@@ -1435,6 +1443,8 @@ static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* s
                             pt_trace_counters* counted) {
     if (!c || !camera || !sampler || !pass) return fail(PT_ERR_INVALID_ARG, "NULL argument");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "pt_render_pass before pt_upload_scene");
+    if (c->width <= 1 || c->height <= 1)   // Camera.CastRay divides by w - 1 and h - 1 (Camera.cs:101-102)
+        return fail(PT_ERR_INVALID_ARG, "a pass needs width and height > 1");
     if (pass->spp <= 0) return fail(PT_ERR_INVALID_ARG, "spp must be >= 1");
     if (sampler->first_hit_samples <= 0 || sampler->max_bounces < 0) return fail(PT_ERR_INVALID_ARG, "bad sampler");
     if (sampler->specular_mode == PT_SPEC_ALL && sampler->max_bounces > 32)
@@ -1798,6 +1808,31 @@ int pt_write_buffer(void* ctx, const double* m, const double* v, const int32_t* 
     return PT_OK;
 }
 
+int pt_read_image(void* ctx, int32_t channel, int32_t format, uint8_t* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return fail(PT_ERR_INVALID_ARG, "NULL argument");
+    if (channel < PT_CHANNEL_COLOR || channel > PT_CHANNEL_NORMAL) return fail(PT_ERR_INVALID_ARG, "channel is not a pt_channel");
+    if (format != PT_IMAGE_RGB8 && format != PT_IMAGE_RGBA8) return fail(PT_ERR_INVALID_ARG, "format is not a pt_image_format");
+    PT_HIP(hipSetDevice(c->device));
+    const size_t P = (size_t)c->width * (size_t)c->height;
+    const size_t staging = pt::image_staging_bytes(c->width, c->height);
+    if (!c->d_image && hipMalloc(&c->d_image, staging + 16) != hipSuccess) {
+        c->d_image = nullptr;
+        return fail(PT_ERR_OUT_OF_MEMORY, "image staging allocation");
+    }
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_image_resolve(channel, format, c->d_m, c->d_v, c->d_n, (int32_t*)(c->d_image + staging),
+                                    (uint32_t*)c->d_image, c->width, c->height, c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    PT_HIP(hipMemcpyAsync(out, c->d_image, P * (format == PT_IMAGE_RGBA8 ? 4 : 3), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->stats.kernel_ms[PT_K_IMAGE] = ms;
+    c->stats.kernel_launches[PT_K_IMAGE] = channel == PT_CHANNEL_SAMPLES ? 2 : 1;
+    return PT_OK;
+}
+
 static int tile_workspace(Ctx* c);
 
 // Host copies of a tile list's packed {M, V, N} (see k_tiles_pack for the order).
@@ -1941,6 +1976,7 @@ void pt_destroy(void* ctx) {
     if (c->d_counters) (void)hipFree(c->d_counters);
     if (c->h_counters) (void)hipHostFree(c->h_counters);
     if (c->d_tiles) (void)hipFree(c->d_tiles);
+    if (c->d_image) (void)hipFree(c->d_image);
     if (c->d_own) (void)hipFree(c->d_own);
     for (void* p : {(void*)c->g_ids, (void*)c->g_m, (void*)c->g_v, (void*)c->g_n, (void*)c->g_cnts, (void*)c->g_all})
         if (p) (void)hipFree(p);

@@ -81,8 +81,26 @@ class Buffer:
         elif channel == Channel.SamplesChannel:
             mx = max(int(self.N.max()), 1)
             c = np.repeat((self.N / mx)[..., None], 3, axis=2)
+        elif channel == Channel.AlbedoChannel:  # CalculateAlbedo (Buffer.cs:240-282)
+            mx = self.M.max(axis=2, keepdims=True)  # NaN where a component is NaN
+            with np.errstate(invalid="ignore", divide="ignore"):
+                c = self.M / mx
+                c = np.where(c < 0, 0.0, np.where(c > 1, 1.0, c))  # Math.Clamp keeps a NaN (inf / inf)
+            c = np.where(np.isnan(mx) | (mx == 0), 0.0, c)
+        elif channel == Channel.NormalChannel:  # GetNormalAt + CalculateNormal (Buffer.cs:99-124,222-233)
+            p = np.zeros((self.H + 2, self.W + 2, 2), np.float64)  # GetPixelOrDefault: 0 outside the image
+            p[1:-1, 1:-1] = self.M[..., :2]
+            top, mid, bot = p[:-2], p[1:-1], p[2:]
+            L, X, R = slice(0, -2), slice(1, -1), slice(2, None)
+            with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                nx = (top[:, L, 0] + 2 * mid[:, L, 0] + bot[:, L, 0] - top[:, R, 0] - 2 * mid[:, R, 0] - bot[:, R, 0]) / 8.0
+                ny = (top[:, L, 1] + 2 * top[:, X, 1] + top[:, R, 1] - bot[:, L, 1] - 2 * bot[:, X, 1] - bot[:, R, 1]) / 8.0
+                length = np.sqrt(nx * nx + ny * ny + 1.0)
+                # new Vector(nx, ny, nz) holds floats (Vector.cs:222-225)
+                v = np.stack([nx / length, ny / length, 1.0 / length], axis=2).astype(np.float32).astype(np.float64)
+                c = np.stack([(v[..., 0] + 1.0) * 0.5, (v[..., 1] + 1.0) * 0.5, v[..., 2]], axis=2)
         else:
-            raise ValueError(f"channel {channel} is outside the render path (albedo/normal heuristics)")
+            raise ValueError(f"channel {channel} is not a Buffer channel")
         with np.errstate(invalid="ignore"):
             v = np.clip(c * 255, 0, 255)
         v = np.nan_to_num(v, nan=0.0)
@@ -123,6 +141,7 @@ class Renderer:
         self.Tiles = None        # optional 32x32 tile ids this context renders (multi-GPU sharding)
         self.Engine = _abi.ENGINE_AUTO  # scheduling only: both engines compute identical per-ray arithmetic
         self.Flags = 0                  # _abi.PASS_KERNEL_TIMING: per-kernel hipEvent timing in Stats()
+        self.DeviceImages = False       # IterativeRender: each pass' image from Image() (pt_read_image), PBuffer once at the end
         self.Verbose = False
         self._ctx = None
         self._lib = None
@@ -235,6 +254,14 @@ class Renderer:
                                             b.N.ctypes.data_as(C.POINTER(C.c_int32))), "pt_read_buffer")
         return b
 
+    def Image(self, channel: Channel = Channel.ColorChannel, rgba: bool = False) -> np.ndarray:
+        """Buffer.Image(channel) resolved on the device (pt_read_image): [H,W,3] uint8, or [H,W,4] with
+        A = 255.  The same bytes as ReadBuffer().Image(channel) for a seventeenth of the copy."""
+        out = np.empty((self.H, self.W, 4 if rgba else 3), np.uint8)
+        _abi.check(self._lib.pt_read_image(self._ctx, int(channel), _abi.IMAGE_RGBA8 if rgba else _abi.IMAGE_RGB8,
+                                           out.ctypes.data_as(C.POINTER(C.c_uint8))), "pt_read_image")
+        return out
+
     def LoadBuffer(self, buf: Buffer, passes_done: int) -> None:
         """Resume an IterativeRender from a saved Buffer (pt_write_buffer): later passes keep adding
         Welford samples to it, numbered from passes_done + 1 (the random streams are keyed by pass)."""
@@ -320,9 +347,13 @@ class Renderer:
             else:
                 self.RenderParallel()
             if pathTemplate:
-                img = self.ReadBuffer().Image(Channel.ColorChannel)
+                img = self.Image(Channel.ColorChannel) if self.DeviceImages else self.ReadBuffer().Image(Channel.ColorChannel)
                 write_png(pathTemplate.replace("{0}", str(i)), img)
-        if img is None:
+        if self.DeviceImages:
+            if img is None:
+                img = self.Image(Channel.ColorChannel)
+            self.ReadBuffer()  # Renderer.PBuffer once, after the last pass
+        elif img is None:
             img = self.ReadBuffer().Image(Channel.ColorChannel)
         return img
 
