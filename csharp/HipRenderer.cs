@@ -28,6 +28,7 @@ namespace PTSharpCore
         public const int PT_PASS_KERNEL_TIMING = 1, PT_PASS_SERIAL = 2;
         public const int PT_MARCH_LANE = 1, PT_MARCH_WAVE = 2;   // pt_intersect / pt_occluded flags
         public const int PT_IMAGE_RGB8 = 0, PT_IMAGE_RGBA8 = 1;  // pt_image_format (pt_read_image)
+        public const int PT_DENOISED_RGB8 = 0, PT_DENOISED_RGBA8 = 1, PT_DENOISED_COLOUR_F64 = 2, PT_DENOISED_VARIANCE_F64 = 3;  // pt_denoised_format
         public const int SHAPE_SPHERE = 0, SHAPE_CUBE = 1, SHAPE_PLANE = 2, SHAPE_TRIANGLE = 3, SHAPE_MESH = 4;
         public const int SHAPE_SDF = 5, SHAPE_VOLUME = 6, SHAPE_TRANSFORMED = 7;
 
@@ -154,6 +155,14 @@ namespace PTSharpCore
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        public struct pt_denoise_params
+        {
+            public int iterations;       // 1..8
+            public int reserved;         // 0
+            public double sigma_colour;  // > 0, finite
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         public struct pt_mesh_data
         {
             public int num_triangles;
@@ -171,6 +180,9 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_buffer(IntPtr ctx, double[] m, double[] v, int[] n);
         // channel: (int)Channel (Buffer.cs:8-16 = pt_channel); format: PT_IMAGE_RGB8 / PT_IMAGE_RGBA8 (ABI 10)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_image(IntPtr ctx, int channel, int format, byte[] rgb);
+        // the variance-guided à-trous denoiser (Renderer.Denoise; not OIDN): filter the Buffer as it stands, read the result
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_denoise(IntPtr ctx, ref pt_denoise_params p, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_denoised(IntPtr ctx, int format, IntPtr dst);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_reset_buffer(IntPtr ctx);
@@ -220,6 +232,13 @@ namespace PTSharpCore
         /// on the device, 4 B per pixel copied back instead of 52) and fills Renderer.PBuffer once, after
         /// the last pass.  False keeps the ReadBuffer + Buffer.Image path after every pass.</summary>
         public bool DeviceImages = false;
+        /// <summary>Renderer.Denoise (Renderer.cs:731-761): IterativeRender also writes albedo_channel.png,
+        /// normal_channel.png and denoised_output.png after each pass, into pathTemplate's directory, and
+        /// returns the denoised image.  The denoiser is the library's variance-guided à-trous filter
+        /// (pt_denoise), not OIDN.</summary>
+        public bool Denoise = false;
+        public int DenoiseIterations = 5;         // 1..8
+        public double DenoiseSigmaColour = 4.0;
         internal IntPtr ctx;
         int W, H, pass;
         internal int Width => W;
@@ -531,11 +550,53 @@ namespace PTSharpCore
                     ReadBuffer();
                     colour = Renderer.PBuffer.Image(Channel.ColorChannel);
                 }
-                using var stream = System.IO.File.OpenWrite(string.Format(pathTemplate, i));
-                colour.Encode(SKEncodedImageFormat.Png, 100).SaveTo(stream);
+                using (var stream = System.IO.File.OpenWrite(string.Format(pathTemplate, i)))
+                    colour.Encode(SKEncodedImageFormat.Png, 100).SaveTo(stream);
+                if (Denoise) colour = WriteDenoiseOutputs(pathTemplate);
             }
             if (DeviceImages) ReadBuffer();   // Renderer.PBuffer once, after the last pass
             return colour;
+        }
+
+        /// <summary>Filter the Buffer as it stands into the context's denoised result (pt_denoise); the Buffer
+        /// and the pass state are unchanged.  Returns the device time of its kernels in ms.</summary>
+        public double DenoiseBuffer()
+        {
+            var p = new PtHip.pt_denoise_params { iterations = DenoiseIterations, reserved = 0, sigma_colour = DenoiseSigmaColour };
+            PtHip.Check(PtHip.pt_denoise(ctx, ref p, out double ms), "pt_denoise");
+            return ms;
+        }
+
+        /// <summary>The last DenoiseBuffer()'s colour, encoded as ReadBitmap(ColorChannel) encodes M.  A
+        /// snapshot: later passes do not change it.</summary>
+        public SKBitmap Denoised()
+        {
+            var bmp = new SKBitmap(new SKImageInfo(W, H, SKColorType.Rgba8888, SKAlphaType.Opaque));
+            var px = new byte[W * H * 4];
+            var pin = GCHandle.Alloc(px, GCHandleType.Pinned);
+            try { PtHip.Check(PtHip.pt_read_denoised(ctx, PtHip.PT_DENOISED_RGBA8, pin.AddrOfPinnedObject()), "pt_read_denoised"); }
+            finally { pin.Free(); }
+            for (int y = 0; y < H; y++)   // row by row: a bitmap's RowBytes may exceed 4 W
+                Marshal.Copy(px, y * W * 4, IntPtr.Add(bmp.GetPixels(), y * bmp.RowBytes), W * 4);
+            return bmp;
+        }
+
+        /// <summary>The denoise step of Renderer.cs:731-761 on this context's Buffer: the Albedo and Normal
+        /// channels and the denoised colour as PNG files beside the pass images; returns the denoised image.</summary>
+        internal SKBitmap WriteDenoiseOutputs(string pathTemplate)
+        {
+            string dir = System.IO.Path.GetDirectoryName(pathTemplate) ?? "";
+            void Save(SKBitmap b, string name)
+            {
+                using var s = System.IO.File.OpenWrite(System.IO.Path.Combine(dir, name));
+                b.Encode(SKEncodedImageFormat.Png, 100).SaveTo(s);
+            }
+            Save(ReadBitmap(Channel.AlbedoChannel), "albedo_channel.png");
+            Save(ReadBitmap(Channel.NormalChannel), "normal_channel.png");
+            DenoiseBuffer();
+            var denoised = Denoised();
+            Save(denoised, "denoised_output.png");
+            return denoised;
         }
 
         /// <summary>Buffer.Image(channel) (Buffer.cs:134-202) resolved on the device (pt_read_image): row-major
@@ -603,6 +664,10 @@ namespace PTSharpCore
         public int NumCPU { get => parts[0].NumCPU; set { foreach (var r in parts) r.NumCPU = value; } }
         /// <summary>As HipRenderer.DeviceImages: gather, resolve on device 0, one ReadBuffer after the last pass.</summary>
         public bool DeviceImages = false;
+        /// <summary>As HipRenderer.Denoise: after each pass' gather device 0 holds the whole frame and denoises it.</summary>
+        public bool Denoise = false;
+        public int DenoiseIterations { set { parts[0].DenoiseIterations = value; } }
+        public double DenoiseSigmaColour { set { parts[0].DenoiseSigmaColour = value; } }
 
         /// <summary>One RenderParallel pass on every GPU, one host thread per context.</summary>
         public void RenderParallel() => Parallel.For(0, parts.Length, new ParallelOptions { MaxDegreeOfParallelism = parts.Length },
@@ -631,6 +696,14 @@ namespace PTSharpCore
             return parts[0].ReadImage(channel, rgba);
         }
 
+        /// <summary>The whole frame gathered onto device 0, denoised there (pt_denoise) and read back.</summary>
+        public SKBitmap Denoised()
+        {
+            Gather();
+            parts[0].DenoiseBuffer();
+            return parts[0].Denoised();
+        }
+
         public SKBitmap IterativeRender(string pathTemplate, int iter)
         {
             SKBitmap colour = null;
@@ -648,8 +721,9 @@ namespace PTSharpCore
                     ReadBuffer();
                     colour = Renderer.PBuffer.Image(Channel.ColorChannel);
                 }
-                using var stream = System.IO.File.OpenWrite(string.Format(pathTemplate, i));
-                colour.Encode(SKEncodedImageFormat.Png, 100).SaveTo(stream);
+                using (var stream = System.IO.File.OpenWrite(string.Format(pathTemplate, i)))
+                    colour.Encode(SKEncodedImageFormat.Png, 100).SaveTo(stream);
+                if (Denoise) colour = parts[0].WriteDenoiseOutputs(pathTemplate);   // either path has gathered onto device 0
             }
             // Renderer.PBuffer once: the last pass' gather left the whole frame on device 0
             if (DeviceImages) { if (iter >= 1) parts[0].ReadBuffer(); else ReadBuffer(); }

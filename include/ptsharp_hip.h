@@ -22,6 +22,8 @@
  *   pt_read_buffer     reading Renderer.PBuffer pixels {Samples, M, V}     Buffer.cs:18-58, Renderer.cs:20
  *   pt_read_image      Renderer.PBuffer.Image(channel), resolved on the    Buffer.cs:134-282
  *                      device to 8-bit RGB / RGBA
+ *   pt_denoise /       Renderer.Denoise: the per-pass denoised image, by   Renderer.cs:731-761
+ *   pt_read_denoised   a native variance-guided à-trous filter (not OIDN)
  *   pt_reset_buffer    Renderer.PBuffer = new Buffer(w,h)                  Renderer.cs:41
  *   pt_write_buffer    resuming IterativeRender from a saved PBuffer       Renderer.cs:702-765
  *   pt_read_tiles /    (new) a tile list's pixels, packed: progressive    SURVEY.md §8e
@@ -347,6 +349,37 @@ typedef enum pt_channel { PT_CHANNEL_COLOR = 0, PT_CHANNEL_VARIANCE = 1, PT_CHAN
                           PT_CHANNEL_SAMPLES = 3, PT_CHANNEL_ALBEDO = 4, PT_CHANNEL_NORMAL = 5 } pt_channel;  /* Buffer.cs:8-16 */
 typedef enum pt_image_format { PT_IMAGE_RGB8 = 0, PT_IMAGE_RGBA8 = 1 } pt_image_format;
 int pt_read_image(void* ctx, int32_t channel, int32_t format, uint8_t* out);
+
+/* Renderer.Denoise (Renderer.cs:731-761), served natively: an edge-avoiding à-trous wavelet filter
+ * (Dammertz et al. 2010) whose colour weight is scaled by each pixel's own variance of the mean,
+ * V / ((N-1)·N) from the Welford state (a spatial 5x5 estimate while N < 2), all in fp64
+ * (ptsharp_amd/csrc/pt_denoise.h).  Intel OIDN, the reference's denoiser, is not used. */
+typedef struct pt_denoise_params {
+    int32_t iterations;      /* 1..8 levels, step 2^j at level j */
+    int32_t reserved;        /* 0 */
+    double  sigma_colour;    /* > 0, finite */
+} pt_denoise_params;
+
+/* Filters the Buffer as it stands into a context-owned result (allocated on first use, freed by
+ * pt_destroy; PT_ERR_OUT_OF_MEMORY if it cannot be had).  Changes neither the Buffer nor any pass
+ * state; needs no scene.  params NULL = defaults (5 iterations, sigma_colour 4.0).  out_kernel_ms
+ * (may be NULL): device time of the call's kernels between two hipEvents.  Runs on the context's
+ * stream after every pass issued before it and synchronises before returning.  A tile-sharded
+ * context filters what it holds (its foreign pixels have N = 0 and are invalid: never a tap, passed
+ * through as centres); the root after a gather filters the whole frame.  A NULL ctx, iterations
+ * outside 1..8, a sigma_colour that is not finite and positive, or reserved != 0:
+ * PT_ERR_INVALID_ARG, nothing launched. */
+int pt_denoise(void* ctx, const pt_denoise_params* params, double* out_kernel_ms);
+
+/* The last pt_denoise's result, row-major, into the caller's `out`.  The result is a snapshot: later
+ * passes do not change it.  The 8-bit formats encode the denoised colour exactly as pt_read_image
+ * encodes the Color channel.  Before any pt_denoise on the context, a NULL ctx or out, or a format
+ * outside the enum: PT_ERR_INVALID_ARG. */
+typedef enum pt_denoised_format { PT_DENOISED_RGB8 = 0, PT_DENOISED_RGBA8 = 1,
+                                  PT_DENOISED_COLOUR_F64 = 2,    /* [H][W][3] double, linear */
+                                  PT_DENOISED_VARIANCE_F64 = 3   /* [H][W][3] double, the propagated s2 */
+} pt_denoised_format;
+int pt_read_denoised(void* ctx, int32_t format, void* out);
 
 /* The Buffer pixels of `num_tiles` 32x32 tiles, packed: m, v [num_tiles][32][32][3], n
  * [num_tiles][32][32], row-major inside a tile (entry (t, r, c) = pixel (32·(tiles[t] mod

@@ -10,10 +10,11 @@ from .geometry import Box, Colour, Matrix, Util, Vector
 from .scene import (OBJ, Camera, CapsuleSDF, ColorTexture, Cube, CubeSDF, CylinderSDF, DefaultSampler, DifferenceSDF,
                     IntersectionSDF, LightMode, Material, Mesh, Plane, RepeatSDF, ScaleSDF, Scene, SDFShape, SpecularMode,
                     Sphere, SphereSDF, TorusSDF, TransformedShape, TransformSDF, Triangle, UnionSDF, Volume, VolumeWindow)
+from ._abi import pt_denoise_params as DenoiseParams   # Renderer.DenoiseParams = DenoiseParams(iterations, 0, sigma_colour)
 from .renderer import Buffer, Channel, Renderer, tiles_for_rank, write_png
 
 __all__ = ["Box", "Colour", "Matrix", "Util", "Vector", "Camera", "ColorTexture", "Cube", "DefaultSampler", "LightMode", "Material",
            "Mesh", "OBJ", "Plane", "Scene", "SpecularMode", "Sphere", "Triangle", "SDFShape", "SphereSDF", "CubeSDF",
            "CylinderSDF", "CapsuleSDF", "TorusSDF", "TransformSDF", "ScaleSDF", "UnionSDF", "DifferenceSDF",
            "IntersectionSDF", "RepeatSDF", "Volume", "VolumeWindow", "TransformedShape", "Buffer", "Channel", "Renderer",
-           "tiles_for_rank", "write_png"]
+           "DenoiseParams", "tiles_for_rank", "write_png"]

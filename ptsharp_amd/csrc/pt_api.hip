@@ -80,6 +80,10 @@ hipError_t launch_intersect(const DevScene& S, uint32_t n, const float* o3, cons
 size_t image_staging_bytes(int32_t W, int32_t H);
 hipError_t launch_image_resolve(int channel, int format, const double* m, const double* v, const int32_t* n,
                                 int32_t* max_n, uint32_t* out, int32_t W, int32_t H, hipStream_t stream);
+// pt_denoise.hip
+size_t denoise_workspace_bytes(int32_t W, int32_t H);
+hipError_t launch_denoise(const double* m, const double* v, const int32_t* n, void* ws, int32_t W, int32_t H,
+                          int32_t iterations, double sigma, int* out_pair, hipStream_t stream);
 }
 
 namespace {
@@ -153,6 +157,8 @@ struct Ctx {
     unsigned long long* d_counters = nullptr;   // [pt::kCounterAllocWords] the pass' counters (pt::DevBuffer::counters)
     unsigned long long* h_counters = nullptr;   // [pt::kCounterAllocWords] pinned: their read-back
     uint8_t* d_image = nullptr;                 // pt_read_image's staging image, then its max-N word (first use)
+    void* d_denoise = nullptr;                  // pt_denoise's workspace: two {c, s2} pairs and the validity bytes (first use)
+    int denoise_pair = -1;                      // the pair that holds the last pt_denoise's result (-1: none yet)
     int32_t* d_tiles = nullptr;
     int32_t tiles_cap = 0;
     std::vector<int32_t> h_tiles;               // the tile list in d_tiles (uploaded when it changes)
@@ -1833,6 +1839,64 @@ int pt_read_image(void* ctx, int32_t channel, int32_t format, uint8_t* out) {
     return PT_OK;
 }
 
+int pt_denoise(void* ctx, const pt_denoise_params* params, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    const int32_t iterations = params ? params->iterations : 5;
+    const double sigma = params ? params->sigma_colour : 4.0;
+    if (iterations < 1 || iterations > 8) return fail(PT_ERR_INVALID_ARG, "denoise: iterations must be 1..8");
+    if (params && params->reserved != 0) return fail(PT_ERR_INVALID_ARG, "denoise: reserved must be 0");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(PT_ERR_INVALID_ARG, "denoise: sigma_colour must be finite and > 0");
+    PT_HIP(hipSetDevice(c->device));
+    if (!c->d_denoise && hipMalloc(&c->d_denoise, pt::denoise_workspace_bytes(c->width, c->height)) != hipSuccess) {
+        c->d_denoise = nullptr;
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, "denoise workspace allocation");
+    }
+    int pair = -1;
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_denoise(c->d_m, c->d_v, c->d_n, c->d_denoise, c->width, c->height, iterations, sigma, &pair, c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    c->denoise_pair = pair;
+    if (out_kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *out_kernel_ms = ms;
+    }
+    return PT_OK;
+}
+
+int pt_read_denoised(void* ctx, int32_t format, void* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return fail(PT_ERR_INVALID_ARG, "NULL argument");
+    if (format < PT_DENOISED_RGB8 || format > PT_DENOISED_VARIANCE_F64)
+        return fail(PT_ERR_INVALID_ARG, "format is not a pt_denoised_format");
+    if (c->denoise_pair < 0) return fail(PT_ERR_INVALID_ARG, "pt_read_denoised before any pt_denoise on this context");
+    PT_HIP(hipSetDevice(c->device));
+    const size_t P = (size_t)c->width * (size_t)c->height;
+    const double* colour = (const double*)c->d_denoise + (size_t)c->denoise_pair * 6 * P;
+    if (format == PT_DENOISED_COLOUR_F64 || format == PT_DENOISED_VARIANCE_F64) {
+        const double* src = format == PT_DENOISED_COLOUR_F64 ? colour : colour + 3 * P;
+        PT_HIP(hipMemcpyAsync(out, src, 3 * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PT_HIP(hipStreamSynchronize(c->stream));
+        return PT_OK;
+    }
+    // the Color channel's encoding (image_component<kChColor>, image_byte) of the denoised colour
+    const size_t staging = pt::image_staging_bytes(c->width, c->height);
+    if (!c->d_image && hipMalloc(&c->d_image, staging + 16) != hipSuccess) {
+        c->d_image = nullptr;
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, "image staging allocation");
+    }
+    const int image_format = format == PT_DENOISED_RGBA8 ? PT_IMAGE_RGBA8 : PT_IMAGE_RGB8;
+    PT_HIP(pt::launch_image_resolve(PT_CHANNEL_COLOR, image_format, colour, nullptr, nullptr, (int32_t*)(c->d_image + staging),
+                                    (uint32_t*)c->d_image, c->width, c->height, c->stream));
+    PT_HIP(hipMemcpyAsync(out, c->d_image, P * (image_format == PT_IMAGE_RGBA8 ? 4 : 3), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
 static int tile_workspace(Ctx* c);
 
 // Host copies of a tile list's packed {M, V, N} (see k_tiles_pack for the order).
@@ -1977,6 +2041,7 @@ void pt_destroy(void* ctx) {
     if (c->h_counters) (void)hipHostFree(c->h_counters);
     if (c->d_tiles) (void)hipFree(c->d_tiles);
     if (c->d_image) (void)hipFree(c->d_image);
+    if (c->d_denoise) (void)hipFree(c->d_denoise);
     if (c->d_own) (void)hipFree(c->d_own);
     for (void* p : {(void*)c->g_ids, (void*)c->g_m, (void*)c->g_v, (void*)c->g_n, (void*)c->g_cnts, (void*)c->g_all})
         if (p) (void)hipFree(p);

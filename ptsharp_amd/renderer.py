@@ -4,8 +4,10 @@ Buffer.cs) driving the MI355X path through libptsharp_hip.so.
 `Renderer.NewRenderer(scene, camera, sampler, w, h, multithreaded)` keeps the
 reference's factory and knobs (SamplesPerPixel, StratifiedSampling, ...);
 `RenderParallel()` is one GPU pass; `IterativeRender(pathTemplate, iter)` runs
-`iter` passes and writes a PNG after each, as Renderer.cs:702-765 does.  The
-Welford state stays in HBM between passes; `Renderer.PBuffer` is refreshed
+`iter` passes and writes a PNG after each, as Renderer.cs:702-765 does; with
+`Denoise` set it also writes the Albedo and Normal channels and the denoised
+image after each pass (Renderer.cs:731-761), the denoiser being the library's
+own variance-guided à-trous filter (pt_denoise), not OIDN.  The Welford state stays in HBM between passes; `Renderer.PBuffer` is refreshed
 from it on demand.
 """
 from __future__ import annotations
@@ -133,7 +135,8 @@ class Renderer:
         self.StratifiedSampling = False
         self.AdaptiveSamples = 0
         self.FireflySamples = 0
-        self.Denoise = False
+        self.Denoise = False     # IterativeRender: the denoise step of Renderer.cs:731-761, by pt_denoise
+        self.DenoiseParams = _abi.pt_denoise_params(5, 0, 4.0)   # iterations (1..8), reserved, sigma_colour
         self.NumCPU = 1
         # MI355X extensions (no reference counterpart)
         self.Seed = 0            # Random.Shared is unseedable; this keys the counter-based stream
@@ -262,6 +265,31 @@ class Renderer:
                                            out.ctypes.data_as(C.POINTER(C.c_uint8))), "pt_read_image")
         return out
 
+    def DenoiseBuffer(self) -> float:
+        """Filter the Buffer as it stands into the context's denoised result (pt_denoise, DenoiseParams);
+        the Buffer and the pass state are unchanged.  Returns the device time of its kernels in ms."""
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_denoise(self._ctx, C.byref(self.DenoiseParams), C.byref(ms)), "pt_denoise")
+        return float(ms.value)
+
+    def _read_denoised(self, fmt: int, out: np.ndarray) -> np.ndarray:
+        _abi.check(self._lib.pt_read_denoised(self._ctx, int(fmt), out.ctypes.data_as(C.c_void_p)), "pt_read_denoised")
+        return out
+
+    def Denoised(self, rgba: bool = False) -> np.ndarray:
+        """The last DenoiseBuffer()'s colour, encoded as Image(ColorChannel) encodes M: [H,W,3] uint8,
+        or [H,W,4] with A = 255.  A snapshot: later passes do not change it."""
+        return self._read_denoised(_abi.DENOISED_RGBA8 if rgba else _abi.DENOISED_RGB8,
+                                   np.empty((self.H, self.W, 4 if rgba else 3), np.uint8))
+
+    def DenoisedColour(self) -> np.ndarray:
+        """The last DenoiseBuffer()'s linear colour, [H,W,3] float64."""
+        return self._read_denoised(_abi.DENOISED_COLOUR_F64, np.empty((self.H, self.W, 3), np.float64))
+
+    def DenoisedVariance(self) -> np.ndarray:
+        """The variance of the mean the filter propagated to its output, [H,W,3] float64."""
+        return self._read_denoised(_abi.DENOISED_VARIANCE_F64, np.empty((self.H, self.W, 3), np.float64))
+
     def LoadBuffer(self, buf: Buffer, passes_done: int) -> None:
         """Resume an IterativeRender from a saved Buffer (pt_write_buffer): later passes keep adding
         Welford samples to it, numbered from passes_done + 1 (the random streams are keyed by pass)."""
@@ -336,9 +364,13 @@ class Renderer:
 
     def IterativeRender(self, pathTemplate: str | None, iterations: int) -> np.ndarray:
         """Renderer.IterativeRender (Renderer.cs:702-765).  Each iteration is one Render
-        (NumCPU == 1) or RenderParallel pass, including its adaptive / firefly phases."""
+        (NumCPU == 1) or RenderParallel pass, including its adaptive / firefly phases.  With Denoise
+        (Renderer.cs:731-761) each pass also writes albedo_channel.png, normal_channel.png and
+        denoised_output.png beside the pass image (in pathTemplate's directory), and the denoised
+        image is returned; with no pathTemplate the Buffer is denoised once, after the last pass."""
         self.iterations = iterations
         img = None
+        denoised = None
         for i in range(1, iterations + 1):
             if self.Verbose:
                 print(f"Iteration {i} of {iterations}")
@@ -349,13 +381,23 @@ class Renderer:
             if pathTemplate:
                 img = self.Image(Channel.ColorChannel) if self.DeviceImages else self.ReadBuffer().Image(Channel.ColorChannel)
                 write_png(pathTemplate.replace("{0}", str(i)), img)
+                if self.Denoise:
+                    where = os.path.dirname(pathTemplate)
+                    write_png(os.path.join(where, "albedo_channel.png"), self.Image(Channel.AlbedoChannel))
+                    write_png(os.path.join(where, "normal_channel.png"), self.Image(Channel.NormalChannel))
+                    self.DenoiseBuffer()
+                    denoised = self.Denoised()
+                    write_png(os.path.join(where, "denoised_output.png"), denoised)
+        if self.Denoise and denoised is None:
+            self.DenoiseBuffer()
+            denoised = self.Denoised()
         if self.DeviceImages:
             if img is None:
                 img = self.Image(Channel.ColorChannel)
             self.ReadBuffer()  # Renderer.PBuffer once, after the last pass
         elif img is None:
             img = self.ReadBuffer().Image(Channel.ColorChannel)
-        return img
+        return denoised if self.Denoise else img
 
     # ------------------------------------------------------------- multi-GPU
     def CommInit(self, nranks: int, rank: int, unique_id: bytes) -> None:
