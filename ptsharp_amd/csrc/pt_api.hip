@@ -209,9 +209,10 @@ struct Ctx {
 // samples whose widest depth fits the queues; every chunk pays the fill and drain of
 // 16 persistent launches, so fewer, larger chunks are faster (C4, 16 spp per pass: 8
 // chunks of 32M-entry queues 2574 Mrays/s, 2 chunks 2809, one chunk 2853).  The bound is
-// the largest power of two whose queues (209 B per entry: two extension queues of o, d, throughput r g,
-// key + throughput b, the hits, one shadow set) fit half of the device's memory and half of its free memory,
-// clamped to [2^20, 2^29] entries (2^29: 112 GB of the MI355X's 288 GB: C2's 33M camera samples × 16 children
+// the largest power of two whose queues (229 B per entry: two extension queues of o, d, throughput r g,
+// key + throughput b, the hits, one shadow set, the head pass' two lists: 4 B per extension ray and 16 B per
+// shadow ray) fit half of the device's memory and half of its free memory,
+// clamped to [2^20, 2^29] entries (2^29: 123 GB of the MI355X's 288 GB: C2's 33M camera samples × 16 children
 // in one chunk).  A chunk small enough for the side stream (kSideStreamMaxRays) keeps a second shadow set
 // (ensure_wavefront), within the same budget.
 constexpr uint32_t kWfMinCapLimit = 1u << 20, kWfMaxCapLimit = 1u << 29;
@@ -234,9 +235,9 @@ constexpr double kSideStreamMaxRays = (double)(64ull << 20);   // a chunk's wide
 // Outside this budget, for row-4 scenes only (counted in, they halved C4-sized queues from 2^28 to 2^27
 // entries and split the pass in two chunks, -3 %): the two deferred-record queues of a scene with SDF
 // shapes or Volumes (sdfq, sdfq_sh: 32 B per entry), with Volumes their record words (volq, volq_sh: 8 B),
-// and under the routed split the heavy queues (hq, hq_sh: 8 B).  At most 48 B per entry, 17 % over the
-// 274 B: 12.9 GB at 2^28 entries, inside the three quarters of the device the budget leaves free.
-constexpr size_t kWfBytesPerEntry = 2 * (16 + 16 + 16 + 16) + 16 + (64 + 1);
+// and under the routed split the heavy queues (hq, hq_sh: 8 B).  At most 48 B per entry, 21 % over the
+// 229 B: 25.8 GB at 2^29 entries, inside the half of the device the budget leaves free.
+constexpr size_t kWfBytesPerEntry = 2 * (16 + 16 + 16 + 16) + 16 + (64 + 1) + (4 + 16);
 
 // PT_WF_MAX_CAP (entries, environment) lowers the bound: tests use it to force many chunks.
 uint32_t wf_max_cap(Ctx* c) {
@@ -327,6 +328,9 @@ int ensure_wavefront(Ctx* c, uint32_t cap, uint32_t scap, int32_t acc_passes, bo
     if (want_vol && (rc = wf_alloc(c, &Q.volq_sh, scap))) return rc;
     if (want_heavy && (rc = wf_alloc(c, &Q.hq, cap))) return rc;
     if (want_heavy && (rc = wf_alloc(c, &Q.hq_sh, scap))) return rc;   // one shadow pass at a time uses it
+    // the head pass' lists (pt_wavefront.hip k_wf_trace_head / k_wf_shadow_head)
+    if ((rc = wf_alloc(c, &Q.tlist, cap))) return rc;
+    if ((rc = wf_alloc(c, &Q.slist, scap))) return rc;   // one shadow pass at a time uses it
     if ((rc = wf_alloc(c, &Q.counts, pt::kCountWords))) return rc;
     Q.overflow = c->d_counters + pt::kOverflowCounter;
     // spill columns: one region for the closest-hit kernels, one for the shadow kernels (they
@@ -1501,6 +1505,9 @@ static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* s
     if (const char* f = std::getenv("PT_SHADE_FORM")) plan.shade_form = !std::strcmp(f, "direct") ? 1 : !std::strcmp(f, "scan") ? 2 : 0;
     plan.lanes = -1;
     if (const char* f = std::getenv("PT_LANES")) plan.lanes = !std::strcmp(f, "0") ? 0 : !std::strcmp(f, "1") ? 1 : -1;
+    plan.head = 1;
+    if (const char* f = std::getenv("PT_HEAD")) plan.head = !std::strcmp(f, "0") ? 0 : 1;
+    if (const char* f = std::getenv("PT_HEAD_STATS")) plan.head_stats = !std::strcmp(f, "1") ? 1 : 0;
     plan.linear = -1;
     if (const char* f = std::getenv("PT_LINEAR")) plan.linear = !std::strcmp(f, "0") ? 0 : -1;
     plan.root_children = (uint32_t)std::max(1, n_root * n_root * nm_root);
@@ -1516,6 +1523,10 @@ static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* s
     plan.full_shadow_blocks = c->grids.full_shadow_blocks;
     plan.linear_trace_blocks = c->grids.linear_trace_blocks;
     plan.linear_shadow_blocks = c->grids.linear_shadow_blocks;
+    plan.head_trace_blocks = c->grids.head_trace_blocks;
+    plan.head_shadow_blocks = c->grids.head_shadow_blocks;
+    plan.list_trace_blocks = c->grids.list_trace_blocks;
+    plan.list_shadow_blocks = c->grids.list_shadow_blocks;
     const bool extra = pass->adaptive_samples > 0 || pass->firefly_samples > 0;
     const bool serial = (pass->flags & PT_PASS_SERIAL) != 0;   // Renderer.Render's extra phases (NumCPU == 1)
     // pt_pass_params.passes: K consecutive passes.  Plain RenderParallel passes run as one batch

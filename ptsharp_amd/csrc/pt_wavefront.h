@@ -34,6 +34,11 @@ struct WfQueues {
     // per partition (pcap / spcap entries each): only these go through the FULL analytic half
     uint32_t* hq;        // closest-hit rays (k_wf_trace_lanes → k_wf_trace<.., SPLIT>)
     uint32_t* hq_sh;     // shadow rays (k_wf_shadow_lanes → k_wf_shadow<.., SPLIT>; one shadow pass at a time)
+    // Head pass (k_wf_trace_head / k_wf_shadow_head, pt_wavefront.hip): the rays that enter the triangle BVH,
+    // per partition (pcap / spcap entries each), in slot order inside a head block's claim; the list-fed refill
+    // kernels take their rays from these
+    uint32_t* tlist;     // closest-hit rays: the slot (its provisional hit of the planes and analytic shapes in hits)
+    uint4* slist;        // shadow rays: {slot, phantom light, the light's t (fp64 bits)}; one shadow pass at a time
     // Shadow rays (a diffuse child's sampleLights, set up by k_wf_shade), two sets by depth
     // parity (set q holds the shadow rays counted in pair word q), so the shadow pass and the
     // light-term accumulation of depth d can run beside the closest-hit and shade passes of d + 1.
@@ -73,7 +78,11 @@ constexpr int kSdfSlot = 10 * kParts + 2;   // entries of Q.sdfq
 constexpr int kSdfShSlot = 10 * kParts + 3;   // two slots (shadow set q): entries of Q.sdfq_sh
 constexpr int kHeavySlot = 10 * kParts + 5;     // kParts slots: entries of Q.hq per partition
 constexpr int kHeavyShSlot = 11 * kParts + 5;  // 2 x kParts slots (shadow set q): entries of Q.hq_sh per partition
-constexpr int kEndSlot = 13 * kParts + 5;
+constexpr int kListSlot = 13 * kParts + 5;      // kParts slots: entries of Q.tlist per partition
+constexpr int kListFetchSlot = 14 * kParts + 5; // kParts slots: the list-fed closest hit's cursor into them
+constexpr int kListShSlot = 15 * kParts + 5;    // 2 x kParts slots (shadow set q): entries of Q.slist per partition
+constexpr int kListShFetchSlot = 17 * kParts + 5;   // 2 x kParts slots: the list-fed shadow kernel's cursor
+constexpr int kEndSlot = 19 * kParts + 5;
 constexpr int count_word(int slot) { return slot * kCountStride; }
 constexpr int kFetchWord = count_word(kFetchSlot);
 constexpr int kCountWords = count_word(kEndSlot);
@@ -93,6 +102,11 @@ constexpr int kSdfWord = count_word(kSdfSlot);
 constexpr int sdf_sh_word(int q) { return count_word(kSdfShSlot + q); }
 constexpr int heavy_word(int g) { return count_word(kHeavySlot + g); }
 constexpr int heavy_sh_word(int q, int g) { return count_word(kHeavyShSlot + q * kParts + g); }
+// (the lists: k_wf_shade's block 0 zeroes the next closest hit's and those of the shadow set it writes)
+constexpr int list_word(int g) { return count_word(kListSlot + g); }
+constexpr int list_fetch_word(int g) { return count_word(kListFetchSlot + g); }
+constexpr int list_sh_word(int q, int g) { return count_word(kListShSlot + q * kParts + g); }
+constexpr int list_sh_fetch_word(int q, int g) { return count_word(kListShFetchSlot + q * kParts + g); }
 
 #ifndef PT_LDS_STACK
 #define PT_LDS_STACK 16
@@ -124,10 +138,15 @@ struct WfPlan {
     uint32_t shadow_blocks;
     uint32_t lanes_trace_blocks, lanes_shadow_blocks, full_trace_blocks, full_shadow_blocks;
     uint32_t linear_trace_blocks, linear_shadow_blocks;   // k_wf_trace_linear / k_wf_shadow_linear (resident)
+    uint32_t head_trace_blocks, head_shadow_blocks;       // k_wf_trace_head / k_wf_shadow_head (resident)
+    uint32_t list_trace_blocks, list_shadow_blocks;       // the list-fed forms of the refill kernels (resident)
     int32_t shade_form;        // k_wf_shade form: 0 chosen per depth from the kept count, 1 direct, 2 SCAN
                                // (PT_SHADE_FORM=direct|scan in the environment; tests)
     int32_t lanes;             // refill traversal kernels: -1 by BVH size, 0 never, 1 always
                                // (PT_LANES=0|1 in the environment; tests)
+    int32_t head;              // head pass + list-fed refill kernels where they apply (unsplit refill kernels, a
+                               // triangles-only step loop): 1, or 0 never (PT_HEAD=0 in the environment; tests, A/B)
+    int32_t head_stats;        // PT_HEAD_STATS=1: the lists' counts per depth to stderr (a diagnostic: it synchronizes)
     int32_t linear;            // linear kernels (few analytic records, no triangles): -1 where they apply, 0 never
                                // (PT_LINEAR=0 in the environment; tests)
     // Optional second stream: each depth's shadow pass runs there, beside the next depth's
