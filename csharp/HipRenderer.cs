@@ -28,6 +28,7 @@ namespace PTSharpCore
         public const int PT_PASS_KERNEL_TIMING = 1, PT_PASS_SERIAL = 2;
         public const int PT_MARCH_LANE = 1, PT_MARCH_WAVE = 2;   // pt_intersect / pt_occluded flags
         public const int PT_IMAGE_RGB8 = 0, PT_IMAGE_RGBA8 = 1;  // pt_image_format (pt_read_image)
+        public const int PT_FEATURE_ALBEDO_F64 = 0, PT_FEATURE_NORMAL_F32 = 1, PT_FEATURE_DEPTH_F64 = 2, PT_FEATURE_KIND_I32 = 3, PT_FEATURE_MATERIAL_I32 = 4;  // pt_feature
         public const int PT_DENOISED_RGB8 = 0, PT_DENOISED_RGBA8 = 1, PT_DENOISED_COLOUR_F64 = 2, PT_DENOISED_VARIANCE_F64 = 3;  // pt_denoised_format
         public const int SHAPE_SPHERE = 0, SHAPE_CUBE = 1, SHAPE_PLANE = 2, SHAPE_TRIANGLE = 3, SHAPE_MESH = 4;
         public const int SHAPE_SDF = 5, SHAPE_VOLUME = 6, SHAPE_TRANSFORMED = 7;
@@ -163,6 +164,17 @@ namespace PTSharpCore
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        public struct pt_denoise_guided_params
+        {
+            public int iterations;       // 1..8
+            public int reserved;         // 0
+            public double sigma_colour;  // > 0, finite
+            public double sigma_normal;  // >= 0, finite; 0 = term off
+            public double sigma_albedo;  // likewise
+            public double sigma_depth;   // likewise; relative to the centre's depth
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         public struct pt_mesh_data
         {
             public int num_triangles;
@@ -183,6 +195,11 @@ namespace PTSharpCore
         // the variance-guided à-trous denoiser (Renderer.Denoise; not OIDN): filter the Buffer as it stands, read the result
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_denoise(IntPtr ctx, ref pt_denoise_params p, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_denoised(IntPtr ctx, int format, IntPtr dst);
+        // first-hit features (albedo, shading normal, depth, kind, material: one primary ray per pixel) and the filter guided by them
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_render_features(IntPtr ctx, ref pt_camera cam, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_features(IntPtr ctx, int feature, IntPtr dst);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_features(IntPtr ctx, double[] albedo, float[] normal, double[] depth, int[] kind);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_denoise_guided(IntPtr ctx, ref pt_denoise_guided_params p, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_reset_buffer(IntPtr ctx);
@@ -239,6 +256,12 @@ namespace PTSharpCore
         public bool Denoise = false;
         public int DenoiseIterations = 5;         // 1..8
         public double DenoiseSigmaColour = 4.0;
+        /// <summary>With Denoise: the first-hit features are rendered once (RenderFeatures) and the filter is
+        /// pt_denoise_guided, whose tap weights also fall with the albedo, normal and depth distance to the
+        /// centre.</summary>
+        public bool DenoiseGuided { get; set; } = false;
+        public double DenoiseSigmaNormal = 0.3, DenoiseSigmaAlbedo = 0.3, DenoiseSigmaDepth = 0.1;   // 0 = term off
+        bool haveFeatures = false;
         internal IntPtr ctx;
         int W, H, pass;
         internal int Width => W;
@@ -562,9 +585,48 @@ namespace PTSharpCore
         /// and the pass state are unchanged.  Returns the device time of its kernels in ms.</summary>
         public double DenoiseBuffer()
         {
+            if (DenoiseGuided)
+            {
+                if (!haveFeatures) RenderFeatures();   // once: the features do not change with the passes
+                var g = new PtHip.pt_denoise_guided_params { iterations = DenoiseIterations, reserved = 0, sigma_colour = DenoiseSigmaColour,
+                    sigma_normal = DenoiseSigmaNormal, sigma_albedo = DenoiseSigmaAlbedo, sigma_depth = DenoiseSigmaDepth };
+                PtHip.Check(PtHip.pt_denoise_guided(ctx, ref g, out double gms), "pt_denoise_guided");
+                return gms;
+            }
             var p = new PtHip.pt_denoise_params { iterations = DenoiseIterations, reserved = 0, sigma_colour = DenoiseSigmaColour };
             PtHip.Check(PtHip.pt_denoise(ctx, ref p, out double ms), "pt_denoise");
             return ms;
+        }
+
+        /// <summary>The first-hit features of the whole frame (pt_render_features): one ray through each
+        /// pixel's centre, the lens ignored.  The Buffer and the pass state are unchanged.  Returns the
+        /// device time of the kernel in ms.</summary>
+        public double RenderFeatures()
+        {
+            if (!uploaded) Upload();
+            var cam = Cam();
+            PtHip.Check(PtHip.pt_render_features(ctx, ref cam, out double ms), "pt_render_features");
+            haveFeatures = true;
+            return ms;
+        }
+
+        /// <summary>The context's features (pt_read_features), row-major: albedo [H][W][3], normal [H][W][3],
+        /// depth [H][W] (1e9 on a miss), kind [H][W] (the pt_shape_kind hit, or -1), material [H][W] (or -1).</summary>
+        public (double[] albedo, float[] normal, double[] depth, int[] kind, int[] material) ReadFeatures()
+        {
+            int P = W * H;
+            var albedo = new double[3 * P]; var normal = new float[3 * P]; var depth = new double[P];
+            var kind = new int[P]; var material = new int[P];
+            void Read(int feature, Array dst)
+            {
+                var pin = GCHandle.Alloc(dst, GCHandleType.Pinned);
+                try { PtHip.Check(PtHip.pt_read_features(ctx, feature, pin.AddrOfPinnedObject()), "pt_read_features"); }
+                finally { pin.Free(); }
+            }
+            Read(PtHip.PT_FEATURE_ALBEDO_F64, albedo); Read(PtHip.PT_FEATURE_NORMAL_F32, normal);
+            Read(PtHip.PT_FEATURE_DEPTH_F64, depth); Read(PtHip.PT_FEATURE_KIND_I32, kind);
+            Read(PtHip.PT_FEATURE_MATERIAL_I32, material);
+            return (albedo, normal, depth, kind, material);
         }
 
         /// <summary>The last DenoiseBuffer()'s colour, encoded as ReadBitmap(ColorChannel) encodes M.  A
@@ -668,6 +730,8 @@ namespace PTSharpCore
         public bool Denoise = false;
         public int DenoiseIterations { set { parts[0].DenoiseIterations = value; } }
         public double DenoiseSigmaColour { set { parts[0].DenoiseSigmaColour = value; } }
+        /// <summary>As HipRenderer.DenoiseGuided: device 0 renders the whole frame's features and filters with them.</summary>
+        public bool DenoiseGuided { set { parts[0].DenoiseGuided = value; } }
 
         /// <summary>One RenderParallel pass on every GPU, one host thread per context.</summary>
         public void RenderParallel() => Parallel.For(0, parts.Length, new ParallelOptions { MaxDegreeOfParallelism = parts.Length },

@@ -24,6 +24,10 @@
  *                      device to 8-bit RGB / RGBA
  *   pt_denoise /       Renderer.Denoise: the per-pass denoised image, by   Renderer.cs:731-761
  *   pt_read_denoised   a native variance-guided à-trous filter (not OIDN)
+ *   pt_render_features Renderer.DenoiseImage(color, albedo, normal): the     Renderer.cs:686-700
+ *   / pt_read_features denoiser's auxiliary images, here the true first-hit
+ *   / pt_write_features albedo, shading normal and depth of one primary ray
+ *   / pt_denoise_guided per pixel, and the à-trous filter guided by them
  *   pt_reset_buffer    Renderer.PBuffer = new Buffer(w,h)                  Renderer.cs:41
  *   pt_write_buffer    resuming IterativeRender from a saved PBuffer       Renderer.cs:702-765
  *   pt_read_tiles /    (new) a tile list's pixels, packed: progressive    SURVEY.md §8e
@@ -373,13 +377,66 @@ int pt_denoise(void* ctx, const pt_denoise_params* params, double* out_kernel_ms
 
 /* The last pt_denoise's result, row-major, into the caller's `out`.  The result is a snapshot: later
  * passes do not change it.  The 8-bit formats encode the denoised colour exactly as pt_read_image
- * encodes the Color channel.  Before any pt_denoise on the context, a NULL ctx or out, or a format
- * outside the enum: PT_ERR_INVALID_ARG. */
+ * encodes the Color channel.  pt_denoise_guided leaves its result in the same place.  Before any
+ * pt_denoise or pt_denoise_guided on the context, a NULL ctx or out, or a format outside the enum:
+ * PT_ERR_INVALID_ARG. */
 typedef enum pt_denoised_format { PT_DENOISED_RGB8 = 0, PT_DENOISED_RGBA8 = 1,
                                   PT_DENOISED_COLOUR_F64 = 2,    /* [H][W][3] double, linear */
                                   PT_DENOISED_VARIANCE_F64 = 3   /* [H][W][3] double, the propagated s2 */
 } pt_denoised_format;
 int pt_read_denoised(void* ctx, int32_t format, void* out);
+
+/* First-hit features of the whole frame, whatever tile list the context renders: one ray per pixel
+ * (x, y), Camera.CastRay(x, y, W, H, 0.5, 0.5) with the lens ignored (aperture_radius is treated as
+ * 0, so no random number is drawn and the pass is deterministic), its nearest hit by Scene.Intersect
+ * and Hit.Info there: the shading normal after the flip (normal and bump maps included), the material
+ * id and the Material.MaterialAt colour.  On a miss the kind is -1, the depth Hit.INF (1e9), the
+ * normal (0,0,0), the material -1 and the albedo sampleEnvironment(direction).  The features are
+ * context-owned (allocated on first use, freed by pt_destroy; PT_ERR_OUT_OF_MEMORY if they cannot be
+ * had).  Runs on the context's stream after every pass issued before it and synchronises before
+ * returning; changes neither the Buffer nor any pass state or counter.  out_kernel_ms may be NULL.
+ * Needs an uploaded scene (PT_ERR_NO_SCENE); a NULL ctx or camera: PT_ERR_INVALID_ARG. */
+int pt_render_features(void* ctx, const pt_camera* camera, double* out_kernel_ms);
+
+/* One feature of the last pt_render_features or pt_write_features, row-major, into `out`.  Before
+ * either on the context, a NULL ctx or out, or a feature outside the enum: PT_ERR_INVALID_ARG. */
+typedef enum pt_feature { PT_FEATURE_ALBEDO_F64 = 0,     /* [H][W][3] double */
+                          PT_FEATURE_NORMAL_F32 = 1,     /* [H][W][3] float */
+                          PT_FEATURE_DEPTH_F64 = 2,      /* [H][W] double, the ray's t; 1e9 on a miss */
+                          PT_FEATURE_KIND_I32 = 3,       /* [H][W] int32, the pt_shape_kind hit as pt_intersect reports it, or -1 */
+                          PT_FEATURE_MATERIAL_I32 = 4    /* [H][W] int32, the material id, or -1 */
+} pt_feature;
+int pt_read_features(void* ctx, int32_t feature, void* out);
+
+/* Installs a host's own features (its AOVs), as pt_write_buffer installs a Buffer: all four arrays
+ * are required (layouts as pt_read_features; a pixel is a hit where kind >= 0), the material becomes
+ * -1 everywhere, and the filter's guide records are rebuilt on the device.  Needs no scene. */
+int pt_write_features(void* ctx, const double* albedo, const float* normal, const double* depth, const int32_t* kind);
+
+/* pt_denoise guided by the context's features.  Prepare, the variance blur, the levels, the validity
+ * rules and the variance propagation are pt_denoise's; only a tap's weight changes.  With the guide
+ * values (fp32 copies of normal, depth and albedo, and the hit flag) widened to fp64, a tap whose hit
+ * flag differs from the centre's is skipped like an invalid tap, and for the others
+ *   w(q) = h(dx,dy) · exp(−d),  d = d_colour                                   (pt_denoise's term)
+ *        + Σ_k (a_q,k − a_p,k)² / sigma_albedo²                                 if sigma_albedo > 0
+ *        + Σ_k (n_q,k − n_p,k)² / sigma_normal²                                 if p is a hit and sigma_normal > 0
+ *        + (z_q − z_p)² / (sigma_depth · z_p)²                                  if p is a hit and sigma_depth > 0
+ * (ptsharp_amd/csrc/pt_denoise.h). */
+typedef struct pt_denoise_guided_params {
+    int32_t iterations;      /* 1..8 */
+    int32_t reserved;        /* 0 */
+    double  sigma_colour;    /* > 0, finite */
+    double  sigma_normal;    /* >= 0, finite; 0 = term off */
+    double  sigma_albedo;    /* likewise */
+    double  sigma_depth;     /* likewise; relative to the centre's depth */
+} pt_denoise_guided_params;
+
+/* The result goes where pt_denoise's goes: pt_read_denoised returns the last pt_denoise or
+ * pt_denoise_guided.  params NULL = defaults (5 iterations, sigma_colour 4.0, sigma_normal 0.3,
+ * sigma_albedo 0.3, sigma_depth 0.1).  Stream order, out_kernel_ms and the Buffer as for pt_denoise.
+ * No features on the context (no pt_render_features or pt_write_features before), a NULL ctx, or a field out of range:
+ * PT_ERR_INVALID_ARG, nothing launched, out_kernel_ms untouched. */
+int pt_denoise_guided(void* ctx, const pt_denoise_guided_params* params, double* out_kernel_ms);
 
 /* The Buffer pixels of `num_tiles` 32x32 tiles, packed: m, v [num_tiles][32][32][3], n
  * [num_tiles][32][32], row-major inside a tile (entry (t, r, c) = pixel (32·(tiles[t] mod

@@ -84,6 +84,15 @@ hipError_t launch_image_resolve(int channel, int format, const double* m, const 
 size_t denoise_workspace_bytes(int32_t W, int32_t H);
 hipError_t launch_denoise(const double* m, const double* v, const int32_t* n, void* ws, int32_t W, int32_t H,
                           int32_t iterations, double sigma, int* out_pair, hipStream_t stream);
+hipError_t launch_denoise_guided(const double* m, const double* v, const int32_t* n, void* ws, const void* guide,
+                                 int32_t W, int32_t H, int32_t iterations, double sigma, double sigma_albedo,
+                                 double sigma_normal, double sigma_depth, int* out_pair, hipStream_t stream);
+// pt_features.hip
+size_t features_bytes(int32_t W, int32_t H);
+void* features_part(void* base, int32_t W, int32_t H, int part, size_t* bytes);
+const void* features_guide(void* base, int32_t W, int32_t H);
+hipError_t launch_features(const DevScene& S, const DevCamera& cam, void* base, int32_t W, int32_t H, hipStream_t stream);
+hipError_t launch_features_pack(void* base, int32_t W, int32_t H, hipStream_t stream);
 }
 
 namespace {
@@ -158,7 +167,9 @@ struct Ctx {
     unsigned long long* h_counters = nullptr;   // [pt::kCounterAllocWords] pinned: their read-back
     uint8_t* d_image = nullptr;                 // pt_read_image's staging image, then its max-N word (first use)
     void* d_denoise = nullptr;                  // pt_denoise's workspace: two {c, s2} pairs and the validity bytes (first use)
-    int denoise_pair = -1;                      // the pair that holds the last pt_denoise's result (-1: none yet)
+    int denoise_pair = -1;                      // the pair that holds the last pt_denoise's or pt_denoise_guided's result (-1: none yet)
+    void* d_features = nullptr;                 // first-hit features and their guide records (pt_features.hip; first use)
+    bool have_features = false;                 // pt_render_features or pt_write_features filled d_features
     int32_t* d_tiles = nullptr;
     int32_t tiles_cap = 0;
     std::vector<int32_t> h_tiles;               // the tile list in d_tiles (uploaded when it changes)
@@ -1908,6 +1919,118 @@ int pt_read_denoised(void* ctx, int32_t format, void* out) {
     return PT_OK;
 }
 
+// ------------------------------------------------------------------ first-hit features, guided denoise
+// pt_denoise_guided's default guide sigmas (DESIGN.md §4b has the table they were chosen from)
+constexpr double PT_DENOISE_GUIDED_SIGMA_NORMAL = 0.3, PT_DENOISE_GUIDED_SIGMA_ALBEDO = 0.3, PT_DENOISE_GUIDED_SIGMA_DEPTH = 0.1;
+static int features_storage(Ctx* c) {
+    if (!c->d_features && hipMalloc(&c->d_features, pt::features_bytes(c->width, c->height)) != hipSuccess) {
+        c->d_features = nullptr;
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, "features allocation");
+    }
+    return PT_OK;
+}
+
+int pt_render_features(void* ctx, const pt_camera* camera, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !camera) return fail(PT_ERR_INVALID_ARG, "NULL argument");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    PT_HIP(hipSetDevice(c->device));
+    const int rc = features_storage(c);
+    if (rc != PT_OK) return rc;
+    pt::DevCamera cam;
+    std::memcpy(cam.p, camera->p, sizeof cam.p); std::memcpy(cam.u, camera->u, sizeof cam.u);
+    std::memcpy(cam.v, camera->v, sizeof cam.v); std::memcpy(cam.w, camera->w, sizeof cam.w);
+    cam.m = camera->m; cam.focal_distance = camera->focal_distance;
+    cam.aperture_radius = 0.0;   // the lens is ignored: one deterministic ray through the pixel
+    pt::DevScene S = c->S;
+    S.march = nullptr;
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_features(S, cam, c->d_features, c->width, c->height, c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    c->have_features = true;
+    if (out_kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *out_kernel_ms = ms;
+    }
+    return PT_OK;
+}
+
+int pt_read_features(void* ctx, int32_t feature, void* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return fail(PT_ERR_INVALID_ARG, "NULL argument");
+    if (feature < PT_FEATURE_ALBEDO_F64 || feature > PT_FEATURE_MATERIAL_I32)
+        return fail(PT_ERR_INVALID_ARG, "feature is not a pt_feature");
+    if (!c->have_features)
+        return fail(PT_ERR_INVALID_ARG, "pt_read_features before any pt_render_features or pt_write_features on this context");
+    PT_HIP(hipSetDevice(c->device));
+    size_t bytes = 0;
+    const void* src = pt::features_part(c->d_features, c->width, c->height, feature, &bytes);
+    PT_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_features(void* ctx, const double* albedo, const float* normal, const double* depth, const int32_t* kind) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !albedo || !normal || !depth || !kind) return fail(PT_ERR_INVALID_ARG, "NULL argument");
+    PT_HIP(hipSetDevice(c->device));
+    const int rc = features_storage(c);
+    if (rc != PT_OK) return rc;
+    const void* src[4] = {albedo, normal, depth, kind};
+    for (int part = 0; part < 4; part++) {
+        size_t bytes = 0;
+        void* dst = pt::features_part(c->d_features, c->width, c->height, part, &bytes);
+        PT_HIP(hipMemcpyAsync(dst, src[part], bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    size_t bytes = 0;
+    void* mat = pt::features_part(c->d_features, c->width, c->height, PT_FEATURE_MATERIAL_I32, &bytes);
+    PT_HIP(hipMemsetAsync(mat, 0xFF, bytes, c->stream));   // every material id -1
+    PT_HIP(pt::launch_features_pack(c->d_features, c->width, c->height, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    c->have_features = true;
+    return PT_OK;
+}
+
+int pt_denoise_guided(void* ctx, const pt_denoise_guided_params* params, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    const int32_t iterations = params ? params->iterations : 5;
+    const double sigma = params ? params->sigma_colour : 4.0;
+    const double guide[3] = {params ? params->sigma_albedo : PT_DENOISE_GUIDED_SIGMA_ALBEDO,
+                             params ? params->sigma_normal : PT_DENOISE_GUIDED_SIGMA_NORMAL,
+                             params ? params->sigma_depth : PT_DENOISE_GUIDED_SIGMA_DEPTH};
+    if (iterations < 1 || iterations > 8) return fail(PT_ERR_INVALID_ARG, "denoise_guided: iterations must be 1..8");
+    if (params && params->reserved != 0) return fail(PT_ERR_INVALID_ARG, "denoise_guided: reserved must be 0");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(PT_ERR_INVALID_ARG, "denoise_guided: sigma_colour must be finite and > 0");
+    for (double g : guide)
+        if (!(g >= 0.0) || !std::isfinite(g))
+            return fail(PT_ERR_INVALID_ARG, "denoise_guided: sigma_albedo, sigma_normal and sigma_depth must be finite and >= 0");
+    if (!c->have_features)
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_guided before any pt_render_features or pt_write_features on this context");
+    PT_HIP(hipSetDevice(c->device));
+    if (!c->d_denoise && hipMalloc(&c->d_denoise, pt::denoise_workspace_bytes(c->width, c->height)) != hipSuccess) {
+        c->d_denoise = nullptr;
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, "denoise workspace allocation");
+    }
+    int pair = -1;
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_denoise_guided(c->d_m, c->d_v, c->d_n, c->d_denoise, pt::features_guide(c->d_features, c->width, c->height),
+                                     c->width, c->height, iterations, sigma, guide[0], guide[1], guide[2], &pair, c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    c->denoise_pair = pair;
+    if (out_kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *out_kernel_ms = ms;
+    }
+    return PT_OK;
+}
+
 static int tile_workspace(Ctx* c);
 
 // Host copies of a tile list's packed {M, V, N} (see k_tiles_pack for the order).
@@ -2053,6 +2176,7 @@ void pt_destroy(void* ctx) {
     if (c->d_tiles) (void)hipFree(c->d_tiles);
     if (c->d_image) (void)hipFree(c->d_image);
     if (c->d_denoise) (void)hipFree(c->d_denoise);
+    if (c->d_features) (void)hipFree(c->d_features);
     if (c->d_own) (void)hipFree(c->d_own);
     for (void* p : {(void*)c->g_ids, (void*)c->g_m, (void*)c->g_v, (void*)c->g_n, (void*)c->g_cnts, (void*)c->g_all})
         if (p) (void)hipFree(p);

@@ -4,7 +4,8 @@
 // row), each calling the per-pixel text of pt_denoise.h:
 //   k_denoise_prepare  Buffer {M, V, N} -> c, the unblurred s2 and the validity byte
 //   k_denoise_blur     s2 -> its 3x3 binomial blur (once)
-//   k_denoise_level    one à-trous level at step s, from one {c, s2} pair into the other
+//   k_denoise_level_t  one à-trous level at step s, from one {c, s2} pair into the other; its guided
+//                      instantiation also reads the features' guide records (pt_denoise_guided)
 // With a lane per pixel along x every tap of the stencil, whatever the step, is a load of 64
 // consecutive pixels (1536 contiguous bytes of c, as many of s2, 64 validity bytes), so no level
 // needs a gather; the reuse between the rows y, y±s, y±2s is left to L2 and the Infinity Cache.
@@ -46,13 +47,18 @@ __global__ __launch_bounds__(kDenoiseBlockX * kDenoiseBlockY) void k_denoise_blu
     for (int k = 0; k < 3; k++) s2_out[3 * p + k] = out[k];
 }
 
-__global__ __launch_bounds__(kDenoiseBlockX * kDenoiseBlockY) void k_denoise_level(
-    const double* __restrict__ c, const double* __restrict__ s2, const uint8_t* __restrict__ valid, double* __restrict__ c_out,
-    double* __restrict__ s2_out, int32_t W, int32_t H, int32_t step, double sigma2) {
+// GUIDED = false is pt_denoise's level (`guide` unused, denoise_level_at alone); GUIDED = true adds the guide
+// record's terms to each tap's distance (pt_denoise_guided): two more 16-byte loads per tap.
+template <bool GUIDED>
+__global__ __launch_bounds__(kDenoiseBlockX * kDenoiseBlockY) void k_denoise_level_t(
+    const double* __restrict__ c, const double* __restrict__ s2, const uint8_t* __restrict__ valid,
+    const DenoiseGuideRec* __restrict__ guide, double* __restrict__ c_out, double* __restrict__ s2_out, int32_t W, int32_t H,
+    int32_t step, double sigma2, DenoiseGuideSigmas sg) {
     const int32_t x = (int32_t)(blockIdx.x * kDenoiseBlockX + threadIdx.x), y = (int32_t)(blockIdx.y * kDenoiseBlockY + threadIdx.y);
     if (x >= W || y >= H) return;
     double co[3], so[3];
-    denoise_level_at(c, s2, valid, W, H, x, y, step, sigma2, co, so);
+    if (GUIDED) denoise_level_guided_at(c, s2, valid, guide, W, H, x, y, step, sigma2, sg, co, so);
+    else denoise_level_at(c, s2, valid, W, H, x, y, step, sigma2, co, so);
     const size_t p = denoise_index(W, x, y);
     for (int k = 0; k < 3; k++) {
         c_out[3 * p + k] = co[k];
@@ -68,9 +74,12 @@ size_t denoise_workspace_bytes(int32_t W, int32_t H) {
 
 // Filter the Buffer {m, v, n} with `iterations` levels on `stream`.  `ws` is denoise_workspace_bytes
 // of device memory; the result is pair *out_pair (0 or 1): c at ws + pair·6P doubles, s2 3P doubles
-// after it.  iterations and sigma are valid (pt_denoise checks them).
-hipError_t launch_denoise(const double* m, const double* v, const int32_t* n, void* ws, int32_t W, int32_t H,
-                          int32_t iterations, double sigma, int* out_pair, hipStream_t stream) {
+// after it.  iterations and sigma are valid (pt_denoise checks them).  With `guide` ([P] records of 32
+// bytes, pt_features.hip) the levels are the guided ones, with sigma_albedo, sigma_normal and
+// sigma_depth in `gs` (pt_denoise_guided checks them); without, pt_denoise's.
+static hipError_t launch_levels(const double* m, const double* v, const int32_t* n, void* ws, const DenoiseGuideRec* guide,
+                                const double gs[3], int32_t W, int32_t H, int32_t iterations, double sigma, int* out_pair,
+                                hipStream_t stream) {
     const size_t P = (size_t)W * (size_t)H;
     double* base = (double*)ws;
     double* c[2] = {base, base + 6 * P};
@@ -81,12 +90,31 @@ hipError_t launch_denoise(const double* m, const double* v, const int32_t* n, vo
     hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, stream, m, v, n, c[0], s2[1], valid, W, H);
     hipLaunchKernelGGL(k_denoise_blur, grid, block, 0, stream, (const double*)s2[1], (const uint8_t*)valid, s2[0], W, H);
     const double sigma2 = sigma * sigma;
+    const DenoiseGuideSigmas sg = guide ? DenoiseGuideSigmas{gs[0] * gs[0], gs[1] * gs[1], gs[2]} : DenoiseGuideSigmas{0.0, 0.0, 0.0};
     int src = 0;
-    for (int32_t j = 0; j < iterations; j++, src ^= 1)
-        hipLaunchKernelGGL(k_denoise_level, grid, block, 0, stream, (const double*)c[src], (const double*)s2[src],
-                           (const uint8_t*)valid, c[src ^ 1], s2[src ^ 1], W, H, (int32_t)1 << j, sigma2);
+    for (int32_t j = 0; j < iterations; j++, src ^= 1) {
+        if (guide)
+            hipLaunchKernelGGL((k_denoise_level_t<true>), grid, block, 0, stream, (const double*)c[src], (const double*)s2[src],
+                               (const uint8_t*)valid, guide, c[src ^ 1], s2[src ^ 1], W, H, (int32_t)1 << j, sigma2, sg);
+        else
+            hipLaunchKernelGGL((k_denoise_level_t<false>), grid, block, 0, stream, (const double*)c[src], (const double*)s2[src],
+                               (const uint8_t*)valid, guide, c[src ^ 1], s2[src ^ 1], W, H, (int32_t)1 << j, sigma2, sg);
+    }
     *out_pair = src;
     return hipGetLastError();
+}
+
+hipError_t launch_denoise(const double* m, const double* v, const int32_t* n, void* ws, int32_t W, int32_t H,
+                          int32_t iterations, double sigma, int* out_pair, hipStream_t stream) {
+    return launch_levels(m, v, n, ws, nullptr, nullptr, W, H, iterations, sigma, out_pair, stream);
+}
+
+// `guide` is the features' guide records (features_guide, pt_features.hip).
+hipError_t launch_denoise_guided(const double* m, const double* v, const int32_t* n, void* ws, const void* guide,
+                                 int32_t W, int32_t H, int32_t iterations, double sigma, double sigma_albedo,
+                                 double sigma_normal, double sigma_depth, int* out_pair, hipStream_t stream) {
+    const double gs[3] = {sigma_albedo, sigma_normal, sigma_depth};
+    return launch_levels(m, v, n, ws, (const DenoiseGuideRec*)guide, gs, W, H, iterations, sigma, out_pair, stream);
 }
 
 }  // namespace pt

@@ -7,7 +7,9 @@ reference's factory and knobs (SamplesPerPixel, StratifiedSampling, ...);
 `iter` passes and writes a PNG after each, as Renderer.cs:702-765 does; with
 `Denoise` set it also writes the Albedo and Normal channels and the denoised
 image after each pass (Renderer.cs:731-761), the denoiser being the library's
-own variance-guided à-trous filter (pt_denoise), not OIDN.  The Welford state stays in HBM between passes; `Renderer.PBuffer` is refreshed
+own variance-guided à-trous filter (pt_denoise), not OIDN; with `DenoiseGuided` too the filter
+is guided by the first-hit albedo, normal and depth of one primary ray per pixel
+(pt_render_features, pt_denoise_guided).  The Welford state stays in HBM between passes; `Renderer.PBuffer` is refreshed
 from it on demand.
 """
 from __future__ import annotations
@@ -137,6 +139,9 @@ class Renderer:
         self.FireflySamples = 0
         self.Denoise = False     # IterativeRender: the denoise step of Renderer.cs:731-761, by pt_denoise
         self.DenoiseParams = _abi.pt_denoise_params(5, 0, 4.0)   # iterations (1..8), reserved, sigma_colour
+        self.DenoiseGuided = False   # with Denoise: RenderFeatures() once, then pt_denoise_guided instead of pt_denoise
+        # iterations (1..8), reserved, sigma_colour, sigma_normal, sigma_albedo, sigma_depth (0 = term off)
+        self.DenoiseGuidedParams = _abi.pt_denoise_guided_params(5, 0, 4.0, 0.3, 0.3, 0.1)
         self.NumCPU = 1
         # MI355X extensions (no reference counterpart)
         self.Seed = 0            # Random.Shared is unseedable; this keys the counter-based stream
@@ -265,12 +270,51 @@ class Renderer:
                                            out.ctypes.data_as(C.POINTER(C.c_uint8))), "pt_read_image")
         return out
 
-    def DenoiseBuffer(self) -> float:
-        """Filter the Buffer as it stands into the context's denoised result (pt_denoise, DenoiseParams);
-        the Buffer and the pass state are unchanged.  Returns the device time of its kernels in ms."""
+    def DenoiseBuffer(self, guided: bool = False) -> float:
+        """Filter the Buffer as it stands into the context's denoised result (pt_denoise, DenoiseParams;
+        guided: pt_denoise_guided, DenoiseGuidedParams, with the context's features); the Buffer and the
+        pass state are unchanged.  Returns the device time of its kernels in ms."""
         ms = C.c_double(0.0)
-        _abi.check(self._lib.pt_denoise(self._ctx, C.byref(self.DenoiseParams), C.byref(ms)), "pt_denoise")
+        if guided:
+            _abi.check(self._lib.pt_denoise_guided(self._ctx, C.byref(self.DenoiseGuidedParams), C.byref(ms)),
+                       "pt_denoise_guided")
+        else:
+            _abi.check(self._lib.pt_denoise(self._ctx, C.byref(self.DenoiseParams), C.byref(ms)), "pt_denoise")
         return float(ms.value)
+
+    def RenderFeatures(self) -> float:
+        """The first-hit features of the whole frame (pt_render_features): one ray through each pixel's
+        centre, the lens ignored.  The Buffer and the pass state are unchanged.  Returns the device time
+        of the kernel in ms."""
+        self._ensure_scene()
+        cam = self.Camera.to_c()
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_render_features(self._ctx, C.byref(cam), C.byref(ms)), "pt_render_features")
+        return float(ms.value)
+
+    def Features(self):
+        """The context's features (pt_read_features): albedo [H,W,3] float64, normal [H,W,3] float32,
+        depth [H,W] float64 (1e9 on a miss), kind [H,W] int32 (the pt_shape_kind hit, or -1) and
+        material [H,W] int32 (or -1)."""
+        out = (np.empty((self.H, self.W, 3), np.float64), np.empty((self.H, self.W, 3), np.float32),
+               np.empty((self.H, self.W), np.float64), np.empty((self.H, self.W), np.int32),
+               np.empty((self.H, self.W), np.int32))
+        for feature, a in enumerate(out):
+            _abi.check(self._lib.pt_read_features(self._ctx, feature, a.ctypes.data_as(C.c_void_p)), "pt_read_features")
+        return out
+
+    def LoadFeatures(self, albedo, normal, depth, kind) -> None:
+        """Install a host's own features (pt_write_features; layouts as Features()): a pixel is a hit
+        where kind >= 0, and the material becomes -1."""
+        a = np.ascontiguousarray(albedo, np.float64)
+        n = np.ascontiguousarray(normal, np.float32)
+        z = np.ascontiguousarray(depth, np.float64)
+        k = np.ascontiguousarray(kind, np.int32)
+        assert a.shape == n.shape == (self.H, self.W, 3) and z.shape == k.shape == (self.H, self.W)
+        _abi.check(self._lib.pt_write_features(self._ctx, a.ctypes.data_as(C.POINTER(C.c_double)),
+                                               n.ctypes.data_as(C.POINTER(C.c_float)),
+                                               z.ctypes.data_as(C.POINTER(C.c_double)),
+                                               k.ctypes.data_as(C.POINTER(C.c_int32))), "pt_write_features")
 
     def _read_denoised(self, fmt: int, out: np.ndarray) -> np.ndarray:
         _abi.check(self._lib.pt_read_denoised(self._ctx, int(fmt), out.ctypes.data_as(C.c_void_p)), "pt_read_denoised")
@@ -367,10 +411,15 @@ class Renderer:
         (NumCPU == 1) or RenderParallel pass, including its adaptive / firefly phases.  With Denoise
         (Renderer.cs:731-761) each pass also writes albedo_channel.png, normal_channel.png and
         denoised_output.png beside the pass image (in pathTemplate's directory), and the denoised
-        image is returned; with no pathTemplate the Buffer is denoised once, after the last pass."""
+        image is returned; with no pathTemplate the Buffer is denoised once, after the last pass.  With
+        DenoiseGuided as well, the features are rendered once before the loop and the filter is the
+        guided one (pt_denoise_guided)."""
         self.iterations = iterations
         img = None
         denoised = None
+        guided = bool(self.Denoise and self.DenoiseGuided)
+        if guided:
+            self.RenderFeatures()
         for i in range(1, iterations + 1):
             if self.Verbose:
                 print(f"Iteration {i} of {iterations}")
@@ -385,11 +434,11 @@ class Renderer:
                     where = os.path.dirname(pathTemplate)
                     write_png(os.path.join(where, "albedo_channel.png"), self.Image(Channel.AlbedoChannel))
                     write_png(os.path.join(where, "normal_channel.png"), self.Image(Channel.NormalChannel))
-                    self.DenoiseBuffer()
+                    self.DenoiseBuffer(guided)
                     denoised = self.Denoised()
                     write_png(os.path.join(where, "denoised_output.png"), denoised)
         if self.Denoise and denoised is None:
-            self.DenoiseBuffer()
+            self.DenoiseBuffer(guided)
             denoised = self.Denoised()
         if self.DeviceImages:
             if img is None:
