@@ -1,7 +1,7 @@
 // pt_api.hip — C-ABI implementation of libptsharp_hip.so (include/ptsharp_hip.h).
 //
-// Host runtime around the gfx950 render kernels: scene flattening and BVH
-// build (replacing Scene.Compile / Tree.NewTree, Scene.cs:48-68), HBM-resident
+// Host runtime around the gfx950 render kernels: upload of the compiled scene
+// (pt_scene_compile.cpp flattens it and builds the BVHs on the host), HBM-resident
 // Welford buffer (Renderer.PBuffer, Renderer.cs:20), pass launch and timing
 // (RenderParallel + its stopwatch, Renderer.cs:199-213,470), ray statistics
 // (Scene.rays, Scene.cs:70-79), and the multi-GPU Buffer gather over RCCL.
@@ -17,9 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <future>
 #include <memory>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -29,6 +27,7 @@
 #include "pt_device.h"
 #include "pt_math.h"
 #include "pt_scene.h"
+#include "pt_scene_compile.h"
 #include "pt_wavefront.h"
 
 #pragma clang fp contract(off)
@@ -151,7 +150,6 @@ struct EventTimer : pt::LaunchTimer {
     void destroy() { for (auto e : pool) (void)hipEventDestroy(e); pool.clear(); }
 };
 
-struct TriBvhBuild;
 struct Ctx {
     int device = 0;
     int width = 0, height = 0;
@@ -212,7 +210,7 @@ struct Ctx {
     pt::WfPlan grids{};            // persistent grid sizes (pt::wavefront_grids), once per context
     EventTimer timer;
     double tri_build_ms = 0;       // last upload: host time to build (or wait for, or find) the triangle BVH
-    std::shared_ptr<const TriBvhBuild> tri_build;   // that build, shared with the other contexts of its geometry
+    std::shared_ptr<const pt::TriBvhBuild> tri_build;   // that build, shared with the other contexts of its geometry
                                                     // (released at the next upload and at pt_destroy)
 };
 
@@ -227,15 +225,6 @@ struct Ctx {
 // in one chunk).  A chunk small enough for the side stream (kSideStreamMaxRays) keeps a second shadow set
 // (ensure_wavefront), within the same budget.
 constexpr uint32_t kWfMinCapLimit = 1u << 20, kWfMaxCapLimit = 1u << 29;
-#ifndef PT_SDF_LDS_MAX
-#define PT_SDF_LDS_MAX 16384   // LDS bytes k_wf_sdf_* may stage the SDF programs in; 0: never
-#endif
-#ifndef PT_VOL_LDS_MAX
-#define PT_VOL_LDS_MAX 40960   // LDS bytes k_wf_vol_* may stage the scene's one Volume in (its uniform-cell table); 0: never
-#endif
-#ifndef PT_VOL_CELLS_MAX
-#define PT_VOL_CELLS_MAX (1ull << 30)   // bytes of cell-major Volume corners (8 per cell) a scene may hold; 0: none
-#endif
 #ifndef PT_EXTRA_CHUNK_MAX
 #define PT_EXTRA_CHUNK_MAX (64ull << 20)   // camera samples per chunk of the adaptive / firefly phases, at most (round 6: 32M → 64M with the 2^29-entry queues, C5 +1.8 %, profiles/r06ec_ab_extra_chunk.txt)
 #endif
@@ -427,448 +416,61 @@ void free_scene(Ctx* c) {
     c->has_scene = false;
 }
 
-inline float4 f4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
-inline float u2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-inline pt::v3 ld3(const float* p) { return pt::v3{p[0], p[1], p[2]}; }
-
-// Conservative AABB padding for the fp32 slab test (see k_render_pass).
-inline void pad_box(float* lo, float* hi) {
-    for (int k = 0; k < 3; k++) {
-        float m = std::max(std::fabs(lo[k]), std::fabs(hi[k]));
-        float e = m * 2.0e-6f + 1e-30f;
-        lo[k] = lo[k] - e;
-        hi[k] = hi[k] + e;
-    }
+bool env_off(const char* name) {   // "0": the option is off for this upload (tests)
+    const char* v = std::getenv(name);
+    return v && !std::strcmp(v, "0");
 }
 
-// Analytic shapes tested linearly by the refill traversal kernels when there are at most this many
-// (pt_scene.h ana_linear); 0: always through the analytic BVH.
-#ifndef PT_ANA_LINEAR
-#define PT_ANA_LINEAR 8
-#endif
-#ifndef PT_SHADE_ROUTE
-#define PT_SHADE_ROUTE 1   // the routed shade (pt_scene.h shade_route); 0: every vertex of a FULL scene through the FULL shade
-#endif
-#ifndef PT_ROUTE
-#define PT_ROUTE 1   // the routed split traversal (pt_scene.h route); 0: every ray through the FULL analytic half
-#endif
-
-// BVH2 → 4-wide nodes (pt_bvh.h collapse_bvh4) as device float4 rows.  The
-// collapse keeps every path's pushes within the kStackMax-entry traversal stack.
-// The triangle BVH: a binned-SAH BVH2 with kTriBins bins per axis and leaves of at most 3 triangles
-// (one leaf chunk), collapsed to 4-wide nodes by the SAH-optimal dynamic program (pt_bvh.h
-// collapse_bvh4_sah, a triangle test priced at kTriCost traversal steps).  Against 32 bins and the
-// greedy collapse: C4 nodes per closest-hit ray 8.51 → 8.27, 6025 → 6065 Mrays/s (profiles/r04ab1_*).
-// Making SAH's leaf decision always take a full chunk (3 triangles) measured slower.
-constexpr int kTriBins = 128;
-constexpr double kTriCost = 0.5;
-int pack_nodes(const pt::BvhResult& b, std::vector<float4>& out, int32_t& num_nodes, bool sah = false) {
-    pt::Bvh4Result r;
-    if (sah) pt::collapse_bvh4_sah(b, pt::kStack4Budget, r, 1.0, kTriCost, 3);
-    else pt::collapse_bvh4(b, pt::kStack4Budget, r);
-    if (r.stack_need > pt::kStack4Budget) return fail(PT_ERR_UNSUPPORTED, "BVH4 traversal stack bound exceeded");
-    out.resize(r.words.size() / 4);
-    std::memcpy(out.data(), r.words.data(), r.words.size() * sizeof(uint32_t));
-    num_nodes = (int32_t)r.nodes();
-    return PT_OK;
-}
-
-// ---- The triangle BVH, built once per process for identical geometry (Scene.Compile compiles a scene
-// once, Scene.cs:48-68; the reference has one Tree per Scene).  N contexts of one process (the .NET group
-// host, bench.py --gpus N) upload the same scene: the first pt_upload_scene builds the BVH (1.1 s at 1M
-// triangles on the host), the others wait for that build and upload its bytes.  The key is the triangle
-// count, the build parameters and two independent 64-bit hashes of the triangles' vertices in the
-// upload's order; the last two builds are kept.
-struct TriBvhBuild {
-    std::vector<uint32_t> order;      // BVH position -> index into tri_src
-    std::vector<float4> nodes, chunks;
-    int32_t num_nodes = 0;
-    float box[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int rc = PT_OK;
-    std::string err;
-};
-struct TriBvhKey {
-    uint64_t n = 0, h1 = 0, h2 = 0;
-    bool operator==(const TriBvhKey& o) const { return n == o.n && h1 == o.h1 && h2 == o.h2; }
-};
-struct TriBvhCache {
-    std::mutex mu;
-    std::vector<std::pair<TriBvhKey, std::shared_future<std::shared_ptr<const TriBvhBuild>>>> entries;
-    int64_t builds = 0, hits = 0;
-};
-TriBvhCache& tri_bvh_cache() {
-    static TriBvhCache c;
-    return c;
-}
-// A finished build that no context holds (only the cache's own reference): evictable.  Builds held by live
-// contexts and builds in progress are never evicted, so neither a host-only pt_scene_bvh_digest nor another
-// scene's upload can push out the build a context of this process would reuse.
-bool tri_bvh_evictable(const std::shared_future<std::shared_ptr<const TriBvhBuild>>& f) {
-    if (f.wait_for(std::chrono::seconds(0)) != std::future_status::ready) return false;
-    return f.get().use_count() <= 1;
-}
-constexpr size_t kTriBvhSpare = 2;   // unreferenced finished builds kept for a later upload of the same geometry
-TriBvhKey tri_bvh_key(const pt_scene_desc* d, const std::vector<int32_t>& tri_src) {
-    TriBvhKey k;
-    k.n = (uint64_t)tri_src.size() ^ ((uint64_t)kTriBins << 40) ^ ((uint64_t)(kTriCost * 1024) << 52);
-    uint64_t a = 0x243F6A8885A308D3ull, b = 0x13198A2E03707344ull;
-    auto mix = [](uint64_t x) {
-        x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
-        return x;
-    };
-    for (int32_t s : tri_src) {
-        uint32_t w[9];
-        std::memcpy(w, d->tri_v1 + 3 * (size_t)s, 12);
-        std::memcpy(w + 3, d->tri_v2 + 3 * (size_t)s, 12);
-        std::memcpy(w + 6, d->tri_v3 + 3 * (size_t)s, 12);
-        for (int j = 0; j < 9; j++) {
-            a = (a ^ w[j]) * 0x100000001B3ull;          // FNV-1a over 32-bit words
-            b = mix(b + w[j] + 0x9E3779B97F4A7C15ull);  // a splitmix chain
-        }
+// Copies a compiled scene's arrays (pt_scene_compile.h) to the device and returns its DevScene with the
+// pointer fields derived from their addresses.  The host arrays are in use until the stream is synchronised.
+int upload_host_scene(Ctx* c, const pt::HostScene& H, std::vector<pt::DevTexture>& texs, std::vector<pt::DevVolume>& vols,
+                      pt::DevScene& S) {
+    int rc;
+    S = H.S;
+    if ((rc = upload(c, H.lines, &S.lines))) return rc;
+    S.ana_nodes = S.tri_node_line0 == 0 ? nullptr : S.lines;
+    S.tri_nodes = S.tri_chunk_line0 == S.tri_node_line0 ? nullptr : S.lines + 8 * (size_t)S.tri_node_line0;
+    S.tri_chunks = S.lines_n == S.tri_chunk_line0 ? nullptr : S.lines + 8 * (size_t)S.tri_chunk_line0;
+    const float4* d_tri_sh = nullptr;
+    if ((rc = upload(c, H.tri_sh, &d_tri_sh))) return rc;
+    S.tri_recs = d_tri_sh;
+    S.tri_shade = d_tri_sh ? d_tri_sh + 3 : nullptr;
+    S.tri_uv = d_tri_sh && H.tri_uv ? d_tri_sh + 6 : nullptr;
+    if ((rc = upload(c, H.ana_recs, &S.ana_recs))) return rc;
+    if ((rc = upload(c, H.planes, &S.planes))) return rc;
+    if ((rc = upload(c, H.mats, &S.mats))) return rc;
+    if ((rc = upload(c, H.lights, &S.lights))) return rc;
+    const double* d_tex = nullptr;
+    if ((rc = upload(c, H.tex_data, &d_tex))) return rc;
+    for (const pt::HostTexture& t : H.texs) texs.push_back(pt::DevTexture{d_tex + t.off, t.w, t.h});
+    if ((rc = upload(c, texs, &S.texs))) return rc;
+    if ((rc = upload(c, H.sdf_prog, &S.sdf_prog))) return rc;
+    if ((rc = upload(c, H.sdf_params, &S.sdf_params))) return rc;
+    if ((rc = upload(c, H.sdf_shapes, &S.sdf_shapes))) return rc;
+    const double* d_vox = nullptr;
+    const pt::DevWindow* d_win = nullptr;
+    const int8_t* d_runs = nullptr;
+    const double* d_cells = nullptr;
+    if ((rc = upload(c, H.vox, &d_vox))) return rc;
+    if ((rc = upload(c, H.windows, &d_win))) return rc;
+    if ((rc = upload(c, H.vol_runs, &d_runs))) return rc;
+    if ((rc = upload(c, H.vol_cells, &d_cells))) return rc;
+    for (const pt::HostVolume& v : H.volumes) {
+        vols.push_back(v.v);
+        vols.back().data = d_vox + v.vox_off;
+        vols.back().windows = d_win ? d_win + v.win_off : nullptr;
+        vols.back().runs = d_runs ? d_runs + v.runs_off : nullptr;
+        vols.back().cells = v.cells_off >= 0 ? d_cells + v.cells_off : nullptr;
     }
-    k.h1 = a;
-    k.h2 = b;
-    return k;
-}
-std::shared_ptr<const TriBvhBuild> build_tri_bvh(const pt_scene_desc* d, const std::vector<int32_t>& tri_src) {
-    auto out = std::make_shared<TriBvhBuild>();
-    const size_t nt = tri_src.size();
-    std::vector<float> bmin(nt * 3), bmax(nt * 3);
-    for (size_t i = 0; i < nt; i++) {
-        int s = tri_src[i];
-        for (int k = 0; k < 3; k++) {
-            float a = d->tri_v1[3 * s + k], b = d->tri_v2[3 * s + k], cc = d->tri_v3[3 * s + k];
-            bmin[3 * i + k] = std::fmin(std::fmin(a, b), cc);
-            bmax[3 * i + k] = std::fmax(std::fmax(a, b), cc);
-        }
-        pad_box(&bmin[3 * i], &bmax[3 * i]);
-    }
-    pt::BvhResult tb;
-    pt::build_bvh(bmin.data(), bmax.data(), (int64_t)nt, 0, tb, 3, false, kTriBins);   // leaves fit one chunk
-    std::vector<float4> tri_recs(nt * 3);
-    for (size_t i = 0; i < nt; i++) {
-        int s = tri_src[tb.order[i]];
-        pt::v3 v1 = ld3(d->tri_v1 + 3 * s), v2 = ld3(d->tri_v2 + 3 * s), v3_ = ld3(d->tri_v3 + 3 * s);
-        pt::v3 e1 = pt::sub(v2, v1), e2 = pt::sub(v3_, v1);  // Triangle.cs:97-98
-        tri_recs[3 * i + 0] = f4(v1.x, v1.y, v1.z, e1.x);
-        tri_recs[3 * i + 1] = f4(e1.y, e1.z, e2.x, e2.y);
-        tri_recs[3 * i + 2] = f4(e2.z, 0.f, 0.f, 0.f);
-    }
-    // 8-wide nodes with quantized child boxes (pt_bvh.h collapse_bvh8q), leaf chunks (one
-    // 128-B line per leaf: the first record in word 0, up to three {v1, e1, e2})
-    pt::Bvh8Result b8;
-    pt::collapse_bvh8q(tb, pt::kStackMax, b8, 1.0, kTriCost, 3);
-    if (b8.stack_need > pt::kStackMax) {
-        out->rc = fail(PT_ERR_UNSUPPORTED, "BVH8 traversal stack bound exceeded");
-        out->err = g_last_error;
-        return out;
-    }
-    if (b8.chunk_first.size() > 0x1FFFFFFFu) {
-        out->rc = fail(PT_ERR_UNSUPPORTED, "too many triangle leaves");
-        out->err = g_last_error;
-        return out;
-    }
-    out->nodes.resize(b8.words.size() / 4);
-    std::memcpy(out->nodes.data(), b8.words.data(), b8.words.size() * sizeof(uint32_t));
-    out->num_nodes = (int32_t)b8.nodes();
-    out->chunks.resize(8 * b8.chunk_first.size());
-    for (size_t ci = 0; ci < b8.chunk_first.size(); ci++) {
-        float w[32] = {0.f};
-        const uint32_t first = b8.chunk_first[ci], cnt = b8.chunk_count[ci];
-        const uint32_t w0 = first | ((cnt - 1u) << 29);   // the first record, the count - 1 in bits 29-30
-        std::memcpy(&w[0], &w0, 4);
-        for (uint32_t t = 0; t < cnt; t++) {
-            const float* rf = reinterpret_cast<const float*>(&tri_recs[3 * (size_t)(first + t)]);
-            for (int j = 0; j < 9; j++) w[1 + 9 * t + j] = rf[j];
-        }
-        std::memcpy(&out->chunks[8 * ci], w, sizeof w);
-    }
-    if (!out->nodes.empty()) {   // root box = union of the root node's children (their quantized boxes)
-        const uint32_t* w = b8.words.data();
-        for (int ax = 0; ax < 3; ax++) { out->box[ax] = INFINITY; out->box[3 + ax] = -INFINITY; }
-        for (int k = 0; k < (int)(w[3] >> 28); k++) {
-            float lo[3], hi[3];
-            pt::bvh8_child_box(w, k, lo, hi);
-            for (int ax = 0; ax < 3; ax++) {
-                out->box[ax] = std::min(out->box[ax], lo[ax]);
-                out->box[3 + ax] = std::max(out->box[3 + ax], hi[ax]);
-            }
-        }
-    }
-    out->order = std::move(tb.order);
-    return out;
-}
-// The build for this geometry: the cached one, one in progress on another thread (waited for), or a new one.
-std::shared_ptr<const TriBvhBuild> tri_bvh_shared(const pt_scene_desc* d, const std::vector<int32_t>& tri_src) {
-    const TriBvhKey key = tri_bvh_key(d, tri_src);
-    TriBvhCache& C = tri_bvh_cache();
-    std::promise<std::shared_ptr<const TriBvhBuild>> mine;
-    std::shared_future<std::shared_ptr<const TriBvhBuild>> theirs;
-    {
-        std::lock_guard<std::mutex> lk(C.mu);
-        for (auto& e : C.entries)
-            if (e.first == key) { theirs = e.second; break; }
-        if (theirs.valid()) {
-            C.hits++;
-        } else {
-            C.builds++;
-            C.entries.emplace_back(key, mine.get_future().share());
-            // oldest first, only the evictable ones, down to kTriBvhSpare of them
-            size_t spare = 0;
-            for (auto& e : C.entries) spare += tri_bvh_evictable(e.second) ? 1 : 0;
-            for (size_t i = 0; i < C.entries.size() && spare > kTriBvhSpare;) {
-                if (tri_bvh_evictable(C.entries[i].second)) {
-                    C.entries.erase(C.entries.begin() + (long)i);
-                    spare--;
-                } else {
-                    i++;
-                }
-            }
-        }
-    }
-    if (theirs.valid()) {
-        std::shared_ptr<const TriBvhBuild> r = theirs.get();   // waits while another thread builds it
-        if (r->rc == PT_OK) return r;
-        return build_tri_bvh(d, tri_src);                        // that build failed: this thread's own error
-    }
-    std::shared_ptr<const TriBvhBuild> r = build_tri_bvh(d, tri_src);
-    mine.set_value(r);
-    if (r->rc != PT_OK) {   // a failed build is not kept
-        std::lock_guard<std::mutex> lk(C.mu);
-        for (size_t i = 0; i < C.entries.size(); i++)
-            if (C.entries[i].first == key) { C.entries.erase(C.entries.begin() + (long)i); break; }
-    }
-    return r;
-}
-
-// A context lets go of its build (next upload, pt_destroy): the last context of a geometry takes its cache entry
-// along, so the host memory (tens of MB at 1M triangles) lives as long as a context uses it.
-void tri_bvh_release(Ctx* c) {
-    if (!c->tri_build) return;
-    TriBvhCache& C = tri_bvh_cache();
-    std::lock_guard<std::mutex> lk(C.mu);
-    for (size_t i = 0; i < C.entries.size(); i++) {
-        auto& f = C.entries[i].second;
-        if (f.wait_for(std::chrono::seconds(0)) == std::future_status::ready && f.get() == c->tri_build &&
-            f.get().use_count() <= 2) {   // the cache's reference and this context's
-            C.entries.erase(C.entries.begin() + (long)i);
-            break;
-        }
-    }
-    c->tri_build.reset();
-}
-
-// Box of a light shape as Box.Center / Box.OuterRadius compute it (Box.cs:316-324).
-void light_sphere_of_box(pt::v3 mn, pt::v3 mx, pt::DevLight& L) {
-    pt::v3 center = pt::add(mn, pt::mul(pt::sub(mx, mn), pt::mk(0.5, 0.5, 0.5)));
-    L.center[0] = center.x; L.center[1] = center.y; L.center[2] = center.z;
-    L.radius = (double)pt::lengthf(pt::sub(mn, center));
-}
-
-// ---- §8f row 4 host side: SDF tree → postfix program, boxes (IShape.BoundingBox)
-struct HostBox { pt::v3 mn, mx; };
-inline HostBox box_extend(const HostBox& a, const HostBox& b) { return HostBox{pt::vmin(a.mn, b.mn), pt::vmax(a.mx, b.mx)}; }
-inline HostBox box_mul(const double* m, const HostBox& b) { HostBox r; pt::mat_box(m, b.mn, b.mx, r.mn, r.mx); return r; }
-inline void rows12(const double* m16, double* out) { for (int k = 0; k < 12; k++) out[k] = m16[k]; }
-
-// SDF.BoundingBox per node (SDF.cs:136-139, 191-195, 214-219, 280-284, 313-318, 344-353, 374-382, 413-434, 470-476, 509-530, 555-558)
-HostBox sdf_box(const pt_scene_desc* d, int ni) {
-    const pt_sdf_node& n = d->sdf_nodes[ni];
-    const double* P = n.params;
-    switch (n.op) {
-        case PT_SDF_SPHERE: { double r = P[0]; return HostBox{pt::mk(-r, -r, -r), pt::mk(r, r, r)}; }
-        case PT_SDF_CUBE: {
-            double x = (double)(float)P[0] / 2, y = (double)(float)P[1] / 2, z = (double)(float)P[2] / 2;
-            return HostBox{pt::mk(-x, -y, -z), pt::mk(x, y, z)};
-        }
-        case PT_SDF_CYLINDER: { double r = P[0], h = P[1] / 2; return HostBox{pt::mk(-r, -h, -r), pt::mk(r, h, r)}; }
-        case PT_SDF_CAPSULE: {
-            pt::v3 A = pt::mk(P[0], P[1], P[2]), B = pt::mk(P[3], P[4], P[5]);
-            pt::v3 a = pt::vmin(A, B), b = pt::vmax(A, B);
-            double r = P[6];   // SubScalar / AddScalar
-            return HostBox{pt::mk((double)a.x - r, (double)a.y - r, (double)a.z - r),
-                           pt::mk((double)b.x + r, (double)b.y + r, (double)b.z + r)};
-        }
-        case PT_SDF_TORUS: { double a = P[1], b = P[1] + P[0]; return HostBox{pt::mk(-b, -b, a), pt::mk(b, b, a)}; }
-        case PT_SDF_TRANSFORM: return box_mul(n.matrix, sdf_box(d, d->sdf_children[n.first_child]));
-        case PT_SDF_SCALE: {
-            double f = (double)(float)P[0];   // new Matrix().Scale(new Vector(f, f, f))
-            const double m[16] = {f, 0, 0, 0, 0, f, 0, 0, 0, 0, f, 0, 0, 0, 0, 1};
-            return box_mul(m, sdf_box(d, d->sdf_children[n.first_child]));
-        }
-        case PT_SDF_UNION:
-        case PT_SDF_INTERSECTION: {
-            HostBox r{pt::zero3(), pt::zero3()};
-            for (int i = 0; i < n.num_children; i++) {
-                HostBox b = sdf_box(d, d->sdf_children[n.first_child + i]);
-                r = i == 0 ? b : box_extend(r, b);
-            }
-            return r;
-        }
-        case PT_SDF_DIFFERENCE:
-            return n.num_children > 0 ? sdf_box(d, d->sdf_children[n.first_child]) : HostBox{pt::zero3(), pt::zero3()};
-        default: return HostBox{pt::zero3(), pt::zero3()};   // RepeatSDF: new Box()
-    }
-}
-
-// Postfix program of an SDF tree (pt_ext.h SdfOp): SDF.Evaluate's recursion unrolled.
-struct SdfCompiler {
-    const pt_scene_desc* d;
-    std::vector<pt::DevSdfIns> prog;
-    std::vector<double> params;
-    int ps = 0, vs = 0, max_ps = 0, max_vs = 0;
-    void emit(int op, const double* P, int np) {
-        prog.push_back(pt::DevSdfIns{op, (int32_t)params.size()});
-        for (int k = 0; k < np; k++) params.push_back(P[k]);
-        if (np == 0) params.push_back(0.0);
-    }
-    void value() { vs++; max_vs = std::max(max_vs, vs); }
-    void node(int ni) {
-        const pt_sdf_node& n = d->sdf_nodes[ni];
-        const double* P = n.params;
-        auto child = [&](int k) { return d->sdf_children[n.first_child + k]; };
-        switch (n.op) {
-            case PT_SDF_SPHERE: emit(pt::SDF_LEAF_SPHERE, P, 2); value(); return;
-            case PT_SDF_CUBE: {   // Size is a Vector: its halves are taken from the fp32 values
-                const double q[3] = {(double)(float)P[0], (double)(float)P[1], (double)(float)P[2]};
-                emit(pt::SDF_LEAF_CUBE, q, 3); value(); return;
-            }
-            case PT_SDF_CYLINDER: emit(pt::SDF_LEAF_CYLINDER, P, 2); value(); return;
-            case PT_SDF_CAPSULE: emit(pt::SDF_LEAF_CAPSULE, P, 8); value(); return;
-            case PT_SDF_TORUS: emit(pt::SDF_LEAF_TORUS, P, 4); value(); return;
-            case PT_SDF_TRANSFORM:
-            case PT_SDF_SCALE:
-            case PT_SDF_REPEAT: {
-                if (n.op == PT_SDF_TRANSFORM) {
-                    double inv[12];
-                    rows12(n.inverse, inv);
-                    emit(pt::SDF_PUSH_TRANSFORM, inv, 12);
-                } else if (n.op == PT_SDF_SCALE) {
-                    emit(pt::SDF_PUSH_SCALE, P, 1);
-                } else {
-                    const double st[3] = {(double)(float)P[0], (double)(float)P[1], (double)(float)P[2]};
-                    emit(pt::SDF_PUSH_REPEAT, st, 3);
-                }
-                ps++;
-                max_ps = std::max(max_ps, ps);
-                node(child(0));
-                emit(pt::SDF_POP_POINT, nullptr, 0);
-                ps--;
-                if (n.op == PT_SDF_SCALE) emit(pt::SDF_MUL, P, 1);
-                return;
-            }
-            default: {   // Union / Difference / Intersection: fold over the children in order
-                const int fold = n.op == PT_SDF_UNION ? pt::SDF_UNION : n.op == PT_SDF_DIFFERENCE ? pt::SDF_DIFFERENCE
-                                                                                               : pt::SDF_INTERSECTION;
-                if (n.num_children == 0) { emit(pt::SDF_CONST0, nullptr, 0); value(); return; }
-                node(child(0));
-                for (int k = 1; k < n.num_children; k++) {
-                    node(child(k));
-                    emit(fold, nullptr, 0);
-                    vs--;
-                }
-            }
-        }
-    }
-};
-
-// A volume view over host (validation / light registration) or device data.
-pt::DevVolume dev_volume(const pt_volume& v, const double* data, const pt::DevWindow* windows) {
-    pt::DevVolume o{};
-    o.data = data; o.windows = windows;
-    o.w = v.w; o.h = v.h; o.d = v.d; o.nwin = v.num_windows; o.zscale = v.zscale; o.zinv = pt::vol_zinv(v.zscale);
-    for (int k = 0; k < 3; k++) { o.bmin[k] = v.box_min[k]; o.bmax[k] = v.box_max[k]; }
-    return o;
-}
-
-int validate_scene(const pt_scene_desc* d) {
-    if (!d) return fail(PT_ERR_INVALID_ARG, "scene is NULL");
-    if (d->num_materials <= 0 || !d->materials) return fail(PT_ERR_INVALID_ARG, "scene has no materials");
-    if (d->num_shapes < 0 || (d->num_shapes > 0 && (!d->shape_kind || !d->shape_index)))
-        return fail(PT_ERR_INVALID_ARG, "shape arrays missing");
-    auto chk_mat = [&](const int32_t* m, int n) {
-        for (int i = 0; i < n; i++) if (m[i] < 0 || m[i] >= d->num_materials) return false;
-        return true;
-    };
-    if (d->num_spheres > 0 && (!d->sphere_center || !d->sphere_radius || !d->sphere_material ||
-                               !chk_mat(d->sphere_material, d->num_spheres)))
-        return fail(PT_ERR_INVALID_ARG, "bad sphere arrays");
-    if (d->num_cubes > 0 && (!d->cube_min || !d->cube_max || !d->cube_material || !chk_mat(d->cube_material, d->num_cubes)))
-        return fail(PT_ERR_INVALID_ARG, "bad cube arrays");
-    if (d->num_planes > 0 && (!d->plane_point || !d->plane_normal || !d->plane_material ||
-                              !chk_mat(d->plane_material, d->num_planes)))
-        return fail(PT_ERR_INVALID_ARG, "bad plane arrays");
-    if (d->num_triangles > 0 && (!d->tri_v1 || !d->tri_v2 || !d->tri_v3 || !d->tri_n1 || !d->tri_n2 || !d->tri_n3 ||
-                                 !d->tri_material || !chk_mat(d->tri_material, d->num_triangles)))
-        return fail(PT_ERR_INVALID_ARG, "bad triangle arrays");
-    if (d->num_meshes > 0 && (!d->mesh_first || !d->mesh_count)) return fail(PT_ERR_INVALID_ARG, "bad mesh arrays");
-    if (d->num_textures < 0 || (d->num_textures > 0 && !d->textures)) return fail(PT_ERR_INVALID_ARG, "bad texture arrays");
-    for (int i = 0; i < d->num_textures; i++) {
-        const pt_texture& t = d->textures[i];
-        if (t.width < 2 || t.height < 2 || !t.data)   // BilinearSample reads x0 + 1 / y0 + 1 (Texture.cs:198-206)
-            return fail(PT_ERR_INVALID_ARG, "texture " + std::to_string(i) + ": needs data and width, height >= 2");
-    }
-    auto chk_tex = [&](int32_t t) { return t >= 0 && t <= d->num_textures; };
-    for (int i = 0; i < d->num_materials; i++) {
-        const pt_material& m = d->materials[i];
-        if (!chk_tex(m.texture) || !chk_tex(m.normal_texture) || !chk_tex(m.bump_texture) || !chk_tex(m.gloss_texture))
-            return fail(PT_ERR_INVALID_ARG, "material " + std::to_string(i) + ": texture reference out of range");
-    }
-    if (!chk_tex(d->env_texture)) return fail(PT_ERR_INVALID_ARG, "env_texture out of range");
-    // §8f row 4
-    if (d->num_sdf_nodes < 0 || (d->num_sdf_nodes > 0 && (!d->sdf_nodes || !d->sdf_children)))
-        return fail(PT_ERR_INVALID_ARG, "bad SDF node arrays");
-    for (int i = 0; i < d->num_sdf_nodes; i++) {
-        const pt_sdf_node& n = d->sdf_nodes[i];
-        if (n.op < PT_SDF_SPHERE || n.op > PT_SDF_REPEAT) return fail(PT_ERR_INVALID_ARG, "SDF node " + std::to_string(i) + ": bad op");
-        const bool one = n.op == PT_SDF_TRANSFORM || n.op == PT_SDF_SCALE || n.op == PT_SDF_REPEAT;
-        const bool many = n.op >= PT_SDF_UNION && n.op <= PT_SDF_INTERSECTION;
-        if ((one && n.num_children != 1) || (!one && !many && n.num_children != 0) || n.num_children < 0)
-            return fail(PT_ERR_INVALID_ARG, "SDF node " + std::to_string(i) + ": wrong number of children");
-        for (int k = 0; k < n.num_children; k++) {
-            int c = d->sdf_children[n.first_child + k];
-            if (c < 0 || c >= i) return fail(PT_ERR_INVALID_ARG, "SDF node " + std::to_string(i) + ": children must precede their parent");
-        }
-    }
-    if (d->num_sdf_shapes < 0 || (d->num_sdf_shapes > 0 && !d->sdf_shapes)) return fail(PT_ERR_INVALID_ARG, "bad SDF shapes");
-    for (int i = 0; i < d->num_sdf_shapes; i++)
-        if (d->sdf_shapes[i].root < 0 || d->sdf_shapes[i].root >= d->num_sdf_nodes ||
-            d->sdf_shapes[i].material < 0 || d->sdf_shapes[i].material >= d->num_materials)
-            return fail(PT_ERR_INVALID_ARG, "SDF shape " + std::to_string(i) + ": bad root or material");
-    if (d->num_volumes < 0 || (d->num_volumes > 0 && !d->volumes)) return fail(PT_ERR_INVALID_ARG, "bad volumes");
-    for (int i = 0; i < d->num_volumes; i++) {
-        const pt_volume& v = d->volumes[i];
-        if (v.w < 1 || v.h < 1 || v.d < 1 || !v.data || v.num_windows < 0 || (v.num_windows > 0 && !v.windows))
-            return fail(PT_ERR_INVALID_ARG, "volume " + std::to_string(i) + ": bad grid or windows");
-        for (int k = 0; k < v.num_windows; k++)
-            if (v.windows[k].material < 0 || v.windows[k].material >= d->num_materials)
-                return fail(PT_ERR_INVALID_ARG, "volume " + std::to_string(i) + ": window material out of range");
-    }
-    if (d->num_transformed < 0 || (d->num_transformed > 0 && !d->transformed)) return fail(PT_ERR_INVALID_ARG, "bad transformed shapes");
-    for (int i = 0; i < d->num_transformed; i++) {
-        const pt_transformed_shape& x = d->transformed[i];
-        int lim = x.shape_kind == PT_SHAPE_SPHERE ? d->num_spheres : x.shape_kind == PT_SHAPE_CUBE ? d->num_cubes
-                : x.shape_kind == PT_SHAPE_PLANE ? d->num_planes : x.shape_kind == PT_SHAPE_SDF ? d->num_sdf_shapes
-                : x.shape_kind == PT_SHAPE_VOLUME ? d->num_volumes : x.shape_kind == PT_SHAPE_MESH ? d->num_meshes : -1;
-        if (lim < 0) return fail(PT_ERR_UNSUPPORTED, "transformed shape " + std::to_string(i) + ": inner kind not on the GPU path");
-        if (x.shape_index < 0 || x.shape_index >= lim) return fail(PT_ERR_INVALID_ARG, "transformed shape " + std::to_string(i) + ": inner index out of range");
-    }
-    if (d->num_triangles > 0 && ((d->tri_t1 != nullptr) != (d->tri_t2 != nullptr) || (d->tri_t1 != nullptr) != (d->tri_t3 != nullptr)))
-        return fail(PT_ERR_INVALID_ARG, "tri_t1/t2/t3 must be all set or all NULL");
-    for (int i = 0; i < d->num_shapes; i++) {
-        int k = d->shape_kind[i], j = d->shape_index[i];
-        int lim = k == PT_SHAPE_SPHERE ? d->num_spheres : k == PT_SHAPE_CUBE ? d->num_cubes
-                : k == PT_SHAPE_PLANE ? d->num_planes : k == PT_SHAPE_TRIANGLE ? d->num_triangles
-                : k == PT_SHAPE_MESH ? d->num_meshes : k == PT_SHAPE_SDF ? d->num_sdf_shapes
-                : k == PT_SHAPE_VOLUME ? d->num_volumes : k == PT_SHAPE_TRANSFORMED ? d->num_transformed : -1;
-        if (lim < 0) return fail(PT_ERR_UNSUPPORTED, "unsupported shape kind " + std::to_string(k));
-        if (j < 0 || j >= lim) return fail(PT_ERR_INVALID_ARG, "shape index out of range at shape " + std::to_string(i));
-        if (k == PT_SHAPE_MESH) {
-            int64_t f = d->mesh_first[j], n = d->mesh_count[j];
-            if (f < 0 || n < 0 || f + n > d->num_triangles) return fail(PT_ERR_INVALID_ARG, "mesh range out of bounds");
-        }
-    }
-    return PT_OK;
+    if ((rc = upload(c, vols, &S.volumes))) return rc;
+    if ((rc = upload(c, H.xforms, &S.xforms))) return rc;
+    if ((rc = upload(c, H.ext_recs, &S.ext_recs))) return rc;
+    if ((rc = upload(c, H.blas, &S.blas))) return rc;
+    if ((rc = upload(c, H.blas_nodes, &S.blas_nodes))) return rc;
+    if ((rc = upload(c, H.blas_recs, &S.blas_recs))) return rc;
+    if ((rc = upload(c, H.blas_shade, &S.blas_shade))) return rc;
+    if ((rc = upload(c, H.blas_uv, &S.blas_uv))) return rc;
+    return upload(c, H.heavy, &S.heavy);
 }
 
 }  // namespace
@@ -943,506 +545,35 @@ int pt_reset_buffer(void* ctx) {
 int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
-    int rc = validate_scene(d);
-    if (rc != PT_OK) return rc;
+    std::string err;
+    int rc = pt::validate_scene(d, err);   // a scene that does not validate leaves the context's scene as it is
+    if (rc != PT_OK) return fail(rc, err);
+    pt::CompileOptions opt;   // read at each upload: tests flip them between uploads
+    opt.vol_cells = !env_off("PT_VOL_CELLS");
+    opt.vol_lds = !env_off("PT_VOL_LDS");
+    opt.route = !env_off("PT_ROUTE");
     PT_HIP(hipSetDevice(c->device));
     auto t0 = std::chrono::steady_clock::now();
     free_scene(c);
-
-    std::vector<pt::DevMaterial> mats((size_t)d->num_materials);
-    for (int i = 0; i < d->num_materials; i++) {
-        const pt_material& m = d->materials[i];
-        pt::DevMaterial& o = mats[(size_t)i];
-        for (int k = 0; k < 3; k++) o.color[k] = m.color[k];
-        o.emittance = m.emittance;
-        o.tint = m.tint;
-        o.transparent = m.transparent;
-        o.index = m.index;
-        o.gloss = m.gloss;
-        o.reflectivity = m.reflectivity;
-        o.tex = m.texture - 1; o.ntex = m.normal_texture - 1; o.btex = m.bump_texture - 1; o.gtex = m.gloss_texture - 1;
-        o.bump_multiplier = m.bump_multiplier;
-    }
-    // textures: one fp64 texel array in HBM, DevTexture views into it
-    std::vector<size_t> tex_off((size_t)std::max(d->num_textures, 0));
-    size_t texels = 0;
-    for (int i = 0; i < d->num_textures; i++) {
-        tex_off[(size_t)i] = texels;
-        texels += 3 * (size_t)d->textures[i].width * (size_t)d->textures[i].height;
-    }
-    std::vector<double> tex_data(texels);
-    for (int i = 0; i < d->num_textures; i++)
-        std::memcpy(tex_data.data() + tex_off[(size_t)i], d->textures[i].data,
-                    3 * (size_t)d->textures[i].width * (size_t)d->textures[i].height * sizeof(double));
-
-    // --- gather primitives in Scene.Shapes order
-    std::vector<int32_t> ana_kind, ana_scene;     // analytic prims (sphere, cube, SDF, volume, transformed)
-    std::vector<int32_t> tri_src;                  // source triangle index per BVH triangle
-    std::vector<int32_t> plane_scene;
-    for (int i = 0; i < d->num_shapes; i++) {
-        int k = d->shape_kind[i], j = d->shape_index[i];
-        if (k == PT_SHAPE_PLANE) plane_scene.push_back(j);
-        else if (k == PT_SHAPE_TRIANGLE) tri_src.push_back(j);
-        else if (k == PT_SHAPE_MESH) for (int t = 0; t < d->mesh_count[j]; t++) tri_src.push_back(d->mesh_first[j] + t);
-        else { ana_kind.push_back(k); ana_scene.push_back(j); }
-    }
-    if ((int64_t)tri_src.size() >= (int64_t)(1u << 29) || ana_kind.size() >= (1u << 29))
-        return fail(PT_ERR_UNSUPPORTED, "more than 2^29 primitives");
-
-    // --- §8f row 4 tables: SDF programs, volumes, transformed shapes
-    mats.push_back(pt::DevMaterial{});   // `new Material()` (Volume.MaterialAt's fallback)
-    for (auto& m : mats.back().color) m = 0.0;
-    mats.back().tex = mats.back().ntex = mats.back().btex = mats.back().gtex = -1;
-    const int32_t default_mat = d->num_materials;
-    SdfCompiler sdfc{d};
-    std::vector<pt::DevSdfShape> sdf_shapes((size_t)std::max(d->num_sdf_shapes, 0));
-    std::vector<HostBox> sdf_boxes(sdf_shapes.size());
-    for (size_t i = 0; i < sdf_shapes.size(); i++) {
-        pt::DevSdfShape& o = sdf_shapes[i];
-        o.begin = (int32_t)sdfc.prog.size();
-        sdfc.ps = sdfc.vs = 0;
-        sdfc.node(d->sdf_shapes[i].root);
-        o.len = (int32_t)sdfc.prog.size() - o.begin;
-        o.mat = d->sdf_shapes[i].material;
-        int leaves = 0, folds = 0;   // a chain: one leaf, no fold (pt_ext.h sdf_eval_chain)
-        for (int k = o.begin; k < o.begin + o.len; k++) {
-            const int op = sdfc.prog[(size_t)k].op;
-            if (op <= pt::SDF_LEAF_TORUS) leaves++;
-            if (op == pt::SDF_UNION || op == pt::SDF_DIFFERENCE || op == pt::SDF_INTERSECTION || op == pt::SDF_CONST0) folds++;
-        }
-        o.chain = (leaves == 1 && folds == 0) ? 1 : 0;
-        sdf_boxes[i] = sdf_box(d, d->sdf_shapes[i].root);   // SDFShape.BoundingBox (SDF.cs:100-103)
-        o.bmin[0] = sdf_boxes[i].mn.x; o.bmin[1] = sdf_boxes[i].mn.y; o.bmin[2] = sdf_boxes[i].mn.z;
-        o.bmax[0] = sdf_boxes[i].mx.x; o.bmax[1] = sdf_boxes[i].mx.y; o.bmax[2] = sdf_boxes[i].mx.z;
-    }
-    if (sdfc.max_ps + 1 > pt::kSdfStack || sdfc.max_vs > pt::kSdfStack)
-        return fail(PT_ERR_UNSUPPORTED, "SDF tree nested deeper than the device evaluator's stacks");
-    std::vector<pt::DevWindow> windows;
-    std::vector<size_t> vol_off, win_off;
-    size_t voxels = 0;
-    for (int i = 0; i < d->num_volumes; i++) {
-        const pt_volume& v = d->volumes[i];
-        vol_off.push_back(voxels);
-        win_off.push_back(windows.size());
-        voxels += (size_t)v.w * v.h * v.d;
-        for (int k = 0; k < v.num_windows; k++)
-            windows.push_back(pt::DevWindow{v.windows[k].lo, v.windows[k].hi, v.windows[k].material, 0});
-    }
-    std::vector<double> vox(voxels);
-    for (int i = 0; i < d->num_volumes; i++)
-        std::memcpy(vox.data() + vol_off[(size_t)i], d->volumes[i].data,
-                    (size_t)d->volumes[i].w * d->volumes[i].h * d->volumes[i].d * sizeof(double));
-    // host views (Scene.Add's MaterialAt(new Vector()) for light registration)
-    auto host_volume = [&](int i) { return dev_volume(d->volumes[i], vox.data() + vol_off[(size_t)i], windows.data() + win_off[(size_t)i]); };
-    // uniform-cell tables of the march skip (pt_ext.h vol_build_runs), one per volume
-    std::vector<int8_t> vol_runs;
-    std::vector<size_t> runs_off;
-    std::vector<int32_t> zero_sign((size_t)std::max(d->num_volumes, 0));
-    for (int i = 0; i < d->num_volumes; i++) {
-        const pt_volume& v = d->volumes[i];
-        runs_off.push_back(vol_runs.size());
-        vol_runs.resize(vol_runs.size() + (size_t)(v.w + 1) * (v.h + 1) * (v.d + 1));
-        pt::vol_build_runs(host_volume(i), vol_runs.data() + runs_off.back(), zero_sign[(size_t)i]);
-    }
-    // cell-major corners of the march (pt_ext.h vol_build_cells), per volume while they stay within
-    // PT_VOL_CELLS_MAX bytes in all; cells_off = -1: the march reads the grid
-    std::vector<double> vol_cells;
-    std::vector<int64_t> cells_off((size_t)std::max(d->num_volumes, 0), -1);
-    const char* cells_env = std::getenv("PT_VOL_CELLS");   // "0" at upload: the march reads the grid (tests)
-    for (int i = 0; i < d->num_volumes && !(cells_env && !std::strcmp(cells_env, "0")); i++) {
-        const pt_volume& v = d->volumes[i];
-        const size_t n = 8 * (size_t)(v.w + 1) * (v.h + 1) * (v.d + 1);
-        if ((vol_cells.size() + n) * sizeof(double) > (size_t)PT_VOL_CELLS_MAX) continue;
-        cells_off[(size_t)i] = (int64_t)vol_cells.size();
-        vol_cells.resize(vol_cells.size() + n);
-        pt::vol_build_cells(host_volume(i), vol_cells.data() + cells_off[(size_t)i]);
-    }
-    const pt::v3 origin = pt::zero3();
-    // IShape.BoundingBox of a shape that can be analytic or inner (exact, as the reference computes it)
-    auto shape_box = [&](int k, int j) -> HostBox {
-        switch (k) {
-            case PT_SHAPE_SPHERE: {
-                const float* cc = d->sphere_center + 3 * j;
-                double r = d->sphere_radius[j];
-                return HostBox{pt::mk((double)cc[0] - r, (double)cc[1] - r, (double)cc[2] - r),
-                               pt::mk((double)cc[0] + r, (double)cc[1] + r, (double)cc[2] + r)};
-            }
-            case PT_SHAPE_CUBE: return HostBox{ld3(d->cube_min + 3 * j), ld3(d->cube_max + 3 * j)};
-            case PT_SHAPE_PLANE: return HostBox{pt::mk(-1e9, -1e9, -1e9), pt::mk(1e9, 1e9, 1e9)};
-            case PT_SHAPE_SDF: return sdf_boxes[(size_t)j];
-            case PT_SHAPE_VOLUME: return HostBox{ld3(d->volumes[j].box_min), ld3(d->volumes[j].box_max)};
-            case PT_SHAPE_MESH: {   // Mesh.BoundingBox (Mesh.cs:88-120)
-                const int f = d->mesh_first[j], n = d->mesh_count[j];
-                if (n <= 0) return HostBox{pt::zero3(), pt::zero3()};
-                HostBox b{ld3(d->tri_v1 + 3 * f), ld3(d->tri_v1 + 3 * f)};
-                for (int t = f; t < f + n; t++) {
-                    b.mn = pt::vmin(pt::vmin(pt::vmin(b.mn, ld3(d->tri_v1 + 3 * t)), ld3(d->tri_v2 + 3 * t)), ld3(d->tri_v3 + 3 * t));
-                    b.mx = pt::vmax(pt::vmax(pt::vmax(b.mx, ld3(d->tri_v1 + 3 * t)), ld3(d->tri_v2 + 3 * t)), ld3(d->tri_v3 + 3 * t));
-                }
-                return b;
-            }
-        }
-        return HostBox{pt::zero3(), pt::zero3()};
-    };
-    // IShape.MaterialAt(p) of an analytic / inner shape
-    auto shape_mat = [&](int k, int j, pt::v3 p) -> int32_t {
-        switch (k) {
-            case PT_SHAPE_SPHERE: return d->sphere_material[j];
-            case PT_SHAPE_CUBE: return d->cube_material[j];
-            case PT_SHAPE_PLANE: return d->plane_material[j];
-            case PT_SHAPE_SDF: return d->sdf_shapes[j].material;
-            case PT_SHAPE_VOLUME: { pt::DevVolume v = host_volume(j); return pt::vol_material(v, p, default_mat); }
-        }
-        return default_mat;
-    };
-    // analytic-format record of a shape (top level: ana_recs; inner of a transformed shape: ext_recs)
-    auto make_rec = [&](int k, int j, int32_t ext_mat, float4* r) {
-        if (k == PT_SHAPE_SPHERE) {
-            const float* cc = d->sphere_center + 3 * j;
-            uint64_t rb; double rad = d->sphere_radius[j]; std::memcpy(&rb, &rad, 8);
-            r[0] = f4(cc[0], cc[1], cc[2], u2f(pt::KIND_SPHERE));
-            r[1] = f4(0.f, 0.f, 0.f, u2f((uint32_t)j));
-            r[2] = f4(u2f((uint32_t)d->sphere_material[j]), u2f((uint32_t)(rb & 0xFFFFFFFFu)), u2f((uint32_t)(rb >> 32)), 0.f);
-        } else if (k == PT_SHAPE_CUBE) {
-            const float* mn = d->cube_min + 3 * j; const float* mx = d->cube_max + 3 * j;
-            r[0] = f4(mn[0], mn[1], mn[2], u2f(pt::KIND_CUBE));
-            r[1] = f4(mx[0], mx[1], mx[2], u2f((uint32_t)j));
-            r[2] = f4(u2f((uint32_t)d->cube_material[j]), 0.f, 0.f, 0.f);
-        } else if (k == PT_SHAPE_PLANE) {
-            const float* pp = d->plane_point + 3 * j; const float* nn = d->plane_normal + 3 * j;
-            r[0] = f4(pp[0], pp[1], pp[2], u2f(pt::KIND_PLANE));
-            r[1] = f4(nn[0], nn[1], nn[2], u2f((uint32_t)j));
-            r[2] = f4(u2f((uint32_t)d->plane_material[j]), 0.f, 0.f, 0.f);
-        } else {   // SDF / volume / transformed: the shape lives in its table, `ext_mat` = MaterialAt(origin)
-            const int32_t kind = k == PT_SHAPE_SDF ? pt::KIND_SDF : k == PT_SHAPE_VOLUME ? pt::KIND_VOLUME : pt::KIND_XFORM;
-            r[0] = f4(0.f, 0.f, 0.f, u2f((uint32_t)kind));
-            r[1] = f4(0.f, 0.f, 0.f, u2f((uint32_t)j));
-            r[2] = f4(u2f((uint32_t)ext_mat), u2f((uint32_t)j), 0.f, 0.f);
-        }
-    };
-    // instanced meshes: one object-space BVH4 per distinct inner mesh (BLAS), records in their own arrays
-    std::vector<pt::DevBlas> blas;
-    std::vector<float4> blas_nodes, blas_recs, blas_shade, blas_uv;
-    std::vector<int32_t> blas_of_mesh((size_t)std::max(d->num_meshes, 0), -1);
-    for (int i = 0; i < d->num_transformed; i++) {
-        const pt_transformed_shape& x = d->transformed[i];
-        if (x.shape_kind != PT_SHAPE_MESH || blas_of_mesh[(size_t)x.shape_index] >= 0) continue;
-        const int f = d->mesh_first[x.shape_index], n = d->mesh_count[x.shape_index];
-        std::vector<float> lo((size_t)n * 3), hi((size_t)n * 3);
-        for (int t = 0; t < n; t++)
-            for (int k = 0; k < 3; k++) {
-                float a = d->tri_v1[3 * (f + t) + k], b = d->tri_v2[3 * (f + t) + k], cc = d->tri_v3[3 * (f + t) + k];
-                lo[3 * (size_t)t + k] = std::fmin(std::fmin(a, b), cc);
-                hi[3 * (size_t)t + k] = std::fmax(std::fmax(a, b), cc);
-            }
-        for (int t = 0; t < n; t++) pad_box(&lo[3 * (size_t)t], &hi[3 * (size_t)t]);
-        pt::BvhResult bb;
-        pt::build_bvh(lo.data(), hi.data(), (int64_t)n, 0, bb);
-        std::vector<float4> nodes;
-        int32_t nn = 0;
-        if ((rc = pack_nodes(bb, nodes, nn))) return rc;
-        pt::DevBlas B{(int32_t)(blas_nodes.size() / 8), nn, (int32_t)(blas_recs.size() / 3), 0};
-        blas_nodes.insert(blas_nodes.end(), nodes.begin(), nodes.end());
-        for (int t = 0; t < n; t++) {
-            const int src = f + (int)bb.order[(size_t)t];
-            pt::v3 v1 = ld3(d->tri_v1 + 3 * src), v2 = ld3(d->tri_v2 + 3 * src), v3_ = ld3(d->tri_v3 + 3 * src);
-            pt::v3 e1 = pt::sub(v2, v1), e2 = pt::sub(v3_, v1);
-            blas_recs.push_back(f4(v1.x, v1.y, v1.z, e1.x));
-            blas_recs.push_back(f4(e1.y, e1.z, e2.x, e2.y));
-            blas_recs.push_back(f4(e2.z, 0.f, 0.f, 0.f));
-            const float* n1 = d->tri_n1 + 3 * src; const float* n2 = d->tri_n2 + 3 * src; const float* n3 = d->tri_n3 + 3 * src;
-            blas_shade.push_back(f4(n1[0], n1[1], n1[2], n2[0]));
-            blas_shade.push_back(f4(n2[1], n2[2], n3[0], n3[1]));
-            blas_shade.push_back(f4(n3[2], u2f((uint32_t)d->tri_material[src]), 0.f, 0.f));
-            const float zero[3] = {0.f, 0.f, 0.f};
-            const float* t1 = d->tri_t1 ? d->tri_t1 + 3 * src : zero;
-            const float* t2 = d->tri_t2 ? d->tri_t2 + 3 * src : zero;
-            const float* t3 = d->tri_t3 ? d->tri_t3 + 3 * src : zero;
-            blas_uv.push_back(f4(t1[0], t1[1], t2[0], t2[1]));
-            blas_uv.push_back(f4(t3[0], t3[1], 0.f, 0.f));
-        }
-        blas_of_mesh[(size_t)x.shape_index] = (int32_t)blas.size();
-        blas.push_back(B);
-    }
-    std::vector<pt::DevXform> xforms((size_t)std::max(d->num_transformed, 0));
-    std::vector<float4> ext_recs(xforms.size() * 3);
-    std::vector<HostBox> xform_boxes(xforms.size()), xform_bvh_boxes(xforms.size());
-    // Hits of marched shapes can sit just outside their box (SDF: start 1e-4 and a 1e-3 jump back;
-    // Volume: one step of 1/512 before the box): the BVH boxes are widened by that much.
-    auto march_pad = [](int k) { return k == PT_SHAPE_SDF ? 2e-3 : k == PT_SHAPE_VOLUME ? 4.0 / 512 : 0.0; };
-    for (size_t i = 0; i < xforms.size(); i++) {
-        const pt_transformed_shape& x = d->transformed[i];
-        pt::DevXform& o = xforms[i];
-        rows12(x.matrix, o.m);
-        rows12(x.inverse, o.inv);
-        o.kind = x.shape_kind == PT_SHAPE_SDF ? pt::KIND_SDF : x.shape_kind == PT_SHAPE_VOLUME ? pt::KIND_VOLUME
-               : x.shape_kind == PT_SHAPE_MESH ? pt::KIND_MESH : x.shape_kind;
-        o.rec = x.shape_kind == PT_SHAPE_MESH ? blas_of_mesh[(size_t)x.shape_index] : (int32_t)i;
-        if (x.shape_kind != PT_SHAPE_MESH)
-            make_rec(x.shape_kind, x.shape_index, shape_mat(x.shape_kind, x.shape_index, origin), &ext_recs[3 * i]);
-        HostBox ib = shape_box(x.shape_kind, x.shape_index);
-        xform_boxes[i] = box_mul(x.matrix, ib);   // TransformedShape.BoundingBox (TransformedShape.cs:36-39)
-        const double mp = march_pad(x.shape_kind);
-        HostBox pb{pt::mk((double)ib.mn.x - mp, (double)ib.mn.y - mp, (double)ib.mn.z - mp),
-                   pt::mk((double)ib.mx.x + mp, (double)ib.mx.y + mp, (double)ib.mx.z + mp)};
-        xform_bvh_boxes[i] = box_mul(x.matrix, pb);
-    }
-    auto shape_mat_any = [&](int k, int j, pt::v3 p) -> int32_t {   // including TransformedShape.MaterialAt
-        if (k == PT_SHAPE_TRANSFORMED) return shape_mat(d->transformed[j].shape_kind, d->transformed[j].shape_index, p);
-        return shape_mat(k, j, p);
-    };
-
-    // --- triangle BVH (built once per process for the same geometry: tri_bvh_shared)
-    const size_t nt = tri_src.size();
-    const auto tbuild_t0 = std::chrono::steady_clock::now();
-    const std::shared_ptr<const TriBvhBuild> tbv = tri_bvh_shared(d, tri_src);
-    tri_bvh_release(c);   // the previous upload's build
-    if (tbv->rc == PT_OK) c->tri_build = tbv;
-    c->tri_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tbuild_t0).count();
-    if (tbv->rc != PT_OK) return fail(tbv->rc, tbv->err);
-    std::vector<float4> tri_recs(nt * 3), tri_shade(nt * 3);
-    const bool want_uv = d->num_textures > 0 && nt > 0;   // texture coordinates only matter with textures
-    std::vector<float4> tri_uv(want_uv ? nt * 2 : 0);
-    for (size_t i = 0; i < nt; i++) {
-        int s = tri_src[tbv->order[i]];
-        pt::v3 v1 = ld3(d->tri_v1 + 3 * s), v2 = ld3(d->tri_v2 + 3 * s), v3_ = ld3(d->tri_v3 + 3 * s);
-        pt::v3 e1 = pt::sub(v2, v1), e2 = pt::sub(v3_, v1);  // Triangle.cs:97-98
-        tri_recs[3 * i + 0] = f4(v1.x, v1.y, v1.z, e1.x);
-        tri_recs[3 * i + 1] = f4(e1.y, e1.z, e2.x, e2.y);
-        tri_recs[3 * i + 2] = f4(e2.z, 0.f, 0.f, 0.f);
-        const float* n1 = d->tri_n1 + 3 * s; const float* n2 = d->tri_n2 + 3 * s; const float* n3 = d->tri_n3 + 3 * s;
-        tri_shade[3 * i + 0] = f4(n1[0], n1[1], n1[2], n2[0]);
-        tri_shade[3 * i + 1] = f4(n2[1], n2[2], n3[0], n3[1]);
-        tri_shade[3 * i + 2] = f4(n3[2], u2f((uint32_t)d->tri_material[s]), 0.f, 0.f);
-        if (want_uv) {
-            const float zero[3] = {0.f, 0.f, 0.f};
-            const float* t1 = d->tri_t1 ? d->tri_t1 + 3 * s : zero;
-            const float* t2 = d->tri_t2 ? d->tri_t2 + 3 * s : zero;
-            const float* t3 = d->tri_t3 ? d->tri_t3 + 3 * s : zero;
-            tri_uv[2 * i + 0] = f4(t1[0], t1[1], t2[0], t2[1]);
-            tri_uv[2 * i + 1] = f4(t3[0], t3[1], 0.f, 0.f);
-        }
-    }
-    const std::vector<float4>& tri_nodes = tbv->nodes;
-    const int32_t tri_num_nodes = tbv->num_nodes;
-    const std::vector<float4>& tri_chunks = tbv->chunks;
-    float tri_box[6];
-    std::memcpy(tri_box, tbv->box, sizeof tri_box);
-
-    // --- analytic BVH (spheres, cubes, SDF shapes, volumes, transformed shapes)
-    const size_t na = ana_kind.size();
-    std::vector<float> amin(na * 3), amax(na * 3);
-    for (size_t i = 0; i < na; i++) {
-        int k = ana_kind[i], j = ana_scene[i];
-        if (k == PT_SHAPE_SPHERE) {
-            double r = d->sphere_radius[j];
-            for (int q = 0; q < 3; q++) {
-                double cc = d->sphere_center[3 * j + q];
-                amin[3 * i + q] = std::nextafter((float)(cc - r), -INFINITY);
-                amax[3 * i + q] = std::nextafter((float)(cc + r), INFINITY);
-            }
-        } else {
-            HostBox b = k == PT_SHAPE_TRANSFORMED ? xform_bvh_boxes[(size_t)j] : shape_box(k, j);
-            const double mp = k == PT_SHAPE_TRANSFORMED ? 0.0 : march_pad(k);
-            const float lo[3] = {b.mn.x, b.mn.y, b.mn.z}, hi[3] = {b.mx.x, b.mx.y, b.mx.z};
-            for (int q = 0; q < 3; q++) {
-                amin[3 * i + q] = (float)((double)lo[q] - mp);
-                amax[3 * i + q] = (float)((double)hi[q] + mp);
-            }
-        }
-        pad_box(&amin[3 * i], &amax[3 * i]);
-    }
-    pt::BvhResult ab;
-    pt::build_bvh(amin.data(), amax.data(), (int64_t)na, 0, ab);
-    std::vector<float4> ana_recs(na * 3);
-    // position in ana_recs of each shape (first occurrence), per kind: Sampler's identity test
-    std::vector<std::vector<int32_t>> ana_pos(8);
-    const int32_t counts[8] = {d->num_spheres, d->num_cubes, 0, 0, 0, d->num_sdf_shapes, d->num_volumes, d->num_transformed};
-    for (int k = 0; k < 8; k++) ana_pos[(size_t)k].assign((size_t)std::max(counts[k], 0), -1);
-    for (size_t i = 0; i < na; i++) {
-        size_t src = ab.order[i];
-        int k = ana_kind[src], j = ana_scene[src];
-        make_rec(k, j, shape_mat_any(k, j, origin), &ana_recs[3 * i]);
-        if (ana_pos[(size_t)k][(size_t)j] < 0) ana_pos[(size_t)k][(size_t)j] = (int32_t)i;
-    }
-    // the row-4 records (SDF shapes, volumes, transformed shapes) with their BVH boxes, in record order:
-    // what the routed split's refill kernels test against a ray's segment (pt_scene.h route)
-    std::vector<float4> heavy;
-    for (size_t i = 0; i < na; i++) {
-        const size_t src = ab.order[i];
-        const int k = ana_kind[src];
-        if (k != PT_SHAPE_SDF && k != PT_SHAPE_VOLUME && k != PT_SHAPE_TRANSFORMED) continue;
-        heavy.push_back(f4(amin[3 * src], amin[3 * src + 1], amin[3 * src + 2], u2f((uint32_t)i)));
-        heavy.push_back(f4(amax[3 * src], amax[3 * src + 1], amax[3 * src + 2], 0.f));
-    }
-    std::vector<float4> ana_nodes;
-    int32_t ana_num_nodes = 0;
-    if ((rc = pack_nodes(ab, ana_nodes, ana_num_nodes))) return rc;
-
-    // --- planes
-    std::vector<float4> planes(plane_scene.size() * 2);
-    std::vector<int32_t> plane_pos_of_scene(d->num_planes > 0 ? d->num_planes : 0, -1);
-    for (size_t i = 0; i < plane_scene.size(); i++) {
-        int j = plane_scene[i];
-        const float* p = d->plane_point + 3 * j; const float* n = d->plane_normal + 3 * j;
-        planes[2 * i] = f4(p[0], p[1], p[2], u2f((uint32_t)d->plane_material[j]));
-        planes[2 * i + 1] = f4(n[0], n[1], n[2], u2f((uint32_t)j));
-        if (plane_pos_of_scene[(size_t)j] < 0) plane_pos_of_scene[(size_t)j] = (int32_t)i;
-    }
-
-    // --- lights, Scene.Add order (Scene.cs:29-38): MaterialAt(new Vector()).Emittance > 0
-    std::vector<pt::DevLight> lights;
-    for (int i = 0; i < d->num_shapes; i++) {
-        int k = d->shape_kind[i], j = d->shape_index[i];
-        int mat = k == PT_SHAPE_TRIANGLE ? d->tri_material[j] : k == PT_SHAPE_MESH ? -1 : shape_mat_any(k, j, origin);
-        if (mat < 0 || mat >= d->num_materials || !(d->materials[mat].emittance > 0)) continue;  // Mesh: `default`
-        pt::DevLight L{};
-        L.kind = k; L.mat = mat; L.phantom = 0;
-        if (k == PT_SHAPE_SPHERE) {   // Sampler.cs:218-223
-            L.index = ana_pos[PT_SHAPE_SPHERE][(size_t)j];
-            const float* cc = d->sphere_center + 3 * j;
-            L.center[0] = cc[0]; L.center[1] = cc[1]; L.center[2] = cc[2];
-            L.radius = d->sphere_radius[j];
-        } else if (k == PT_SHAPE_PLANE) {
-            L.index = plane_pos_of_scene[(size_t)j];
-            light_sphere_of_box(pt::mk(-1e9, -1e9, -1e9), pt::mk(1e9, 1e9, 1e9), L);  // Plane.BoundingBox
-        } else if (k == PT_SHAPE_TRIANGLE) {  // a directly-added struct Triangle: never passes the identity test
-            L.index = -1; L.phantom = 1;
-            pt::v3 a = ld3(d->tri_v1 + 3 * j), b = ld3(d->tri_v2 + 3 * j), cc = ld3(d->tri_v3 + 3 * j);
-            light_sphere_of_box(pt::vmin(pt::vmin(a, b), cc), pt::vmax(pt::vmax(a, b), cc), L);
-        } else {   // Cube, SDFShape, Volume: class shapes; TransformedShape: a struct, never identical
-            const int32_t kind = k == PT_SHAPE_CUBE ? pt::KIND_CUBE : k == PT_SHAPE_SDF ? pt::KIND_SDF
-                               : k == PT_SHAPE_VOLUME ? pt::KIND_VOLUME : pt::KIND_XFORM;
-            L.kind = kind;
-            L.index = ana_pos[(size_t)k][(size_t)j];
-            L.phantom = k == PT_SHAPE_TRANSFORMED;
-            HostBox b = k == PT_SHAPE_TRANSFORMED ? xform_boxes[(size_t)j] : shape_box(k, j);   // light.BoundingBox()
-            light_sphere_of_box(b.mn, b.mx, L);
-        }
-        lights.push_back(L);
-    }
-
-    pt::DevScene S{};
-    std::memcpy(S.tri_box, tri_box, sizeof tri_box);
-    {   // the traversal lines: [ana_nodes | tri_nodes | tri_chunks], 8 float4 per node / chunk
-        std::vector<float4> lines;
-        lines.reserve(ana_nodes.size() + tri_nodes.size() + tri_chunks.size());
-        lines.insert(lines.end(), ana_nodes.begin(), ana_nodes.end());
-        lines.insert(lines.end(), tri_nodes.begin(), tri_nodes.end());
-        lines.insert(lines.end(), tri_chunks.begin(), tri_chunks.end());
-        if (lines.size() >= 0xFFFFFFFFull) return fail(PT_ERR_UNSUPPORTED, "more than 2^29 BVH lines");   // 32-bit piece offsets
-        rc = upload(c, lines, &S.lines); if (rc) return rc;
-        S.lines_n = (uint32_t)(lines.size() / 8);
-        S.tri_node_line0 = (uint32_t)(ana_nodes.size() / 8);
-        S.tri_chunk_line0 = (uint32_t)((ana_nodes.size() + tri_nodes.size()) / 8);
-        S.ana_nodes = ana_nodes.empty() ? nullptr : S.lines;
-        S.tri_nodes = tri_nodes.empty() ? nullptr : S.lines + 8 * (size_t)S.tri_node_line0;
-        S.tri_chunks = tri_chunks.empty() ? nullptr : S.lines + 8 * (size_t)S.tri_chunk_line0;
-    }
-    // one 128-B shading record per triangle (pt_scene.h tri_rstride): what k_wf_shade reads
-    // for a triangle hit is one line instead of two or three
-    std::vector<float4> tri_sh(nt * 8, f4(0.f, 0.f, 0.f, 0.f));
-    for (size_t i = 0; i < nt; i++) {
-        for (int k = 0; k < 3; k++) tri_sh[8 * i + k] = tri_recs[3 * i + k];
-        for (int k = 0; k < 3; k++) tri_sh[8 * i + 3 + k] = tri_shade[3 * i + k];
-        if (want_uv)
-            for (int k = 0; k < 2; k++) tri_sh[8 * i + 6 + k] = tri_uv[2 * i + k];
-    }
-    const float4* d_tri_sh = nullptr;
-    rc = upload(c, tri_sh, &d_tri_sh); if (rc) return rc;
-    S.tri_recs = d_tri_sh;
-    S.tri_shade = d_tri_sh ? d_tri_sh + 3 : nullptr;
-    S.tri_uv = d_tri_sh && want_uv ? d_tri_sh + 6 : nullptr;
-    S.tri_rstride = 8;
-    S.tri_ustride = 8;
-    rc = upload(c, ana_recs, &S.ana_recs); if (rc) return rc;
-    rc = upload(c, planes, &S.planes); if (rc) return rc;
-    rc = upload(c, mats, &S.mats); if (rc) return rc;
-    rc = upload(c, lights, &S.lights); if (rc) return rc;
-    const double* d_tex = nullptr;
-    rc = upload(c, tex_data, &d_tex); if (rc) return rc;
-    std::vector<pt::DevTexture> texs((size_t)std::max(d->num_textures, 0));
-    for (int i = 0; i < d->num_textures; i++)
-        texs[(size_t)i] = pt::DevTexture{d_tex + tex_off[(size_t)i], d->textures[i].width, d->textures[i].height};
-    rc = upload(c, texs, &S.texs); if (rc) return rc;
-    S.env_tex = d->env_texture - 1;
-    S.env_angle = d->env_texture_angle;
-    rc = upload(c, sdfc.prog, &S.sdf_prog); if (rc) return rc;
-    rc = upload(c, sdfc.params, &S.sdf_params); if (rc) return rc;
-    {   // the SDF programs, staged in LDS by the SDF queue kernels when small (pt_wavefront.hip stage_sdf)
-        const size_t need = sdfc.prog.size() * sizeof(pt::DevSdfIns) + sdfc.params.size() * sizeof(double);
-        S.sdf_prog_n = (int32_t)sdfc.prog.size();
-        S.sdf_lds = (!sdfc.prog.empty() && need <= (size_t)PT_SDF_LDS_MAX) ? (int32_t)need : 0;
-    }
-    rc = upload(c, sdf_shapes, &S.sdf_shapes); if (rc) return rc;
-    const double* d_vox = nullptr;
-    const pt::DevWindow* d_win = nullptr;
-    rc = upload(c, vox, &d_vox); if (rc) return rc;
-    rc = upload(c, windows, &d_win); if (rc) return rc;
-    const int8_t* d_runs = nullptr;
-    rc = upload(c, vol_runs, &d_runs); if (rc) return rc;
-    const double* d_cells = nullptr;
-    rc = upload(c, vol_cells, &d_cells); if (rc) return rc;
+    pt::HostScene H;
+    rc = pt::compile_scene(d, opt, H, err);
+    // the previous upload's build goes after the new one was looked up, so re-uploading a geometry finds it;
+    // a failed compile leaves the context without scene and without build
+    const auto t1 = std::chrono::steady_clock::now();
+    pt::tri_bvh_release(c->tri_build);
+    c->tri_build = std::move(H.tri_build);
+    c->tri_build_ms = H.tri_build_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    if (rc != PT_OK) return fail(rc, err);
+    std::vector<pt::DevTexture> texs;
     std::vector<pt::DevVolume> vols;
-    for (int i = 0; i < d->num_volumes; i++) {
-        vols.push_back(dev_volume(d->volumes[i], d_vox + vol_off[(size_t)i], d_win ? d_win + win_off[(size_t)i] : nullptr));
-        vols.back().runs = d_runs ? d_runs + runs_off[(size_t)i] : nullptr;
-        vols.back().zero_sign = zero_sign[(size_t)i];
-        vols.back().cells = cells_off[(size_t)i] >= 0 ? d_cells + cells_off[(size_t)i] : nullptr;
-    }
-    rc = upload(c, vols, &S.volumes); if (rc) return rc;
-    S.vol_lds = 0;
-    const char* lds_env = std::getenv("PT_VOL_LDS");   // "0" at upload: no staging (tests)
-    if (d->num_volumes == 1 && !vol_runs.empty() && !(lds_env && !std::strcmp(lds_env, "0"))) {   // k_wf_vol_* stage it in LDS (pt_wavefront.hip stage_vol)
-        const size_t need = pt::kVolLdsHeader + (((size_t)d->volumes[0].num_windows * sizeof(pt::DevWindow) + 15) & ~(size_t)15) +
-                            ((vol_runs.size() + 15) & ~(size_t)15);
-        if (need <= (size_t)PT_VOL_LDS_MAX) S.vol_lds = (int32_t)need;
-    }
-    rc = upload(c, xforms, &S.xforms); if (rc) return rc;
-    rc = upload(c, ext_recs, &S.ext_recs); if (rc) return rc;
-    rc = upload(c, blas, &S.blas); if (rc) return rc;
-    rc = upload(c, blas_nodes, &S.blas_nodes); if (rc) return rc;
-    rc = upload(c, blas_recs, &S.blas_recs); if (rc) return rc;
-    rc = upload(c, blas_shade, &S.blas_shade); if (rc) return rc;
-    rc = upload(c, blas_uv, &S.blas_uv); if (rc) return rc;
-    S.default_mat = default_mat;
-    S.full_geom = (d->num_sdf_shapes > 0 || d->num_volumes > 0 || d->num_transformed > 0) ? 1 : 0;
-    S.full = (d->num_textures > 0 || S.full_geom) ? 1 : 0;
-    S.tri_num_nodes = tri_num_nodes;
-    S.ana_num_nodes = ana_num_nodes;
-    S.ana_count = (int32_t)na;
-    // C4's floor cube and two light spheres: a linear test of 3 records at refill costs less than a BVH
-    // node step (seven loads through the texture path) and leaf record loads per ray
-    S.ana_linear = (na > 0 && na <= (size_t)PT_ANA_LINEAR && !S.full_geom) ? 1 : 0;
-    S.num_sdf = d->num_sdf_shapes;
-    S.num_vol = d->num_volumes;
-    S.lights_lean = 1;
-    for (const pt::DevLight& L : lights)
-        if (!L.phantom && (L.kind == pt::KIND_SDF || L.kind == pt::KIND_VOLUME || L.kind == pt::KIND_XFORM)) S.lights_lean = 0;
-    // Routed split (C5's kind of scene: the 1M-triangle mesh, a floor cube, light spheres, one SDF shape and
-    // one transformed Volume): only the rays whose segment reaches a row-4 box take the FULL kernels
-    // (environment PT_ROUTE=0 at upload: every ray through the FULL analytic half, as a -DPT_ROUTE=0 build;
-    // tests compare the two, whose only possible difference is the exact-t tie order of DESIGN.md §5)
-    const char* route_env = std::getenv("PT_ROUTE");
-    const bool route_on = PT_ROUTE && !(route_env && !std::strcmp(route_env, "0"));
-    S.route = (route_on && S.full_geom && S.lights_lean && na <= (size_t)PT_ANA_LINEAR && !heavy.empty() &&
-               tri_num_nodes > 64) ? 1 : 0;
-    S.heavy_count = (int32_t)(heavy.size() / 2);
-    bool mat_tex = false;
-    for (const auto& m : mats) mat_tex = mat_tex || m.tex >= 0 || m.ntex >= 0 || m.btex >= 0 || m.gtex >= 0;
-    S.shade_route = (PT_SHADE_ROUTE && S.full && !mat_tex && S.lights_lean) ? 1 : 0;   // (a Volume light's colour is FULL work)
-    rc = upload(c, heavy, &S.heavy); if (rc) return rc;
-    S.num_planes = (int32_t)plane_scene.size();
-    S.num_lights = (int32_t)lights.size();
-    S.num_mats = (int32_t)mats.size();
-    for (int k = 0; k < 3; k++) S.env[k] = d->env_color[k];
+    pt::DevScene S{};
+    if ((rc = upload_host_scene(c, H, texs, vols, S))) return rc;
     PT_HIP(hipStreamSynchronize(c->stream));
     c->S = S;
     c->has_scene = true;
-    c->stats.bvh_nodes = (uint64_t)tri_num_nodes + (uint64_t)ana_num_nodes;
-    c->stats.traversal_bytes = (tri_nodes.size() + tri_chunks.size() + ana_nodes.size() + ana_recs.size()) * sizeof(float4);
-    c->stats.bvh_bytes = (tri_nodes.size() + tri_chunks.size() + ana_nodes.size()) * sizeof(float4) +
-                         (tri_sh.size() + ana_recs.size()) * sizeof(float4);
+    c->stats.bvh_nodes = H.bvh_nodes;
+    c->stats.traversal_bytes = H.traversal_bytes;
+    c->stats.bvh_bytes = H.bvh_bytes;
     c->stats.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PT_OK;
 }
@@ -2125,15 +1256,10 @@ int pt_occluded(void* ctx, int64_t n, const float* origins, const float* dirs, c
 
 int pt_scene_bvh_digest(const pt_scene_desc* d, uint64_t out[4]) {
     if (!out) return fail(PT_ERR_INVALID_ARG, "out is NULL");
-    const int rc = validate_scene(d);
-    if (rc != PT_OK) return rc;
-    std::vector<int32_t> tri_src;
-    for (int i = 0; i < d->num_shapes; i++) {   // pt_upload_scene's triangle order
-        const int k = d->shape_kind[i], j = d->shape_index[i];
-        if (k == PT_SHAPE_TRIANGLE) tri_src.push_back(j);
-        else if (k == PT_SHAPE_MESH) for (int t = 0; t < d->mesh_count[j]; t++) tri_src.push_back(d->mesh_first[j] + t);
-    }
-    const std::shared_ptr<const TriBvhBuild> b = tri_bvh_shared(d, tri_src);
+    std::string err;
+    const int rc = pt::validate_scene(d, err);
+    if (rc != PT_OK) return fail(rc, err);
+    const std::shared_ptr<const pt::TriBvhBuild> b = pt::tri_bvh_shared(d, pt::gather_tri_src(d));   // pt_upload_scene's triangle order
     if (b->rc != PT_OK) return fail(b->rc, b->err);
     uint64_t h = 0xCBF29CE484222325ull;
     auto eat = [&](const void* p, size_t n) {
@@ -2145,10 +1271,9 @@ int pt_scene_bvh_digest(const pt_scene_desc* d, uint64_t out[4]) {
     eat(b->chunks.data(), b->chunks.size() * sizeof(float4));
     out[0] = h;
     out[1] = (uint64_t)(b->nodes.size() + b->chunks.size()) * sizeof(float4);
-    TriBvhCache& C = tri_bvh_cache();
-    std::lock_guard<std::mutex> lk(C.mu);
-    out[2] = (uint64_t)C.builds;
-    out[3] = (uint64_t)C.hits;
+    const pt::TriBvhStats cs = pt::tri_bvh_stats();
+    out[2] = (uint64_t)cs.builds;
+    out[3] = (uint64_t)cs.hits;
     return PT_OK;
 }
 
@@ -2165,7 +1290,7 @@ void pt_destroy(void* ctx) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    tri_bvh_release(c);
+    pt::tri_bvh_release(c->tri_build);
     free_scene(c);
     free_wavefront(c);
     if (c->d_m) (void)hipFree(c->d_m);

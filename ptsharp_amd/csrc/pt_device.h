@@ -21,7 +21,7 @@ struct HitRec {
 };
 
 // A whole traversal stack in a private array (scratch): the nested traversal of an instanced mesh, whose
-// object-space BVH4 keeps every path within kStack4Budget pushes (pack_nodes checks it).  Sized by that bound,
+// object-space BVH4 keeps every path within kStack4Budget pushes (pt_scene_compile.cpp pack_nodes checks it).  Sized by that bound,
 // not by the triangle BVH8's kStackMax (64 since round 5: 128 B more scratch per lane for no use).
 struct LocalStack {
     static constexpr int kLds = kStack4Budget;
@@ -391,7 +391,7 @@ __device__ __forceinline__ bool traverse(const DevScene& S, const float4* __rest
                                          "+v"((q).x), "+v"((q).y), "+v"((q).z), "+v"((q).w))
 
 
-// The triangles of a leaf chunk (pt_api.hip build_tri_bvh): word 0 = the first triangle
+// The triangles of a leaf chunk (pt_scene_compile.cpp build_tri_bvh): word 0 = the first triangle
 // record, triangle k = words 1 + 9k .. 9 + 9k as {v1, e1, e2}; a0..a2 is the first, b the
 // second, c the third (shifted down after each test).  A chunk of cnt triangles is read with its
 // first 1 + 2·cnt 16-B pieces; the rest of q is stale and never tested.
@@ -400,7 +400,7 @@ __device__ __forceinline__ bool traverse(const DevScene& S, const float4* __rest
     v3 b0{q2.z, q2.w, q3.x}, b1{q3.y, q3.z, q3.w}, b2{q4.x, q4.y, q4.z};                  \
     const v3 c0{q4.w, q5.x, q5.y}, c1{q5.z, q5.w, q6.x}, c2{q6.y, q6.z, q6.w}
 
-// Triangle-BVH traversal over leaf chunks (pt_api.hip build_tri_bvh).  The node step is
+// Triangle-BVH traversal over leaf chunks (pt_scene_compile.cpp build_tri_bvh).  The node step is
 // node8_step's (8-wide quantized nodes); a leaf ref points at a 128-B chunk of up to three
 // triangles, so an inner step and a leaf step read the same 128-B line's 16-B pieces and a
 // wave whose lanes are split between nodes and leaves pays for one set of load

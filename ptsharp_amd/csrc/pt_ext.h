@@ -1,7 +1,7 @@
 // pt_ext.h — §8f row 4 shapes on the render path: SDFShape (SDF.cs), Volume
 // (Volume.cs) and TransformedShape (TransformedShape.cs).
 //
-// Layout in HBM (pt_api.hip builds it):
+// Layout in HBM (pt_scene_compile.cpp builds it, pt_api.hip uploads it):
 //   SDF trees are compiled on the host into one postfix program per SDFShape: point-
 //   stack pushes for TransformSDF / ScaleSDF / RepeatSDF, a leaf op per primitive SDF
 //   and a binary fold per Union / Difference / Intersection child, so the device

@@ -1,5 +1,5 @@
 // pt_scene.h — device-resident scene layout (HBM) shared by the host runtime
-// and the gfx950 kernels.
+// (pt_scene_compile.cpp fills it, pt_api.hip uploads it) and the gfx950 kernels.
 //
 // Hot / cold split: traversal touches only node pairs (64 B) and primitive
 // records (48 B, three 16-B loads from one line); shading data (normals,
@@ -55,7 +55,7 @@ struct DevScene {
     const float4* tri_nodes;   // 2 float4 per node (pt::BvhNode)
     int32_t tri_num_nodes;
     const float4* tri_recs;    // 3 float4 per triangle: {v1.xyz,e1.x} {e1.yz,e2.xy} {e2.z,-,-,-}
-    const float4* tri_chunks;  // 8 float4 per triangle leaf (pt_api.hip build_tri_bvh)
+    const float4* tri_chunks;  // 8 float4 per triangle leaf (pt_scene_compile.cpp build_tri_bvh)
     const float4* tri_shade;   // 3 float4 per triangle: {n1.xyz,n2.x} {n2.yz,n3.xy} {n3.z,mat,-,-}
     // analytic BVH (spheres, cubes)
     const float4* ana_nodes;

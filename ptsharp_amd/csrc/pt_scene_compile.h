@@ -1,0 +1,93 @@
+// pt_scene_compile.h — host-only scene compilation: a pt_scene_desc turned into the bytes pt_upload_scene
+// copies to the device (replacing Scene.Compile / Tree.NewTree, Scene.cs:48-68).  Nothing here touches the
+// GPU: pt_scene_compile.cpp is built by the host compiler, pt_api.hip uploads a HostScene's arrays and
+// derives the DevScene's pointer fields from their device addresses.
+#pragma once
+#include <stdint.h>
+
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/ptsharp_hip.h"
+#include "pt_scene.h"
+
+namespace pt {
+
+// What pt_upload_scene reads from the environment at each upload (tests flip them between uploads);
+// the compile itself reads no environment.
+struct CompileOptions {
+    bool vol_cells = true;   // PT_VOL_CELLS=0: no cell-major Volume corners, the march reads the grid
+    bool vol_lds = true;     // PT_VOL_LDS=0: the scene's one Volume is not staged in LDS
+    bool route = true;       // PT_ROUTE=0: every ray through the FULL analytic half
+};
+
+// The triangle BVH of one geometry, shared by every context of the process that uploads it (tri_bvh_shared).
+struct TriBvhBuild {
+    std::vector<uint32_t> order;      // BVH position -> index into tri_src
+    std::vector<float4> nodes, chunks;
+    int32_t num_nodes = 0;
+    float box[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int rc = PT_OK;
+    std::string err;
+};
+
+struct HostTexture {
+    size_t off;   // first texel component in tex_data
+    int32_t w, h;
+};
+struct HostVolume {
+    DevVolume v;   // every field but the pointers (data, windows, runs, cells), which are the offsets below
+    size_t vox_off, win_off, runs_off;   // into vox, windows, vol_runs
+    int64_t cells_off;                   // into vol_cells; -1: the march reads the grid
+};
+
+// A compiled scene on the host: every array pt_upload_scene uploads, and the DevScene with every
+// non-pointer field filled.
+struct HostScene {
+    std::vector<float4> lines;   // [ana nodes | tri nodes | tri chunks], 8 float4 per line (S.tri_node_line0, S.tri_chunk_line0)
+    std::vector<float4> tri_sh;  // one 128-B shading record per triangle: recs at +0, shade at +3, uv at +6
+    bool tri_uv = false;         // tri_sh carries texture coordinates (a scene with textures and triangles)
+    std::vector<float4> ana_recs, planes, heavy;
+    std::vector<DevMaterial> mats;   // the scene's, then `new Material()` (S.default_mat)
+    std::vector<DevLight> lights;
+    std::vector<double> tex_data;
+    std::vector<HostTexture> texs;
+    std::vector<DevSdfIns> sdf_prog;
+    std::vector<double> sdf_params;
+    std::vector<DevSdfShape> sdf_shapes;
+    std::vector<double> vox;
+    std::vector<DevWindow> windows;
+    std::vector<int8_t> vol_runs;
+    std::vector<double> vol_cells;
+    std::vector<HostVolume> volumes;
+    std::vector<DevXform> xforms;
+    std::vector<float4> ext_recs;
+    std::vector<DevBlas> blas;
+    std::vector<float4> blas_nodes, blas_recs, blas_shade, blas_uv;
+    DevScene S{};
+    uint64_t bvh_nodes = 0, traversal_bytes = 0, bvh_bytes = 0;   // pt_stats
+    std::shared_ptr<const TriBvhBuild> tri_build;   // the shared triangle build `lines` was filled from
+    double tri_build_ms = 0;                        // host time to build (or wait for, or find) it
+};
+
+// Validates and compiles.  PT_OK, or an error code with its message in err (H is then partly filled; its
+// tri_build is set once the triangle BVH was found or built).
+int compile_scene(const pt_scene_desc* d, const CompileOptions& opt, HostScene& H, std::string& err);
+
+int validate_scene(const pt_scene_desc* d, std::string& err);
+// Source triangle of every triangle of the world BVH, in Scene.Shapes order (loose triangles and top-level meshes).
+std::vector<int32_t> gather_tri_src(const pt_scene_desc* d);
+
+// The build for this geometry: the cached one, one in progress on another thread (waited for), or a new one.
+std::shared_ptr<const TriBvhBuild> tri_bvh_shared(const pt_scene_desc* d, const std::vector<int32_t>& tri_src);
+// A holder lets go of its build (next upload, pt_destroy): the last holder of a geometry takes its cache entry
+// along, so the host memory (tens of MB at 1M triangles) lives as long as a context uses it.
+void tri_bvh_release(std::shared_ptr<const TriBvhBuild>& build);
+struct TriBvhStats {
+    int64_t builds, hits;   // since the process started
+    size_t entries;         // builds the cache holds now
+};
+TriBvhStats tri_bvh_stats();
+
+}  // namespace pt

@@ -3,7 +3,7 @@
 //     first, child indices in range, every node reached once from the root, the stack bound (the pushes
 //     Σ (children - 1) on every root-to-leaf path) within kStackMax and equal to the reported need;
 //   * boxes: every slot box on a primitive's path (bvh8_child_box, exact decode) holds the primitive's padded
-//     box (pt_api.hip pad_box); empty slots are +inf / -inf;
+//     box (pt_scene_compile.cpp pad_box); empty slots are +inf / -inf;
 //   * the device's slab arithmetic (pt_device.h node8_step: fma(q, step/d, (origin - o)/d) in fp32, near /
 //     far by direction sign, the far distance widened by 2^-21 relative) restated here: a ray whose exact
 //     fp64 slab test enters a primitive's box before tmax also enters every quantized box on that
@@ -79,7 +79,7 @@ static bool slab_exact(const Box& b, const float o[3], const float d[3], double 
 
 static void run_case(const char* name, std::vector<float>& lo, std::vector<float>& hi, int rays, unsigned seed) {
     const int64_t n = (int64_t)lo.size() / 3;
-    // the tree is built on the boxes padded as pt_api.hip pad_box pads them (the fp32 slab tests' margin);
+    // the tree is built on the boxes padded as pt_scene_compile.cpp pad_box pads them (the fp32 slab tests' margin);
     // the rays below test the exact, unpadded boxes
     std::vector<float> plo = lo, phi = hi;
     for (int64_t i = 0; i < n; i++)

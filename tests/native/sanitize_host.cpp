@@ -6,6 +6,10 @@
 // links the sanitised objects directly and exercises the same paths the CPU suite does:
 //   * pt_bvh.cpp  — the threaded binned-SAH build (8 threads) and the BVH4 collapse, with the
 //                   structural invariants checked (every primitive once, boxes nested);
+//   * pt_scene_compile.cpp — compile_scene on the fixed scene of scene_fixture.h (every branch of the compile),
+//                   then 8 threads compiling one 2000-triangle geometry at once: the process-wide
+//                   triangle-BVH cache (a shared_future per geometry) builds it once, every thread holds
+//                   that build, and releasing them all lets the entry go; then another geometry;
 //   * pt_obj.cpp  — pt_obj_load on well-formed files (v, v/vt, v/vt/vn, v//vn, CRLF, tabs, a
 //                   line longer than the read block), on malformed ones (every error path), and
 //                   pt_mesh_smooth_normals on the result;
@@ -20,11 +24,14 @@
 #include <cstring>
 #include <random>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/ptsharp_hip.h"
 #include "../../oracle/oracle.h"
 #include "../../ptsharp_amd/csrc/pt_bvh.h"
+#include "../../ptsharp_amd/csrc/pt_scene_compile.h"
+#include "scene_fixture.h"
 
 static int failures = 0;
 #define CHECK(c)                                                                  \
@@ -67,6 +74,52 @@ static void bvh_case(int64_t n, int threads, unsigned seed) {
     CHECK(b4.nodes() > 0);
     std::printf("bvh: %lld prims, %d threads: %zu BVH2 nodes (depth %d), %zu BVH4 nodes (stack %d)\n", (long long)n,
                 threads, b2.nodes.size(), b2.max_depth, b4.nodes(), b4.stack_need);
+}
+
+static void scene_compile_cases() {
+    {
+        FixScene s;
+        fixed_scene(s, false);
+        pt::HostScene H;
+        std::string err;
+        CHECK(pt::compile_scene(&s.d, pt::CompileOptions{}, H, err) == PT_OK);
+        CHECK(H.lines.size() == 8 * (size_t)H.S.lines_n && H.lights.size() == 5 && H.blas.size() == 1);
+        pt::tri_bvh_release(H.tri_build);
+    }
+    const pt::TriBvhStats before = pt::tri_bvh_stats();
+    {   // N contexts uploading one scene from N threads: one build, shared
+        FixScene s;
+        big_scene(s, 2000, 7);
+        const int T = 8;
+        std::vector<pt::HostScene> H((size_t)T);
+        std::vector<int> rc((size_t)T, -1);
+        std::vector<std::thread> th;
+        for (int t = 0; t < T; t++)
+            th.emplace_back([&, t] { std::string err; rc[(size_t)t] = pt::compile_scene(&s.d, pt::CompileOptions{}, H[(size_t)t], err); });
+        for (auto& x : th) x.join();
+        const pt::TriBvhStats mid = pt::tri_bvh_stats();
+        CHECK(mid.builds == before.builds + 1 && mid.hits == before.hits + T - 1 && mid.entries == before.entries + 1);
+        for (int t = 0; t < T; t++) {
+            CHECK(rc[(size_t)t] == PT_OK && H[(size_t)t].tri_build && H[(size_t)t].tri_build == H[0].tri_build);
+            CHECK(H[(size_t)t].lines.size() == H[0].lines.size() &&   // as bytes: node words are no floats
+                  !std::memcmp(H[(size_t)t].lines.data(), H[0].lines.data(), H[0].lines.size() * sizeof(float4)));
+        }
+        th.clear();
+        for (int t = 0; t < T; t++) th.emplace_back([&, t] { pt::tri_bvh_release(H[(size_t)t].tri_build); });
+        for (auto& x : th) x.join();
+        CHECK(pt::tri_bvh_stats().entries == before.entries);   // the last holder took the entry along
+        std::printf("scene_compile: %d threads, %lld build, %lld hits\n", T, (long long)(mid.builds - before.builds),
+                    (long long)(mid.hits - before.hits));
+    }
+    {
+        FixScene s;
+        big_scene(s, 2000, 8);
+        pt::HostScene H;
+        std::string err;
+        CHECK(pt::compile_scene(&s.d, pt::CompileOptions{}, H, err) == PT_OK);
+        CHECK(pt::tri_bvh_stats().builds == before.builds + 2);
+        pt::tri_bvh_release(H.tri_build);
+    }
 }
 
 static std::string write_file(const char* name, const std::string& body) {
@@ -220,6 +273,7 @@ int main() {
     bvh_case(200000, 8, 2);
     bvh_case(37, 8, 3);
     bvh_case(1, 1, 4);
+    scene_compile_cases();
     obj_cases();
     oracle_cases(8);
     if (failures) {

@@ -413,7 +413,7 @@ static void build(const Mesh& m, const std::string& variant, Tree& T, double& bu
         for (int k = 0; k < 3; k++) {
             const float a = m.v1[3 * i + k], b = m.v2[3 * i + k], c = m.v3[3 * i + k];
             float l = std::fmin(std::fmin(a, b), c), h = std::fmax(std::fmax(a, b), c);
-            const float e = std::fmax(std::fabs(l), std::fabs(h)) * 2.0e-6f + 1e-30f;   // pt_api.hip pad_box
+            const float e = std::fmax(std::fabs(l), std::fabs(h)) * 2.0e-6f + 1e-30f;   // pt_scene_compile.cpp pad_box
             lo[3 * i + k] = l - e; hi[3 * i + k] = h + e;
         }
     const auto t0 = std::chrono::steady_clock::now();
