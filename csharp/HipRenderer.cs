@@ -206,6 +206,8 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_stats_get(IntPtr ctx, out pt_stats stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_scene_bvh_digest(ref pt_scene_desc scene, ulong[] out4);
         // Scene.Intersect of a batch of rays / the shadow query against a t (PT_MARCH_* flags: the Volume march form)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_triangles(IntPtr ctx, int numTriangles, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tri_bvh(IntPtr ctx, long[] counts, uint[] nodes, uint[] chunks, uint[] records, float[] box);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr pt_last_error();
@@ -596,6 +598,32 @@ namespace PTSharpCore
             var p = new PtHip.pt_denoise_params { iterations = DenoiseIterations, reserved = 0, sigma_colour = DenoiseSigmaColour };
             PtHip.Check(PtHip.pt_denoise(ctx, ref p, out double ms), "pt_denoise");
             return ms;
+        }
+
+        /// <summary>New vertex positions (and optionally normals, all three or none) for every triangle of the
+        /// uploaded scene, [n * 3] floats in the upload's order (pt_update_triangles): the triangle BVH is
+        /// refitted on the device, nothing is rebuilt.  The caller keeps its own scene in step.  Returns the
+        /// device time of the kernels in ms.</summary>
+        public double UpdateTriangles(float[] v1, float[] v2, float[] v3, float[] n1 = null, float[] n2 = null, float[] n3 = null)
+        {
+            if (!uploaded) Upload();
+            PtHip.Check(PtHip.pt_update_triangles(ctx, v1.Length / 3, v1, v2, v3, n1, n2, n3, out double ms), "pt_update_triangles");
+            return ms;
+        }
+
+        /// <summary>The context's triangle BVH as it stands on the device (pt_read_tri_bvh): 32 words per node,
+        /// leaf chunk and triangle record, and the root box.</summary>
+        public (uint[] nodes, uint[] chunks, uint[] records, float[] box) ReadTriBvh()
+        {
+            if (!uploaded) Upload();
+            var counts = new long[3];
+            PtHip.Check(PtHip.pt_read_tri_bvh(ctx, counts, null, null, null, null), "pt_read_tri_bvh");
+            var nodes = new uint[counts[0] * 32];
+            var chunks = new uint[counts[1] * 32];
+            var records = new uint[counts[2] * 32];
+            var box = new float[6];
+            PtHip.Check(PtHip.pt_read_tri_bvh(ctx, counts, nodes, chunks, records, box), "pt_read_tri_bvh");
+            return (nodes, chunks, records, box);
         }
 
         /// <summary>The first-hit features of the whole frame (pt_render_features): one ray through each

@@ -14,6 +14,8 @@
  *                      (+ new Buffer(w,h)                                  Buffer.cs:67-80)
  *   pt_upload_scene    Scene.Compile() → Tree.NewTree / Mesh.Compile        Scene.cs:48-68, Tree.cs:22-29, Mesh.cs:45-57
  *                      (lights registered as in Scene.Add                  Scene.cs:29-38)
+ *   pt_update_triangles (new) new vertex positions for the uploaded scene:  Example.cs:163-223 rebuilds the
+ *   / pt_read_tri_bvh  the triangle BVH refitted on the device, no rebuild  scene for every frame of its loop
  *   pt_render_pass     one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
@@ -133,7 +135,7 @@ typedef struct pt_volume {    /* Volume fields W, H, D, ZScale, Data, Windows, B
 } pt_volume;
 
 typedef struct pt_transformed_shape {  /* TransformedShape(Shape, Matrix, Inverse), TransformedShape.cs:9-24 */
-    int32_t shape_kind;       /* inner IShape: SPHERE, CUBE, PLANE, SDF or VOLUME */
+    int32_t shape_kind;       /* inner IShape: SPHERE, CUBE, PLANE, SDF, VOLUME or MESH (an instanced mesh) */
     int32_t shape_index;      /* index into that kind's arrays */
     double matrix[16];
     double inverse[16];
@@ -525,6 +527,27 @@ int pt_occluded(void* ctx, int64_t n, const float* origins, const float* dirs, c
  * out[0] a 64-bit digest of the BVH bytes a context of this scene receives (node lines, leaf chunks,
  * triangle order), out[1] their size in bytes, out[2] / out[3] the builds made / builds reused so far. */
 int pt_scene_bvh_digest(const pt_scene_desc* scene, uint64_t out[4]);
+
+/* New vertex positions (and optionally normals) for every triangle of the uploaded scene, in
+ * pt_scene_desc order; topology, materials, texture coordinates and every other shape stay.  The
+ * triangle BVH is refitted on the device: afterwards every ray query, feature pass and
+ * render pass sees the scene a fresh pt_upload_scene of the same pt_scene_desc with these arrays would
+ * see, up to the exact-t tie order of DESIGN.md §5.  Runs on the context's stream after every pass issued
+ * before it and synchronises before returning; out_kernel_ms (may be NULL) is the device time of its
+ * kernels.  The Buffer, the pass state and the counters are unchanged.  Lights that are emissive
+ * triangles added directly to the scene follow their triangle.
+ * Errors (nothing launched, the scene untouched): a NULL ctx, v1, v2 or v3, normals partly NULL, or
+ * num_triangles different from the uploaded scene's: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; a scene
+ * with an instanced mesh (a pt_transformed_shape whose shape_kind is PT_SHAPE_MESH): PT_ERR_UNSUPPORTED.
+ * A scene without triangles and num_triangles 0: PT_OK, nothing launched. */
+int pt_update_triangles(void* ctx, int32_t num_triangles,
+                        const float* v1, const float* v2, const float* v3,   /* [n][3], required */
+                        const float* n1, const float* n2, const float* n3,   /* [n][3]; all three or all NULL = keep */
+                        double* out_kernel_ms);
+/* The context's triangle BVH as it stands on the device (tests and tools): counts[0..2] = nodes, leaf
+ * chunks, triangle records; each non-NULL array receives 32 words per node / chunk / record;
+ * out_box[6] = the root box the traversal tests first.  Any argument but ctx may be NULL. */
+int pt_read_tri_bvh(void* ctx, int64_t counts[3], uint32_t* nodes, uint32_t* chunks, uint32_t* records, float out_box[6]);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

@@ -156,6 +156,9 @@ SIGNATURES = {
     "pt_device_count": (C.c_int, [_i]),
     "pt_create": (C.c_int, [C.POINTER(pt_device_opts), C.POINTER(C.c_void_p)]),
     "pt_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(pt_scene_desc)]),
+    "pt_update_triangles": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, _f, _f, _f, _d]),
+    "pt_read_tri_bvh": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint32), _f]),
     "pt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_sampler), C.POINTER(pt_pass_params)]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_reset_buffer": (C.c_int, [C.c_void_p]),

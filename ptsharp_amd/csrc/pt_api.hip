@@ -92,6 +92,11 @@ void* features_part(void* base, int32_t W, int32_t H, int part, size_t* bytes);
 const void* features_guide(void* base, int32_t W, int32_t H);
 hipError_t launch_features(const DevScene& S, const DevCamera& cam, void* base, int32_t W, int32_t H, hipStream_t stream);
 hipError_t launch_features_pack(void* base, int32_t W, int32_t H, hipStream_t stream);
+// pt_refit.hip
+hipError_t launch_refit(int64_t num_chunks, int64_t num_levels, const uint32_t* level_off, const uint32_t* level_nodes,
+                        uint32_t* nodes, uint32_t* chunks, uint32_t* recs, const int32_t* src_of_pos, const float* v1,
+                        const float* v2, const float* v3, const float* n1, const float* n2, const float* n3,
+                        float* node_box, float* chunk_box, hipStream_t stream);
 }
 
 namespace {
@@ -212,6 +217,12 @@ struct Ctx {
     double tri_build_ms = 0;       // last upload: host time to build (or wait for, or find) the triangle BVH
     std::shared_ptr<const pt::TriBvhBuild> tri_build;   // that build, shared with the other contexts of its geometry
                                                     // (released at the next upload and at pt_destroy)
+    // pt_update_triangles: the host tables of the last upload; the device side (one allocation: the six staged
+    // input arrays, src_of_pos, level_nodes, an exact box per node and per chunk) comes with the first update
+    pt::RefitTables refit;
+    std::vector<pt::DevLight> h_lights;   // the uploaded lights (loose emissive triangles' spheres follow an update)
+    bool has_blas = false;                // an instanced mesh: no refit
+    DeviceArray refit_dev;
 };
 
 // Queue capacity bound (entries per queue).  A pass is rendered in chunks of camera
@@ -412,6 +423,10 @@ int upload(Ctx* c, const std::vector<T>& host, const T** out) {
 void free_scene(Ctx* c) {
     for (auto& a : c->scene_arrays) a.release();
     c->scene_arrays.clear();
+    c->refit_dev.release();
+    c->refit = pt::RefitTables{};
+    c->h_lights.clear();
+    c->has_blas = false;
     c->S = pt::DevScene{};
     c->has_scene = false;
 }
@@ -571,6 +586,9 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     PT_HIP(hipStreamSynchronize(c->stream));
     c->S = S;
     c->has_scene = true;
+    c->refit = std::move(H.refit);
+    c->h_lights = std::move(H.lights);
+    c->has_blas = !H.blas.empty();
     c->stats.bvh_nodes = H.bvh_nodes;
     c->stats.traversal_bytes = H.traversal_bytes;
     c->stats.bvh_bytes = H.bvh_bytes;
@@ -1252,6 +1270,118 @@ int pt_occluded(void* ctx, int64_t n, const float* origins, const float* dirs, c
                 int32_t* out_blocked) {
     if (n > 0 && !t_max) return fail(PT_ERR_INVALID_ARG, "t_max is NULL");
     return ray_queries(ctx, n, origins, dirs, t_max, flags, nullptr, out_blocked);
+}
+
+// ---- moving triangles
+namespace {
+// The parts of Ctx::refit_dev, each 256-B aligned: [v1 v2 v3 n1 n2 n3 | src_of_pos | level_nodes | node_box | chunk_box]
+struct RefitDev {
+    float* in[6];
+    int32_t* src_of_pos;
+    uint32_t* level_nodes;
+    float* node_box;
+    float* chunk_box;
+    size_t bytes;
+};
+RefitDev refit_layout(const pt::RefitTables& T, void* base) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    RefitDev r{};
+    size_t at = 0;
+    char* p = (char*)base;
+    const size_t arr = up((size_t)T.num_triangles * 3 * sizeof(float));
+    for (int k = 0; k < 6; k++) { r.in[k] = (float*)(p + at); at += arr; }
+    r.src_of_pos = (int32_t*)(p + at); at += up(T.src_of_pos.size() * sizeof(int32_t));
+    r.level_nodes = (uint32_t*)(p + at); at += up(T.level_nodes.size() * sizeof(uint32_t));
+    r.node_box = (float*)(p + at); at += up((size_t)T.num_nodes * 6 * sizeof(float));
+    r.chunk_box = (float*)(p + at); at += up((size_t)T.num_chunks * 6 * sizeof(float));
+    r.bytes = at;
+    return r;
+}
+}  // namespace
+
+int pt_update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
+                        const float* n2, const float* n3, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!v1 || !v2 || !v3) return fail(PT_ERR_INVALID_ARG, "update: v1, v2 and v3 are required");
+    if ((n1 != nullptr) != (n2 != nullptr) || (n1 != nullptr) != (n3 != nullptr))
+        return fail(PT_ERR_INVALID_ARG, "update: n1/n2/n3 must be all set or all NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::RefitTables& T = c->refit;
+    if (num_triangles != T.num_triangles)
+        return fail(PT_ERR_INVALID_ARG, "update: num_triangles is " + std::to_string(num_triangles) + ", the uploaded scene has " +
+                                            std::to_string(T.num_triangles));
+    if (c->has_blas)
+        return fail(PT_ERR_UNSUPPORTED, "update: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
+                                        "its BLAS is not refitted");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (T.num_chunks == 0) return PT_OK;   // no triangle in the BVH (num_triangles == 0, or none of them in Scene.Shapes)
+    PT_HIP(hipSetDevice(c->device));
+    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
+    RefitDev D = refit_layout(T, nullptr);
+    const bool first = !c->refit_dev.ptr;
+    if (first) {
+        if (hipMalloc(&c->refit_dev.ptr, D.bytes) != hipSuccess) {
+            c->refit_dev.ptr = nullptr;
+            (void)hipGetLastError();
+            return fail(PT_ERR_OUT_OF_MEMORY, "refit workspace allocation");
+        }
+        c->refit_dev.bytes = D.bytes;
+    }
+    D = refit_layout(T, c->refit_dev.ptr);
+    if (first) {
+        PT_HIP(hipMemcpyAsync(D.src_of_pos, T.src_of_pos.data(), T.src_of_pos.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        PT_HIP(hipMemcpyAsync(D.level_nodes, T.level_nodes.data(), T.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
+    const float* src[6] = {v1, v2, v3, n1, n2, n3};
+    for (int k = 0; k < (n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
+    uint32_t* nodes = (uint32_t*)const_cast<float4*>(c->S.tri_nodes);
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_refit(T.num_chunks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes, nodes,
+                            (uint32_t*)const_cast<float4*>(c->S.tri_chunks), (uint32_t*)const_cast<float4*>(c->S.tri_recs),
+                            D.src_of_pos, D.in[0], D.in[1], D.in[2], n1 ? D.in[3] : nullptr, n1 ? D.in[4] : nullptr,
+                            n1 ? D.in[5] : nullptr, D.node_box, D.chunk_box, c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    // the root box follows (pt_wavefront.hip's refill kernels skip the triangle phase of a ray that misses it)
+    uint32_t root[pt::kNode8Words];
+    PT_HIP(hipMemcpyAsync(root, nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
+    // lights that are loose emissive triangles: their sphere from the new vertices
+    bool lights_moved = false;
+    for (size_t i = 0; i < c->h_lights.size() && i < T.light_tri.size(); i++) {
+        const int64_t j = T.light_tri[i];
+        if (j < 0) continue;
+        pt::tri_light_sphere(v1 + 3 * j, v2 + 3 * j, v3 + 3 * j, c->h_lights[i]);
+        lights_moved = true;
+    }
+    if (lights_moved)
+        PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
+                              hipMemcpyHostToDevice, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    pt::tri_root_box(root, c->S.tri_box);
+    if (out_kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *out_kernel_ms = ms;
+    }
+    return PT_OK;
+}
+
+int pt_read_tri_bvh(void* ctx, int64_t counts[3], uint32_t* nodes, uint32_t* chunks, uint32_t* records, float out_box[6]) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::RefitTables& T = c->refit;
+    if (counts) { counts[0] = T.num_nodes; counts[1] = T.num_chunks; counts[2] = (int64_t)T.src_of_pos.size(); }
+    if (out_box) std::memcpy(out_box, c->S.tri_box, sizeof c->S.tri_box);
+    PT_HIP(hipSetDevice(c->device));
+    const size_t line = pt::kNode8Words * sizeof(uint32_t);
+    if (nodes && T.num_nodes) PT_HIP(hipMemcpyAsync(nodes, c->S.tri_nodes, (size_t)T.num_nodes * line, hipMemcpyDeviceToHost, c->stream));
+    if (chunks && T.num_chunks) PT_HIP(hipMemcpyAsync(chunks, c->S.tri_chunks, (size_t)T.num_chunks * line, hipMemcpyDeviceToHost, c->stream));
+    if (records && !T.src_of_pos.empty())
+        PT_HIP(hipMemcpyAsync(records, c->S.tri_recs, T.src_of_pos.size() * line, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
 }
 
 int pt_scene_bvh_digest(const pt_scene_desc* d, uint64_t out[4]) {

@@ -1,5 +1,6 @@
 // pt_bvh.cpp — parallel binned-SAH BVH2 builder (host, C++17 threads).
 #include "pt_bvh.h"
+#include "pt_refit.h"
 
 #include <algorithm>
 #include <atomic>
@@ -425,13 +426,7 @@ namespace {
 
 // ---- 8-wide quantized collapse (pt_bvh.h collapse_bvh8q)
 constexpr int kW8 = 8;
-constexpr uint32_t kQMax = 2047;   // child bounds as binary16 integers: 0..2047 are exact
-
-uint16_t half_of_int(uint32_t q) {   // an integer 0..2047 as binary16 bits (exact)
-    if (q == 0) return 0;
-    int e = 31 - __builtin_clz(q);   // 2^e <= q < 2^(e+1), e <= 10
-    return (uint16_t)(((uint32_t)(e + 15) << 10) | ((q - (1u << e)) << (10 - e)));
-}
+static_assert(kRefitQMax == 2047, "child bounds as binary16 integers: 0..2047 are exact (pt_refit.h refit_half_of_int)");
 uint32_t int_of_half(uint16_t h) {   // the inverse, for the integers half_of_int makes
     if (h == 0) return 0;
     const int e = (int)(h >> 10) - 15;
@@ -586,43 +581,21 @@ struct Wide8 {
             cnt_bits |= (np - 1u) << (2 * k);
         }
         uint32_t* w = &out.words[(size_t)at * kNode8Words];
-        // quantization, per axis: origin = the children's lowest bound, step 2^e the least power of two with
-        // every bound within kQMax steps; q rounded outward (exact arithmetic in double)
-        uint32_t ebits = 0;
-        uint16_t qb[6][kW8];
-        for (int ax = 0; ax < 3; ax++) {
-            float o = INFINITY, top = -INFINITY;
-            for (uint32_t c : C) { o = std::min(o, n2[c].bmin[ax]); top = std::max(top, n2[c].bmax[ax]); }
-            const double ext = (double)top - (double)o;
-            int e = -126;
-            while (e < 127 && std::ldexp((double)kQMax, e) < ext) e++;
-            for (;;) {   // the outward rounding can need one more step
-                bool ok = true;
-                for (int k = 0; k < nc && ok; k++) {
-                    const double hi = std::ceil(((double)n2[C[(size_t)k]].bmax[ax] - (double)o) / std::ldexp(1.0, e));
-                    ok = hi <= (double)kQMax;
-                }
-                if (ok || e >= 127) break;
-                e++;
-            }
-            std::memcpy(&w[ax], &o, 4);
-            ebits |= (uint32_t)(e + 127) << (8 * ax);
-            for (int k = 0; k < kW8; k++) {
-                if (k >= nc) { qb[2 * ax][k] = 0x7C00; qb[2 * ax + 1][k] = 0xFC00; continue; }   // +inf / -inf
-                const double step = std::ldexp(1.0, e);
-                const double lo = std::floor(((double)n2[C[(size_t)k]].bmin[ax] - (double)o) / step);
-                const double hi = std::ceil(((double)n2[C[(size_t)k]].bmax[ax] - (double)o) / step);
-                qb[2 * ax][k] = half_of_int((uint32_t)std::max(0.0, lo));
-                qb[2 * ax + 1][k] = half_of_int((uint32_t)std::min((double)kQMax, std::max(0.0, hi)));
-            }
-        }
+        // quantization (pt_refit.h refit_quantize, the one quantizer: pt_update_triangles refits with it), per axis:
+        // origin = the children's lowest bound, step 2^e the least power of two with every bound within kQMax
+        // steps; q rounded outward (exact arithmetic in double)
+        float clo[kW8][3], chi[kW8][3], own[6];
+        for (int k = 0; k < nc; k++)
+            for (int ax = 0; ax < 3; ax++) { clo[k][ax] = n2[C[(size_t)k]].bmin[ax]; chi[k][ax] = n2[C[(size_t)k]].bmax[ax]; }
+        uint32_t w03[4];
+        refit_quantize(nc, clo, chi, 0u, w03, w + 8, own);
+        for (int ax = 0; ax < 3; ax++) w[ax] = w03[ax];
+        const uint32_t ebits = w03[3];
         w[3] = ebits | ((uint32_t)nin << 24) | ((uint32_t)nc << 28);
         w[4] = base_in;
         w[5] = 0x80000000u + base_chunk - (uint32_t)nin;   // leaf slot k's ref (0x80000000 | chunk) is w[5] + k
         w[6] = cnt_bits;
         w[7] = 0;
-        for (int r = 0; r < 6; r++)
-            for (int k = 0; k < kW8; k += 2) w[8 + 4 * r + k / 2] = (uint32_t)qb[r][k] | ((uint32_t)qb[r][k + 1] << 16);
         for (int k = 0; k < nin; k++) emit(base_in + (uint32_t)k, C[(size_t)k], pushed, depth + 1);
     }
 };
@@ -658,20 +631,12 @@ void collapse_bvh8q(const BvhResult& bvh2, int stack_budget, Bvh8Result& out, do
     const uint32_t root = c.alloc(1);
     if (c.is_leaf(0)) {   // a lone leaf: the root node holds it in slot 0
         uint32_t* w = &out.words[0];
-        for (int ax = 0; ax < 3; ax++) std::memcpy(&w[ax], &bvh2.nodes[0].bmin[ax], 4);
-        uint32_t ebits = 0;
-        for (int ax = 0; ax < 3; ax++) {
-            const double ext = (double)bvh2.nodes[0].bmax[ax] - (double)bvh2.nodes[0].bmin[ax];
-            int e = -126;
-            while (e < 127 && std::ldexp((double)kQMax, e) < ext) e++;
-            ebits |= (uint32_t)(e + 127) << (8 * ax);
-            const double hi = std::ceil(ext / std::ldexp(1.0, e));
-            for (int k = 0; k < kW8; k += 2) {
-                const uint32_t lo0 = 0, hi0 = half_of_int((uint32_t)std::min((double)kQMax, hi));
-                w[8 + 8 * ax + k / 2] = k == 0 ? (lo0 | (0x7C00u << 16)) : (0x7C00u | (0x7C00u << 16));
-                w[12 + 8 * ax + k / 2] = k == 0 ? (hi0 | (0xFC00u << 16)) : (0xFC00u | (0xFC00u << 16));
-            }
-        }
+        float clo[kW8][3], chi[kW8][3], own[6];
+        for (int ax = 0; ax < 3; ax++) { clo[0][ax] = bvh2.nodes[0].bmin[ax]; chi[0][ax] = bvh2.nodes[0].bmax[ax]; }
+        uint32_t w03[4];
+        refit_quantize(1, clo, chi, 0u, w03, w + 8, own);
+        for (int ax = 0; ax < 3; ax++) w[ax] = w03[ax];
+        const uint32_t ebits = w03[3];
         w[3] = ebits | (0u << 24) | (1u << 28);
         w[4] = 0;
         w[5] = 0x80000000u;   // the ref of chunk 0 - n_in (0)

@@ -106,7 +106,7 @@ int pack_nodes(const BvhResult& b, std::vector<float4>& out, int32_t& num_nodes,
     else collapse_bvh4(b, kStack4Budget, r);
     if (r.stack_need > kStack4Budget) return fail(err, PT_ERR_UNSUPPORTED, "BVH4 traversal stack bound exceeded");
     out.resize(r.words.size() / 4);
-    std::memcpy(out.data(), r.words.data(), r.words.size() * sizeof(uint32_t));
+    if (!r.words.empty()) std::memcpy(out.data(), r.words.data(), r.words.size() * sizeof(uint32_t));
     num_nodes = (int32_t)r.nodes();
     return PT_OK;
 }
@@ -162,8 +162,8 @@ TriBvhKey tri_bvh_key(const pt_scene_desc* d, const std::vector<int32_t>& tri_sr
     return k;
 }
 // Root box = union of the root node's children (their quantized boxes)
-void bvh8_root_box(const Bvh8Result& b8, float* box) {
-    const uint32_t* w = b8.words.data();
+void bvh8_root_box(const Bvh8Result& b8, float* box) { tri_root_box(b8.words.data(), box); }
+void root_box_of(const uint32_t* w, float* box) {
     for (int ax = 0; ax < 3; ax++) { box[ax] = INFINITY; box[3 + ax] = -INFINITY; }
     for (int k = 0; k < (int)(w[3] >> 28); k++) {
         float lo[3], hi[3];
@@ -194,7 +194,7 @@ std::shared_ptr<const TriBvhBuild> build_tri_bvh(const pt_scene_desc* d, const s
         return out;
     }
     out->nodes.resize(b8.words.size() / 4);
-    std::memcpy(out->nodes.data(), b8.words.data(), b8.words.size() * sizeof(uint32_t));
+    if (!b8.words.empty()) std::memcpy(out->nodes.data(), b8.words.data(), b8.words.size() * sizeof(uint32_t));
     out->num_nodes = (int32_t)b8.nodes();
     out->chunks.resize(8 * b8.chunk_first.size());
     for (size_t ci = 0; ci < b8.chunk_first.size(); ci++) {
@@ -644,6 +644,13 @@ int Compiler::triangles() {
     H.S.tri_ustride = 8;
     H.S.tri_num_nodes = tbv->num_nodes;
     std::memcpy(H.S.tri_box, tbv->box, sizeof H.S.tri_box);
+    // what a later pt_update_triangles needs (RefitTables)
+    H.refit.num_triangles = d->num_triangles;
+    H.refit.src_of_pos.resize(nt);
+    for (size_t i = 0; i < nt; i++) H.refit.src_of_pos[i] = tri_src[tbv->order[i]];
+    H.refit.num_nodes = tbv->num_nodes;
+    H.refit.num_chunks = (int64_t)(tbv->chunks.size() / 8);
+    refit_levels((const uint32_t*)tbv->nodes.data(), tbv->num_nodes, H.refit.level_nodes, H.refit.level_off);
     return PT_OK;
 }
 
@@ -734,8 +741,7 @@ void Compiler::lights() {
             light_sphere_of_box(mk(-1e9, -1e9, -1e9), mk(1e9, 1e9, 1e9), L);  // Plane.BoundingBox
         } else if (k == PT_SHAPE_TRIANGLE) {  // a directly-added struct Triangle: never passes the identity test
             L.index = -1; L.phantom = 1;
-            v3 a = ld3(d->tri_v1 + 3 * j), b = ld3(d->tri_v2 + 3 * j), cc = ld3(d->tri_v3 + 3 * j);
-            light_sphere_of_box(vmin(vmin(a, b), cc), vmax(vmax(a, b), cc), L);
+            tri_light_sphere(d->tri_v1 + 3 * j, d->tri_v2 + 3 * j, d->tri_v3 + 3 * j, L);
         } else {   // Cube, SDFShape, Volume: class shapes; TransformedShape: a struct, never identical
             const int32_t kind = k == PT_SHAPE_CUBE ? KIND_CUBE : k == PT_SHAPE_SDF ? KIND_SDF
                                : k == PT_SHAPE_VOLUME ? KIND_VOLUME : KIND_XFORM;
@@ -746,6 +752,7 @@ void Compiler::lights() {
             light_sphere_of_box(b.mn, b.mx, L);
         }
         H.lights.push_back(L);
+        H.refit.light_tri.push_back(k == PT_SHAPE_TRIANGLE ? j : -1);
     }
     H.S.num_lights = (int32_t)H.lights.size();
 }
@@ -835,6 +842,37 @@ int validate_shape_list(const pt_scene_desc* d, std::string& err) {
 }
 
 }  // namespace
+
+void tri_root_box(const uint32_t* root, float box[6]) { root_box_of(root, box); }
+
+void tri_light_sphere(const float* p1, const float* p2, const float* p3, DevLight& L) {
+    v3 a = ld3(p1), b = ld3(p2), cc = ld3(p3);
+    light_sphere_of_box(vmin(vmin(a, b), cc), vmax(vmax(a, b), cc), L);
+}
+
+void refit_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {
+    level_nodes.clear();
+    level_off.assign(1, 0u);
+    if (num_nodes <= 0) return;
+    std::vector<uint32_t> depth((size_t)num_nodes, 0u);
+    uint32_t deepest = 0;
+    for (int64_t i = 0; i < num_nodes; i++) {
+        const uint32_t* w = nodes + i * kNode8Words;
+        const uint32_t nin = (w[3] >> 24) & 15u;
+        for (uint32_t k = 0; k < nin; k++) {
+            const int64_t c = (int64_t)w[4] + k;
+            if (c <= i || c >= num_nodes) continue;   // not a tree of this builder: left at depth 0
+            depth[(size_t)c] = depth[(size_t)i] + 1;
+            deepest = std::max(deepest, depth[(size_t)c]);
+        }
+    }
+    level_off.assign((size_t)deepest + 2, 0u);
+    for (int64_t i = 0; i < num_nodes; i++) level_off[depth[(size_t)i] + 1]++;
+    for (size_t l = 1; l < level_off.size(); l++) level_off[l] += level_off[l - 1];
+    level_nodes.resize((size_t)num_nodes);
+    std::vector<uint32_t> at(level_off.begin(), level_off.end() - 1);
+    for (int64_t i = 0; i < num_nodes; i++) level_nodes[at[depth[(size_t)i]]++] = (uint32_t)i;
+}
 
 std::vector<int32_t> gather_tri_src(const pt_scene_desc* d) {
     std::vector<int32_t> tri_src;

@@ -42,6 +42,23 @@ struct HostVolume {
     int64_t cells_off;                   // into vol_cells; -1: the march reads the grid
 };
 
+// What pt_update_triangles needs beside the device arrays: small host tables kept from the upload.
+struct RefitTables {
+    int32_t num_triangles = 0;          // pt_scene_desc::num_triangles: the length of the arrays an update takes
+    std::vector<int32_t> src_of_pos;    // source triangle of BVH position i: tri_src[order[i]]
+    std::vector<uint32_t> level_nodes;  // the triangle BVH's node indices grouped by depth, the root's level first
+    std::vector<uint32_t> level_off;    // level l is level_nodes[level_off[l] .. level_off[l + 1])
+    std::vector<int32_t> light_tri;     // per HostScene::lights entry: its source triangle, or -1 (not a loose triangle)
+    int64_t num_nodes = 0, num_chunks = 0;
+};
+// The nodes of an 8-wide BVH (kNode8Words words each) grouped by depth.  A child's index is greater than its
+// parent's (pt_bvh.cpp Wide8::emit allocates children after their parent), so one forward sweep gives the depths.
+void refit_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off);
+// The box of the triangle BVH from its root node's 32 words, as the compile computes DevScene::tri_box.
+void tri_root_box(const uint32_t* root, float box[6]);
+// Centre and radius of a loose emissive triangle's light, as the compile's light stage computes them.
+void tri_light_sphere(const float* p1, const float* p2, const float* p3, DevLight& L);
+
 // A compiled scene on the host: every array pt_upload_scene uploads, and the DevScene with every
 // non-pointer field filled.
 struct HostScene {
@@ -69,6 +86,7 @@ struct HostScene {
     uint64_t bvh_nodes = 0, traversal_bytes = 0, bvh_bytes = 0;   // pt_stats
     std::shared_ptr<const TriBvhBuild> tri_build;   // the shared triangle build `lines` was filled from
     double tri_build_ms = 0;                        // host time to build (or wait for, or find) it
+    RefitTables refit;
 };
 
 // Validates and compiles.  PT_OK, or an error code with its message in err (H is then partly filled; its

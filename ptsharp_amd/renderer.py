@@ -397,6 +397,42 @@ class Renderer:
                                          int(flags), b.ctypes.data_as(C.POINTER(C.c_int32))), "pt_occluded")
         return b
 
+    def UpdateTriangles(self, v1, v2, v3, n1=None, n2=None, n3=None) -> float:
+        """New vertex positions (and optionally normals) for every triangle of the scene, [n, 3] float32 in
+        the order of the compiled scene's tri_v1 (pt_update_triangles): the triangle BVH is refitted on the
+        device, nothing is rebuilt or re-uploaded.  The arrays are then written into the uploaded FlatScene
+        in place, so it describes what the device holds.  Returns the device time of the kernels in ms."""
+        self._ensure_scene()
+        flat = self._uploaded
+        n = len(flat.tri_material)
+        if (n1 is None) != (n2 is None) or (n1 is None) != (n3 is None):
+            raise ValueError("n1, n2 and n3 must be all given or all None")
+        arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (v1, v2, v3)]
+        if n1 is not None:
+            arrs += [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (n1, n2, n3)]
+        if any(len(a) != n for a in arrs):
+            raise ValueError(f"the scene has {n} triangles")
+        fp = C.POINTER(C.c_float)
+        ptrs = [a.ctypes.data_as(fp) for a in arrs] + [fp()] * (6 - len(arrs))
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_update_triangles(self._ctx, n, *ptrs, C.byref(ms)), "pt_update_triangles")
+        for dst, a in zip((flat.tri_v1, flat.tri_v2, flat.tri_v3, flat.tri_n1, flat.tri_n2, flat.tri_n3), arrs):
+            dst[...] = a
+        return float(ms.value)
+
+    def ReadTriBvh(self):
+        """The context's triangle BVH as it stands on the device (pt_read_tri_bvh): (nodes [N, 32],
+        chunks [C, 32], records [T, 32], all uint32, and the root box [6] float32)."""
+        self._ensure_scene()
+        counts = (C.c_int64 * 3)()
+        _abi.check(self._lib.pt_read_tri_bvh(self._ctx, counts, None, None, None, None), "pt_read_tri_bvh")
+        out = [np.zeros((int(c), 32), np.uint32) for c in counts]
+        box = np.zeros(6, np.float32)
+        up = C.POINTER(C.c_uint32)
+        _abi.check(self._lib.pt_read_tri_bvh(self._ctx, counts, *[a.ctypes.data_as(up) for a in out],
+                                             box.ctypes.data_as(C.POINTER(C.c_float))), "pt_read_tri_bvh")
+        return out[0], out[1], out[2], box
+
     def ResetBuffer(self) -> None:
         _abi.check(self._lib.pt_reset_buffer(self._ctx), "pt_reset_buffer")
         self._pass = 0
