@@ -208,6 +208,9 @@ namespace PTSharpCore
         // Scene.Intersect of a batch of rays / the shadow query against a t (PT_MARCH_* flags: the Volume march form)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_triangles(IntPtr ctx, int numTriangles, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tri_bvh(IntPtr ctx, long[] counts, uint[] nodes, uint[] chunks, uint[] records, float[] box);
+        public const int PT_NORMALS_FACE = 1, PT_NORMALS_SMOOTH = 2;   // pt_normals_mode
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_triangles_normals(IntPtr ctx, int numTriangles, float[] v1, float[] v2, float[] v3, int mode, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tri_normals(IntPtr ctx, float[] n1, float[] n2, float[] n3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr pt_last_error();
@@ -609,6 +612,29 @@ namespace PTSharpCore
             if (!uploaded) Upload();
             PtHip.Check(PtHip.pt_update_triangles(ctx, v1.Length / 3, v1, v2, v3, n1, n2, n3, out double ms), "pt_update_triangles");
             return ms;
+        }
+
+        /// <summary>UpdateTriangles with the normals derived on the device from the new positions
+        /// (pt_update_triangles_normals): mode PtHip.PT_NORMALS_FACE, every corner the triangle's face normal, or
+        /// PtHip.PT_NORMALS_SMOOTH, Mesh.SmoothNormals on each mesh of the scene.  Returns the device time of
+        /// the kernels in ms; ReadTriNormals returns what was computed.</summary>
+        public double UpdateTrianglesNormals(float[] v1, float[] v2, float[] v3, int mode)
+        {
+            if (!uploaded) Upload();
+            PtHip.Check(PtHip.pt_update_triangles_normals(ctx, v1.Length / 3, v1, v2, v3, mode, out double ms), "pt_update_triangles_normals");
+            return ms;
+        }
+
+        /// <summary>The normals the uploaded scene holds on the device now (pt_read_tri_normals): [n * 3] floats
+        /// each, in the upload's triangle order.</summary>
+        public (float[] n1, float[] n2, float[] n3) ReadTriNormals(int numTriangles)
+        {
+            if (!uploaded) Upload();
+            var n1 = new float[numTriangles * 3];
+            var n2 = new float[numTriangles * 3];
+            var n3 = new float[numTriangles * 3];
+            PtHip.Check(PtHip.pt_read_tri_normals(ctx, n1, n2, n3), "pt_read_tri_normals");
+            return (n1, n2, n3);
         }
 
         /// <summary>The context's triangle BVH as it stands on the device (pt_read_tri_bvh): 32 words per node,

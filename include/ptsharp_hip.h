@@ -16,6 +16,8 @@
  *                      (lights registered as in Scene.Add                  Scene.cs:29-38)
  *   pt_update_triangles (new) new vertex positions for the uploaded scene:  Example.cs:163-223 rebuilds the
  *   / pt_read_tri_bvh  the triangle BVH refitted on the device, no rebuild  scene for every frame of its loop
+ *   pt_update_triangles_normals  the same with the normals derived on the   Triangle.FixNormals, Mesh.SmoothNormals
+ *   / pt_read_tri_normals        device: face or smooth                     Triangle.cs:224-237, Mesh.cs:191-229
  *   pt_render_pass     one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
@@ -548,6 +550,34 @@ int pt_update_triangles(void* ctx, int32_t num_triangles,
  * chunks, triangle records; each non-NULL array receives 32 words per node / chunk / record;
  * out_box[6] = the root box the traversal tests first.  Any argument but ctx may be NULL. */
 int pt_read_tri_bvh(void* ctx, int64_t counts[3], uint32_t* nodes, uint32_t* chunks, uint32_t* records, float out_box[6]);
+
+/* pt_update_triangles with the normals derived on the device from the new positions: everything
+ * pt_update_triangles does with v1..v3 and given normals happens here, the normals being computed, not given.
+ *   PT_NORMALS_FACE    every corner of a triangle takes Triangle.Normal(), normalize(cross(V2 - V1, V3 - V1)) in
+ *                      fp32, each operation rounded on its own (Triangle.FixNormals on zeroed normals).
+ *   PT_NORMALS_SMOOTH  the face normals, then Mesh.SmoothNormals (Mesh.cs:191-229) on each mesh (a
+ *                      mesh_first / mesh_count range of the uploaded pt_scene_desc) by itself: per distinct vertex
+ *                      position of the mesh the fp32 sum of its corners' normals from (+0, +0, +0) in ascending
+ *                      (triangle, corner 1-2-3) order, normalised; every corner at that position takes it.
+ *                      Positions compare as Vector == (-0 and +0 are one position).  Meshes that share positions
+ *                      do not share sums; a triangle outside every mesh keeps its face normal; a triangle inside
+ *                      several ranges belongs to the last of them.  The result is pt_mesh_smooth_normals' on the
+ *                      face normals, bit for bit (a NaN where that gives a NaN: a zero-area triangle poisons its
+ *                      vertices; payloads may differ), and does not depend on the run.
+ * Non-finite positions (the reference throws): the normals of corners at such a position, and of triangles that
+ * have one, are unspecified; every other normal is as above, and no access leaves its array.
+ * out_kernel_ms (may be NULL) covers every kernel of the call: the normals, the sort, the refit.
+ * Errors (nothing launched, the scene untouched): those of pt_update_triangles, a mode outside pt_normals_mode:
+ * PT_ERR_INVALID_ARG; PT_NORMALS_SMOOTH's workspace (about 60 B per triangle, kept until the next upload) not
+ * allocated: PT_ERR_OUT_OF_MEMORY; PT_NORMALS_SMOOTH with 3 * num_triangles >= 2^31: PT_ERR_UNSUPPORTED. */
+typedef enum pt_normals_mode { PT_NORMALS_FACE = 1, PT_NORMALS_SMOOTH = 2 } pt_normals_mode;
+int pt_update_triangles_normals(void* ctx, int32_t num_triangles,
+                                const float* v1, const float* v2, const float* v3,   /* [n][3], required */
+                                int32_t mode, double* out_kernel_ms);
+/* The normals the uploaded scene holds on the device now, [n][3] each in pt_scene_desc order (a triangle that is
+ * in no shape of the scene has none: zeros).  Valid any time after an upload; synchronises and changes nothing.
+ * A NULL ctx or output: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

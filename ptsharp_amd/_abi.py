@@ -35,6 +35,7 @@ FEATURE_ALBEDO_F64, FEATURE_NORMAL_F32, FEATURE_DEPTH_F64, FEATURE_KIND_I32, FEA
 SHAPE_SPHERE, SHAPE_CUBE, SHAPE_PLANE, SHAPE_TRIANGLE, SHAPE_MESH = 0, 1, 2, 3, 4
 SHAPE_SDF, SHAPE_VOLUME, SHAPE_TRANSFORMED = 5, 6, 7
 MARCH_LANE, MARCH_WAVE = 1, 2   # pt_intersect / pt_occluded flags (PT_MARCH_*)
+NORMALS_FACE, NORMALS_SMOOTH = 1, 2   # pt_normals_mode (pt_update_triangles_normals)
 
 _f = C.POINTER(C.c_float)
 _d = C.POINTER(C.c_double)
@@ -157,6 +158,8 @@ SIGNATURES = {
     "pt_create": (C.c_int, [C.POINTER(pt_device_opts), C.POINTER(C.c_void_p)]),
     "pt_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(pt_scene_desc)]),
     "pt_update_triangles": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, _f, _f, _f, _d]),
+    "pt_update_triangles_normals": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, C.c_int32, _d]),
+    "pt_read_tri_normals": (C.c_int, [C.c_void_p, _f, _f, _f]),
     "pt_read_tri_bvh": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32), _f]),
     "pt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_sampler), C.POINTER(pt_pass_params)]),

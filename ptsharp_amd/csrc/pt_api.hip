@@ -97,6 +97,13 @@ hipError_t launch_refit(int64_t num_chunks, int64_t num_levels, const uint32_t* 
                         uint32_t* nodes, uint32_t* chunks, uint32_t* recs, const int32_t* src_of_pos, const float* v1,
                         const float* v2, const float* v3, const float* n1, const float* n2, const float* n3,
                         float* node_box, float* chunk_box, hipStream_t stream);
+// pt_normals.hip
+hipError_t normals_sort_temp_bytes(int64_t corners, int32_t num_groups, size_t* out);
+hipError_t launch_normals(bool smooth, int64_t n, const float* v1, const float* v2, const float* v3, float* n1, float* n2,
+                          float* n3, const int32_t* group, int32_t num_groups, uint32_t* keys_a, uint32_t* keys_b,
+                          uint32_t* vals_a, uint32_t* vals_b, void* temp, size_t temp_bytes, hipStream_t stream);
+hipError_t launch_normals_gather(int64_t num_pos, const uint32_t* recs, const int32_t* src_of_pos, float* n1, float* n2,
+                                 float* n3, hipStream_t stream);
 }
 
 namespace {
@@ -223,6 +230,10 @@ struct Ctx {
     std::vector<pt::DevLight> h_lights;   // the uploaded lights (loose emissive triangles' spheres follow an update)
     bool has_blas = false;                // an instanced mesh: no refit
     DeviceArray refit_dev;
+    // pt_update_triangles_normals, PT_NORMALS_SMOOTH: the triangles' groups, two key and two corner arrays and the
+    // sort's temporary, one allocation that comes with the first such call and goes with the scene
+    DeviceArray normals_dev;
+    size_t normals_temp_bytes = 0;
 };
 
 // Queue capacity bound (entries per queue).  A pass is rendered in chunks of camera
@@ -424,6 +435,8 @@ void free_scene(Ctx* c) {
     for (auto& a : c->scene_arrays) a.release();
     c->scene_arrays.clear();
     c->refit_dev.release();
+    c->normals_dev.release();
+    c->normals_temp_bytes = 0;
     c->refit = pt::RefitTables{};
     c->h_lights.clear();
     c->has_blas = false;
@@ -1297,28 +1310,10 @@ RefitDev refit_layout(const pt::RefitTables& T, void* base) {
     r.bytes = at;
     return r;
 }
-}  // namespace
-
-int pt_update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
-                        const float* n2, const float* n3, double* out_kernel_ms) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
-    if (!v1 || !v2 || !v3) return fail(PT_ERR_INVALID_ARG, "update: v1, v2 and v3 are required");
-    if ((n1 != nullptr) != (n2 != nullptr) || (n1 != nullptr) != (n3 != nullptr))
-        return fail(PT_ERR_INVALID_ARG, "update: n1/n2/n3 must be all set or all NULL");
-    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+// Ctx::refit_dev, allocated and its tables uploaded (on the context's stream) at the first use after an upload
+int ensure_refit_dev(Ctx* c, RefitDev& D) {
     const pt::RefitTables& T = c->refit;
-    if (num_triangles != T.num_triangles)
-        return fail(PT_ERR_INVALID_ARG, "update: num_triangles is " + std::to_string(num_triangles) + ", the uploaded scene has " +
-                                            std::to_string(T.num_triangles));
-    if (c->has_blas)
-        return fail(PT_ERR_UNSUPPORTED, "update: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
-                                        "its BLAS is not refitted");
-    if (out_kernel_ms) *out_kernel_ms = 0.0;
-    if (T.num_chunks == 0) return PT_OK;   // no triangle in the BVH (num_triangles == 0, or none of them in Scene.Shapes)
-    PT_HIP(hipSetDevice(c->device));
-    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
-    RefitDev D = refit_layout(T, nullptr);
+    D = refit_layout(T, nullptr);
     const bool first = !c->refit_dev.ptr;
     if (first) {
         if (hipMalloc(&c->refit_dev.ptr, D.bytes) != hipSuccess) {
@@ -1333,15 +1328,92 @@ int pt_update_triangles(void* ctx, int32_t num_triangles, const float* v1, const
         PT_HIP(hipMemcpyAsync(D.src_of_pos, T.src_of_pos.data(), T.src_of_pos.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         PT_HIP(hipMemcpyAsync(D.level_nodes, T.level_nodes.data(), T.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     }
+    return PT_OK;
+}
+
+// The parts of Ctx::normals_dev (PT_NORMALS_SMOOTH), each 256-B aligned: [group | keys a b | corners a b | the sort's temporary]
+struct NormalsDev {
+    int32_t* group;
+    uint32_t* keys[2];
+    uint32_t* vals[2];
+    void* temp;
+    size_t temp_bytes, bytes;
+};
+NormalsDev normals_layout(const pt::RefitTables& T, size_t temp_bytes, void* base) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    NormalsDev r{};
+    size_t at = 0;
+    char* p = (char*)base;
+    r.group = (int32_t*)(p + at); at += up((size_t)T.num_triangles * sizeof(int32_t));
+    const size_t arr = up((size_t)T.num_triangles * 3 * sizeof(uint32_t));
+    for (int k = 0; k < 2; k++) { r.keys[k] = (uint32_t*)(p + at); at += arr; }
+    for (int k = 0; k < 2; k++) { r.vals[k] = (uint32_t*)(p + at); at += arr; }
+    r.temp = p + at; at += up(temp_bytes);
+    r.temp_bytes = temp_bytes;
+    r.bytes = at;
+    return r;
+}
+
+// pt_update_triangles (mode 0: the normals given, or kept) and pt_update_triangles_normals (mode: a pt_normals_mode)
+int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
+                     const float* n2, const float* n3, bool derive, int32_t mode, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!v1 || !v2 || !v3) return fail(PT_ERR_INVALID_ARG, "update: v1, v2 and v3 are required");
+    if ((n1 != nullptr) != (n2 != nullptr) || (n1 != nullptr) != (n3 != nullptr))
+        return fail(PT_ERR_INVALID_ARG, "update: n1/n2/n3 must be all set or all NULL");
+    if (derive && mode != PT_NORMALS_FACE && mode != PT_NORMALS_SMOOTH)
+        return fail(PT_ERR_INVALID_ARG, "update: mode " + std::to_string(mode) + " is not a pt_normals_mode");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::RefitTables& T = c->refit;
+    if (num_triangles != T.num_triangles)
+        return fail(PT_ERR_INVALID_ARG, "update: num_triangles is " + std::to_string(num_triangles) + ", the uploaded scene has " +
+                                            std::to_string(T.num_triangles));
+    if (c->has_blas)
+        return fail(PT_ERR_UNSUPPORTED, "update: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
+                                        "its BLAS is not refitted");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (T.num_chunks == 0) return PT_OK;   // no triangle in the BVH (num_triangles == 0, or none of them in Scene.Shapes)
+    PT_HIP(hipSetDevice(c->device));
+    const bool smooth = derive && mode == PT_NORMALS_SMOOTH;
+    if (smooth && (int64_t)num_triangles * 3 > (int64_t)INT32_MAX)
+        return fail(PT_ERR_UNSUPPORTED, "update: PT_NORMALS_SMOOTH numbers corners in 31 bits");
+    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
+    // both workspaces before the first copy: a failed allocation leaves the scene untouched
+    NormalsDev N{};
+    if (smooth) {
+        const bool first = !c->normals_dev.ptr;
+        if (first) {
+            size_t temp = 0;
+            PT_HIP(pt::normals_sort_temp_bytes((int64_t)num_triangles * 3, T.num_groups, &temp));
+            N = normals_layout(T, temp, nullptr);
+            if (hipMalloc(&c->normals_dev.ptr, N.bytes) != hipSuccess) {
+                c->normals_dev.ptr = nullptr;
+                (void)hipGetLastError();
+                return fail(PT_ERR_OUT_OF_MEMORY, "normals workspace allocation");
+            }
+            c->normals_dev.bytes = N.bytes;
+            c->normals_temp_bytes = temp;
+        }
+        N = normals_layout(T, c->normals_temp_bytes, c->normals_dev.ptr);
+        if (first)
+            PT_HIP(hipMemcpyAsync(N.group, T.tri_group.data(), T.tri_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    RefitDev D{};
+    if (const int rc = ensure_refit_dev(c, D)) return rc;
     const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
     const float* src[6] = {v1, v2, v3, n1, n2, n3};
     for (int k = 0; k < (n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
     uint32_t* nodes = (uint32_t*)const_cast<float4*>(c->S.tri_nodes);
     PT_HIP(hipEventRecord(c->ev0, c->stream));
+    if (derive)
+        PT_HIP(pt::launch_normals(smooth, num_triangles, D.in[0], D.in[1], D.in[2], D.in[3], D.in[4], D.in[5], N.group, T.num_groups,
+                                  N.keys[0], N.keys[1], N.vals[0], N.vals[1], N.temp, N.temp_bytes, c->stream));
+    const bool normals = n1 || derive;
     PT_HIP(pt::launch_refit(T.num_chunks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes, nodes,
                             (uint32_t*)const_cast<float4*>(c->S.tri_chunks), (uint32_t*)const_cast<float4*>(c->S.tri_recs),
-                            D.src_of_pos, D.in[0], D.in[1], D.in[2], n1 ? D.in[3] : nullptr, n1 ? D.in[4] : nullptr,
-                            n1 ? D.in[5] : nullptr, D.node_box, D.chunk_box, c->stream));
+                            D.src_of_pos, D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
+                            normals ? D.in[5] : nullptr, D.node_box, D.chunk_box, c->stream));
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     // the root box follows (pt_wavefront.hip's refill kernels skip the triangle phase of a ray that misses it)
     uint32_t root[pt::kNode8Words];
@@ -1364,6 +1436,42 @@ int pt_update_triangles(void* ctx, int32_t num_triangles, const float* v1, const
         PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
         *out_kernel_ms = ms;
     }
+    return PT_OK;
+}
+}  // namespace
+
+int pt_update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
+                        const float* n2, const float* n3, double* out_kernel_ms) {
+    return update_triangles(ctx, num_triangles, v1, v2, v3, n1, n2, n3, false, 0, out_kernel_ms);
+}
+
+int pt_update_triangles_normals(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, int32_t mode,
+                                double* out_kernel_ms) {
+    return update_triangles(ctx, num_triangles, v1, v2, v3, nullptr, nullptr, nullptr, true, mode, out_kernel_ms);
+}
+
+int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!n1 || !n2 || !n3) return fail(PT_ERR_INVALID_ARG, "read normals: n1, n2 and n3 are required");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::RefitTables& T = c->refit;
+    if (T.num_triangles <= 0) return PT_OK;
+    const size_t arr = (size_t)T.num_triangles * 3 * sizeof(float);
+    float* out[3] = {n1, n2, n3};
+    if (T.src_of_pos.empty()) {   // no triangle of the scene is in the BVH: the device holds no normal
+        for (float* o : out) std::memset(o, 0, arr);
+        return PT_OK;
+    }
+    PT_HIP(hipSetDevice(c->device));
+    RefitDev D{};
+    if (const int rc = ensure_refit_dev(c, D)) return rc;
+    // the staged normal arrays are free between updates: a triangle outside the BVH reads as zeros
+    for (int k = 3; k < 6; k++) PT_HIP(hipMemsetAsync(D.in[k], 0, arr, c->stream));
+    PT_HIP(pt::launch_normals_gather((int64_t)T.src_of_pos.size(), (const uint32_t*)c->S.tri_recs, D.src_of_pos, D.in[3], D.in[4],
+                                     D.in[5], c->stream));
+    for (int k = 0; k < 3; k++) PT_HIP(hipMemcpyAsync(out[k], D.in[3 + k], arr, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
     return PT_OK;
 }
 

@@ -651,6 +651,13 @@ int Compiler::triangles() {
     H.refit.num_nodes = tbv->num_nodes;
     H.refit.num_chunks = (int64_t)(tbv->chunks.size() / 8);
     refit_levels((const uint32_t*)tbv->nodes.data(), tbv->num_nodes, H.refit.level_nodes, H.refit.level_off);
+    H.refit.tri_group.assign((size_t)std::max(d->num_triangles, 0), -1);
+    H.refit.num_groups = std::max(d->num_meshes, 0);
+    for (int j = 0; j < d->num_meshes; j++) {   // only the ranges of meshes in Scene.Shapes were validated: clamp
+        const int64_t f = std::max<int64_t>(d->mesh_first[j], 0);
+        const int64_t e = std::min<int64_t>((int64_t)d->mesh_first[j] + d->mesh_count[j], (int64_t)H.refit.tri_group.size());
+        for (int64_t t = f; t < e; t++) H.refit.tri_group[(size_t)t] = j;
+    }
     return PT_OK;
 }
 

@@ -50,6 +50,10 @@ struct RefitTables {
     std::vector<uint32_t> level_off;    // level l is level_nodes[level_off[l] .. level_off[l + 1])
     std::vector<int32_t> light_tri;     // per HostScene::lights entry: its source triangle, or -1 (not a loose triangle)
     int64_t num_nodes = 0, num_chunks = 0;
+    // pt_update_triangles_normals: the mesh (index into mesh_first / mesh_count) of every source triangle, -1 for
+    // one outside every mesh (a loose triangle); a triangle inside several ranges takes the last of them
+    std::vector<int32_t> tri_group;
+    int32_t num_groups = 0;             // pt_scene_desc::num_meshes
 };
 // The nodes of an 8-wide BVH (kNode8Words words each) grouped by depth.  A child's index is greater than its
 // parent's (pt_bvh.cpp Wide8::emit allocates children after their parent), so one forward sweep gives the depths.

@@ -397,16 +397,23 @@ class Renderer:
                                          int(flags), b.ctypes.data_as(C.POINTER(C.c_int32))), "pt_occluded")
         return b
 
-    def UpdateTriangles(self, v1, v2, v3, n1=None, n2=None, n3=None) -> float:
+    def UpdateTriangles(self, v1, v2, v3, n1=None, n2=None, n3=None, normals=None) -> float:
         """New vertex positions (and optionally normals) for every triangle of the scene, [n, 3] float32 in
         the order of the compiled scene's tri_v1 (pt_update_triangles): the triangle BVH is refitted on the
-        device, nothing is rebuilt or re-uploaded.  The arrays are then written into the uploaded FlatScene
-        in place, so it describes what the device holds.  Returns the device time of the kernels in ms."""
+        device, nothing is rebuilt or re-uploaded.  With normals="face" or "smooth" (exclusive with n1..n3)
+        the normals are derived on the device from the positions (pt_update_triangles_normals): the face
+        normal at every corner, or Mesh.SmoothNormals on each mesh.  The arrays (and the derived normals, read
+        back) are then written into the uploaded FlatScene in place, so it describes what the device holds.
+        Returns the device time of the kernels in ms."""
         self._ensure_scene()
         flat = self._uploaded
         n = len(flat.tri_material)
         if (n1 is None) != (n2 is None) or (n1 is None) != (n3 is None):
             raise ValueError("n1, n2 and n3 must be all given or all None")
+        if normals is not None and n1 is not None:
+            raise ValueError("normals= derives the normals: n1, n2 and n3 cannot be given with it")
+        if normals not in (None, "face", "smooth"):
+            raise ValueError('normals is None, "face" or "smooth"')
         arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (v1, v2, v3)]
         if n1 is not None:
             arrs += [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (n1, n2, n3)]
@@ -415,10 +422,26 @@ class Renderer:
         fp = C.POINTER(C.c_float)
         ptrs = [a.ctypes.data_as(fp) for a in arrs] + [fp()] * (6 - len(arrs))
         ms = C.c_double(0.0)
-        _abi.check(self._lib.pt_update_triangles(self._ctx, n, *ptrs, C.byref(ms)), "pt_update_triangles")
+        if normals is None:
+            _abi.check(self._lib.pt_update_triangles(self._ctx, n, *ptrs, C.byref(ms)), "pt_update_triangles")
+        else:
+            mode = _abi.NORMALS_FACE if normals == "face" else _abi.NORMALS_SMOOTH
+            _abi.check(self._lib.pt_update_triangles_normals(self._ctx, n, *ptrs[:3], mode, C.byref(ms)),
+                       "pt_update_triangles_normals")
+            arrs += list(self.ReadTriNormals())
         for dst, a in zip((flat.tri_v1, flat.tri_v2, flat.tri_v3, flat.tri_n1, flat.tri_n2, flat.tri_n3), arrs):
             dst[...] = a
         return float(ms.value)
+
+    def ReadTriNormals(self):
+        """The normals the uploaded scene holds on the device now (pt_read_tri_normals): n1, n2, n3, [n, 3]
+        float32 each in the order of the compiled scene's tri_n1."""
+        self._ensure_scene()
+        n = len(self._uploaded.tri_material)
+        out = [np.zeros((n, 3), np.float32) for _ in range(3)]
+        _abi.check(self._lib.pt_read_tri_normals(self._ctx, *[a.ctypes.data_as(C.POINTER(C.c_float)) for a in out]),
+                   "pt_read_tri_normals")
+        return out[0], out[1], out[2]
 
     def ReadTriBvh(self):
         """The context's triangle BVH as it stands on the device (pt_read_tri_bvh): (nodes [N, 32],
