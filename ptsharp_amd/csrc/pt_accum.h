@@ -6,10 +6,11 @@
 // order set by queue-slot atomics, so an fp64 atomic sum differs in its last bits from
 // run to run.  Here every term x (fp64) becomes an integer first,
 //
-//     V = round(x·2^44)   (|x| < 2^19, so |V| < 2^63),
+//     V = to_fix(x) ≈ x·2^44   (|x| < 2^19, so |V| < 2^63),
 //
-// and a pixel keeps, per channel, the 128-bit sum T = Σ V as a 64-bit low word (one
-// returning integer atomic per term) and a 64-bit high word that only sees the rare carry
+// a pure function of x with |V − x·2^44| ≤ 1/2 + 2^-22, and exactly round-half-even(x·2^44) for
+// x ≥ 0 (for a few small negative x an intermediate rounds first: see to_fix).  A pixel keeps,
+// per channel, the 128-bit sum T = Σ V as a 64-bit low word (one returning integer atomic per term) and a 64-bit high word that only sees the rare carry
 // out of the low word (the atomic's returned old value tells exactly which add wrapped).
 // Integer addition is associative, so T — and the fp64 value made from it at finalize,
 // T·2^-44 — is the same bits whatever order the terms arrive in, on any engine, rank split
@@ -48,9 +49,16 @@ __device__ __forceinline__ size_t fix_at(const FixAcc& A, size_t i, int k) { ret
 
 __device__ __forceinline__ bool fix_ok(double x) { return fabs(x) < kFixBig; }   // false for NaN too
 
-// x with fix_ok(x): s = x·2^12 and floor(s) are exact and |floor(s)| < 2^31 (a native fp64 →
-// int32 conversion), s − floor(s) ∈ [0, 1) is exact (its bits are s's fraction bits), its scaling
-// by 2^32 is exact, and only the magic-number sum rounds (to nearest even, like llrint).
+// x with fix_ok(x): s = x·2^12 and floor(s) are exact and floor(s) ∈ [−2^31, 2^31) (a native
+// fp64 → int32 conversion).  For x ≥ 0, s − floor(s) ∈ [0, 1) is exact (its bits are s's
+// fraction bits), its scaling by 2^32 is exact, and only the magic-number sum rounds (to nearest
+// even, like llrint): V = round-half-even(x·2^44) exactly.  For x < 0, s − floor(s) = 1 − |frac|
+// can need more than 53 bits when |frac| is small and then rounds too (by at most 2^-54, 2^-22 once
+// scaled), so |V − x·2^44| ≤ 1/2 + 2^-22 for every x, and the two roundings can disagree with a
+// single one: x = −(2^-45 + 2^-72) has s − floor(s) = 1 − 2^-33 − 2^-60, which rounds to 1 − 2^-33,
+// times 2^32 exactly 2^32 − 1/2, a tie the magic-number sum takes to even: V = 0, where
+// round-half-even(x·2^44 = −0.5000000037) is −1.  Every path converts with this one function, so
+// order independence is untouched (tests/accum_ref.py restates it; tests/test_gpu_accum.py).
 __device__ __forceinline__ long long to_fix(double x) {
     const double s = x * kFixHiScale;
     const double f = floor(s);
