@@ -26,6 +26,7 @@
 #include "pt_bvh.h"
 #include "pt_device.h"
 #include "pt_math.h"
+#include "pt_pass_plan.h"
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
 #include "pt_wavefront.h"
@@ -219,7 +220,7 @@ struct Ctx {
     pt::FixAcc acc_s{};            // [acc_s_cap] per-sample accumulators (own allocation; Q.acc_s points at it)
     uint64_t acc_s_cap = 0;
     int last_engine = 0;
-    pt::WfPlan grids{};            // persistent grid sizes (pt::wavefront_grids), once per context
+    pt::WfGrids grids{};           // persistent grid sizes (pt::wavefront_grids), once per context
     EventTimer timer;
     double tri_build_ms = 0;       // last upload: host time to build (or wait for, or find) the triangle BVH
     std::shared_ptr<const pt::TriBvhBuild> tri_build;   // that build, shared with the other contexts of its geometry
@@ -236,47 +237,18 @@ struct Ctx {
     size_t normals_temp_bytes = 0;
 };
 
-// Queue capacity bound (entries per queue).  A pass is rendered in chunks of camera
-// samples whose widest depth fits the queues; every chunk pays the fill and drain of
-// 16 persistent launches, so fewer, larger chunks are faster (C4, 16 spp per pass: 8
-// chunks of 32M-entry queues 2574 Mrays/s, 2 chunks 2809, one chunk 2853).  The bound is
-// the largest power of two whose queues (229 B per entry: two extension queues of o, d, throughput r g,
-// key + throughput b, the hits, one shadow set, the head pass' two lists: 4 B per extension ray and 16 B per
-// shadow ray) fit half of the device's memory and half of its free memory,
-// clamped to [2^20, 2^29] entries (2^29: 123 GB of the MI355X's 288 GB: C2's 33M camera samples × 16 children
-// in one chunk).  A chunk small enough for the side stream (kSideStreamMaxRays) keeps a second shadow set
-// (ensure_wavefront), within the same budget.
-constexpr uint32_t kWfMinCapLimit = 1u << 20, kWfMaxCapLimit = 1u << 29;
-#ifndef PT_EXTRA_CHUNK_MAX
-#define PT_EXTRA_CHUNK_MAX (64ull << 20)   // camera samples per chunk of the adaptive / firefly phases, at most (round 6: 32M → 64M with the 2^29-entry queues, C5 +1.8 %, profiles/r06ec_ab_extra_chunk.txt)
-#endif
 #ifndef PT_VOL_DEFER
 #define PT_VOL_DEFER 1   // split traversal: Volumes deferred to k_wf_vol_hits / k_wf_vol_shadow (0: marched in place)
 #endif
-constexpr double kSideStreamMaxRays = (double)(64ull << 20);   // a chunk's widest depth, extension rays
-// Outside this budget, for row-4 scenes only (counted in, they halved C4-sized queues from 2^28 to 2^27
-// entries and split the pass in two chunks, -3 %): the two deferred-record queues of a scene with SDF
-// shapes or Volumes (sdfq, sdfq_sh: 32 B per entry), with Volumes their record words (volq, volq_sh: 8 B),
-// and under the routed split the heavy queues (hq, hq_sh: 8 B).  At most 48 B per entry, 21 % over the
-// 229 B: 25.8 GB at 2^29 entries, inside the half of the device the budget leaves free.
-constexpr size_t kWfBytesPerEntry = 2 * (16 + 16 + 16 + 16) + 16 + (64 + 1) + (4 + 16);
 
-// PT_WF_MAX_CAP (entries, environment) lowers the bound: tests use it to force many chunks.
-uint32_t wf_max_cap(Ctx* c) {
+// The context's queue capacity bound (pt_pass_plan.h: the budget and what it counts), found at its first pass:
+// from PT_WF_MAX_CAP if the environment sets it, else from the device's memory.
+uint32_t wf_max_cap(Ctx* c, const pt::PassKnobs& knobs) {
     if (c->wf_max_cap) return c->wf_max_cap;
-    if (const char* env = std::getenv("PT_WF_MAX_CAP")) {
-        const unsigned long long v = std::strtoull(env, nullptr, 10);
-        uint32_t cap = kWfMaxCapLimit;
-        while (cap > (uint32_t)pt::kParts * 1024u && cap > v) cap >>= 1;
-        return c->wf_max_cap = cap;
-    }
+    if (knobs.wf_max_cap_set) return c->wf_max_cap = pt::wf_cap_for_limit(knobs.wf_max_cap);
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = (size_t)kWfMinCapLimit * kWfBytesPerEntry * 4;
-    const size_t budget = std::min(total_b / 2, free_b / 2);   // and at most half of what is free now
-    uint32_t cap = kWfMaxCapLimit;
-    while (cap > kWfMinCapLimit && (size_t)cap * kWfBytesPerEntry > budget) cap >>= 1;
-    c->wf_max_cap = cap;
-    return cap;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = (size_t)pt::kWfMinCapLimit * pt::kWfBytesPerEntry * 4;
+    return c->wf_max_cap = pt::wf_cap_for_budget(std::min(total_b / 2, free_b / 2));
 }
 
 void free_wavefront(Ctx* c) {
@@ -609,35 +581,49 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     return PT_OK;
 }
 
-// Passes one batch may hold: its accumulator sets (pt::kFixWords 64-bit words + 3 fp64 side sums per
-// pixel and pass) within an eighth of the device's memory.  PT_BATCH_MAX_PASSES (environment, tests)
-// lowers it.
-static int32_t batch_passes_max(Ctx* c) {
+// Passes one batch may hold (pt::batch_passes_for): its accumulator sets, pt::kFixWords 64-bit words twice + 3 fp64
+// side sums per pixel and pass.
+static int32_t batch_passes_max(Ctx* c, const pt::PassKnobs& knobs) {
     const size_t per_pass = (size_t)c->width * (size_t)c->height *
                             (2 * pt::kFixWords * sizeof(unsigned long long) + 3 * sizeof(double));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = (size_t)8 << 30;
-    int64_t k = (int64_t)std::max<size_t>(1, (total_b / 8) / std::max<size_t>(per_pass, 1));
-    if (const char* env = std::getenv("PT_BATCH_MAX_PASSES")) k = std::min<int64_t>(k, std::max(1LL, std::atoll(env)));
-    return (int32_t)std::min<int64_t>(k, INT32_MAX);
+    return pt::batch_passes_for(total_b, per_pass, knobs.batch_max_passes);
 }
 
-static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* sampler, const pt_pass_params* pass,
-                            pt_trace_counters* counted) {
-    if (!c || !camera || !sampler || !pass) return fail(PT_ERR_INVALID_ARG, "NULL argument");
-    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "pt_render_pass before pt_upload_scene");
-    if (c->width <= 1 || c->height <= 1)   // Camera.CastRay divides by w - 1 and h - 1 (Camera.cs:101-102)
-        return fail(PT_ERR_INVALID_ARG, "a pass needs width and height > 1");
-    if (pass->spp <= 0) return fail(PT_ERR_INVALID_ARG, "spp must be >= 1");
-    if (sampler->first_hit_samples <= 0 || sampler->max_bounces < 0) return fail(PT_ERR_INVALID_ARG, "bad sampler");
-    if (sampler->specular_mode == PT_SPEC_ALL && sampler->max_bounces > 32)
-        return fail(PT_ERR_UNSUPPORTED, "SpecularModeAll with MaxBounces > 32");
-    if (sampler->light_mode < 0 || sampler->light_mode > 1 || sampler->specular_mode < 0 || sampler->specular_mode > 2)
-        return fail(PT_ERR_INVALID_ARG, "bad light/specular mode");
-    PT_HIP(hipSetDevice(c->device));
-    const int tiles_x = (c->width + 31) / 32, tiles_y = (c->height + 31) / 32;
-    int num_tiles = tiles_x * tiles_y;
-    const int32_t* d_tiles = nullptr;
+// The environment's switches of a pass (pt::PassKnobs; tests, A/B runs), read at each pt_render_pass call: tests
+// change them between the passes of one process.
+static pt::PassKnobs read_pass_knobs() {
+    pt::PassKnobs k;
+    if (const char* f = std::getenv("PT_SHADE_FORM")) k.shade_form = !std::strcmp(f, "direct") ? 1 : !std::strcmp(f, "scan") ? 2 : 0;
+    if (const char* f = std::getenv("PT_LANES")) k.lanes = !std::strcmp(f, "0") ? 0 : !std::strcmp(f, "1") ? 1 : -1;
+    if (const char* f = std::getenv("PT_HEAD")) k.head = !std::strcmp(f, "0") ? 0 : 1;
+    if (const char* f = std::getenv("PT_HEAD_STATS")) k.head_stats = !std::strcmp(f, "1") ? 1 : 0;
+    if (const char* f = std::getenv("PT_LINEAR")) k.linear = !std::strcmp(f, "0") ? 0 : -1;
+    if (const char* f = std::getenv("PT_SIDE_STREAM")) k.side_stream = !std::strcmp(f, "1") ? 1 : !std::strcmp(f, "0") ? 0 : -1;
+    if (const char* f = std::getenv("PT_SHADOW_TAIL")) k.tail_early = !std::strcmp(f, "early") ? 1 : 0;
+    if (const char* f = std::getenv("PT_BATCH_MAX_PASSES")) k.batch_max_passes = std::max(1LL, std::atoll(f));
+    if (const char* f = std::getenv("PT_WF_MAX_CAP")) {
+        k.wf_max_cap_set = true;
+        k.wf_max_cap = std::strtoull(f, nullptr, 10);
+    }
+    return k;
+}
+
+// What a pass' launches take: the kernels' arguments, and on the wavefront engine its plan.
+struct PassRun {
+    pt::DevCamera cam;
+    pt::DevSampler smp;
+    pt::DevPass P;
+    pt::DevBuffer B;
+    pt::WfPlan wf{};
+    bool count = false;               // a counted pass
+    pt::LaunchTimer* tm = nullptr;    // PT_PASS_KERNEL_TIMING
+};
+
+// The pass' tile list on the device, uploaded when it differs from the last pass' (*d_tiles null: every tile).
+static int upload_tile_list(Ctx* c, const pt_pass_params* pass, int image_tiles, const int32_t** d_tiles) {
+    *d_tiles = nullptr;
     if (pass->num_tiles > 0) {
         if (!pass->tiles) return fail(PT_ERR_INVALID_ARG, "tiles is NULL");
         if (pass->num_tiles > c->tiles_cap) {
@@ -651,193 +637,117 @@ static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* s
         if (c->h_tiles.size() != (size_t)pass->num_tiles ||
             std::memcmp(c->h_tiles.data(), pass->tiles, (size_t)pass->num_tiles * sizeof(int32_t))) {
             // ids in range, none twice (a tile listed twice would be rendered into its pixels twice)
-            if (int rc = pt_tile_lists_check(pass->tiles, pass->num_tiles, tiles_x * tiles_y)) return rc;
+            if (int rc = pt_tile_lists_check(pass->tiles, pass->num_tiles, image_tiles)) return rc;
             c->h_tiles.assign(pass->tiles, pass->tiles + pass->num_tiles);
             PT_HIP(hipMemcpyAsync(c->d_tiles, c->h_tiles.data(), (size_t)pass->num_tiles * sizeof(int32_t),
                                   hipMemcpyHostToDevice, c->stream));
         }
-        d_tiles = c->d_tiles;
-        num_tiles = pass->num_tiles;
+        *d_tiles = c->d_tiles;
     }
     c->pass_tiles = pass->num_tiles > 0 ? pass->num_tiles : 0;
-    pt::DevCamera cam;
-    std::memcpy(cam.p, camera->p, sizeof cam.p); std::memcpy(cam.u, camera->u, sizeof cam.u);
-    std::memcpy(cam.v, camera->v, sizeof cam.v); std::memcpy(cam.w, camera->w, sizeof cam.w);
-    cam.m = camera->m; cam.focal_distance = camera->focal_distance; cam.aperture_radius = camera->aperture_radius;
-    pt::DevSampler smp{sampler->first_hit_samples, sampler->max_bounces, sampler->direct_lighting, sampler->soft_shadows,
-                       sampler->light_mode, sampler->specular_mode};
-    pt::DevPass P{c->width, c->height, pass->spp, pass->stratified, pass->seed, pass->pass_index, tiles_x, d_tiles,
-                  num_tiles};
-    P.acc_stride = (uint32_t)((size_t)c->width * (size_t)c->height);
-    pt::DevBuffer B{c->d_m, c->d_v, c->d_n, c->d_counters};
-    // ---- engine choice and wavefront plan
-    const int n_root = (int)std::sqrt((double)sampler->first_hit_samples);
-    const int nm_root = (sampler->specular_mode != PT_SPEC_NAIVE) ? 2 : 1;
-    const int nm = sampler->specular_mode == PT_SPEC_ALL ? 2 : 1;
-    pt::WfPlan plan{};
-    if (const char* f = std::getenv("PT_SHADE_FORM")) plan.shade_form = !std::strcmp(f, "direct") ? 1 : !std::strcmp(f, "scan") ? 2 : 0;
-    plan.lanes = -1;
-    if (const char* f = std::getenv("PT_LANES")) plan.lanes = !std::strcmp(f, "0") ? 0 : !std::strcmp(f, "1") ? 1 : -1;
-    plan.head = 1;
-    if (const char* f = std::getenv("PT_HEAD")) plan.head = !std::strcmp(f, "0") ? 0 : 1;
-    if (const char* f = std::getenv("PT_HEAD_STATS")) plan.head_stats = !std::strcmp(f, "1") ? 1 : 0;
-    plan.linear = -1;
-    if (const char* f = std::getenv("PT_LINEAR")) plan.linear = !std::strcmp(f, "0") ? 0 : -1;
-    plan.root_children = (uint32_t)std::max(1, n_root * n_root * nm_root);
-    plan.children = (uint32_t)nm;
-    plan.lights_per_child = (uint32_t)(sampler->light_mode == PT_LIGHT_ALL ? std::max(1, c->S.num_lights) : 1);
+    return PT_OK;
+}
+
+// The wavefront engine's queues and buffers for this plan, and the plan as its launches take it.
+static int prepare_wavefront(Ctx* c, const pt_pass_params* pass, const pt::PassPlan& plan, const pt::PassKnobs& knobs,
+                             pt::WfPlan& wf) {
     if (!c->grids.trace_blocks) PT_HIP(pt::wavefront_grids(c->grids));
-    plan.trace_blocks = c->grids.trace_blocks;
-    plan.shade_blocks = c->grids.shade_blocks;
-    plan.shadow_blocks = c->grids.shadow_blocks;
-    plan.lanes_trace_blocks = c->grids.lanes_trace_blocks;
-    plan.lanes_shadow_blocks = c->grids.lanes_shadow_blocks;
-    plan.full_trace_blocks = c->grids.full_trace_blocks;
-    plan.full_shadow_blocks = c->grids.full_shadow_blocks;
-    plan.linear_trace_blocks = c->grids.linear_trace_blocks;
-    plan.linear_shadow_blocks = c->grids.linear_shadow_blocks;
-    plan.head_trace_blocks = c->grids.head_trace_blocks;
-    plan.head_shadow_blocks = c->grids.head_shadow_blocks;
-    plan.list_trace_blocks = c->grids.list_trace_blocks;
-    plan.list_shadow_blocks = c->grids.list_shadow_blocks;
-    const bool extra = pass->adaptive_samples > 0 || pass->firefly_samples > 0;
-    const bool serial = (pass->flags & PT_PASS_SERIAL) != 0;   // Renderer.Render's extra phases (NumCPU == 1)
-    // pt_pass_params.passes: K consecutive passes.  Plain RenderParallel passes run as one batch
-    // (one launch sequence over all K passes' camera samples, so a small share — one rank's tiles
-    // of a multi-GPU frame — fills the GPU like a whole frame); the others pass by pass.
-    const int32_t batch = pass->passes > 1 ? pass->passes : 1;
-    if (batch > 1 && counted) return fail(PT_ERR_INVALID_ARG, "counted passes run one at a time (passes = 1)");
-    const bool batchable = batch > 1 && !extra && !serial && !pass->stratified && pass->engine != PT_ENGINE_MEGAKERNEL &&
-                           (uint64_t)P.acc_stride * (uint64_t)batch <= 0xFFFFFFFFull;
-    // A batch keeps one set of per-pixel accumulators per pass (72 B per pixel): the sets of one launch
-    // sequence stay within an eighth of the device's memory; a larger K runs as consecutive sub-batches,
-    // each bit-identical to its passes run one by one (4K at K = 500 would ask for ~300 GB).
-    const int32_t sub = batchable ? std::min(batch, batch_passes_max(c)) : 1;
-    if (batchable && sub == batch) P.passes = batch;
-    const uint64_t cam_samples = (uint64_t)num_tiles * 1024u * (uint64_t)(pass->stratified ? 1 : pass->spp) *
-                                 (uint64_t)P.passes;
-    double growth = 1.0;   // queue growth beyond depth 1 (SpecularModeAll doubles every depth)
-    if (nm == 2) growth = std::ldexp(1.0, std::min(std::max(sampler->max_bounces - 1, 0), 60));
-    const double per_sample = (double)plan.root_children * growth;   // extension rays per camera sample (widest depth)
-    const double per_sample_nee = per_sample * (double)plan.lights_per_child;  // shadow-ray slots per camera sample
-    // Queues are kParts partitions.  Camera samples are dealt to the XCD groups in
-    // 256-sample blocks, so a group gets at most ceil(ceil(chunk/256)/kParts)·256 of
-    // them, and everything it appends stays in its own partition.
-    const double pmax = (double)(wf_max_cap(c) / pt::kParts);
-    const int32_t spp_launch = pass->stratified ? 1 : pass->spp;
-    auto group_max = [&](uint64_t ch) { return (double)pt::deal_group_max(ch, spp_launch); };
-    uint64_t chunk = (uint64_t)std::min<double>((double)cam_samples,
-                                                std::floor(pmax / per_sample_nee / 256.0) * 256.0 * pt::kParts);
-    // the deal's runs can give one partition a little more than an eighth: shrink until it fits
-    {
-        const uint64_t step = (uint64_t)pt::deal_run(spp_launch) * 256u * pt::kParts;
-        while (chunk > step && group_max(chunk) * std::max(1.0, per_sample_nee) > pmax) chunk -= step;
-        while (chunk > 256 && group_max(chunk) * std::max(1.0, per_sample_nee) > pmax) chunk -= 256;
-        const uint64_t tile = (uint64_t)pt::deal_run(spp_launch) * 256u;   // chunks of whole tiles where they fit
-        if (chunk < cam_samples && chunk >= tile) chunk = chunk / tile * tile;
+    if (int rc = ensure_wavefront(c, plan.cap, plan.scap, plan.passes_per_launch, plan.use_side)) return rc;
+    if (pass->adaptive_samples > 0 || pass->firefly_samples > 0)
+        if (int rc = ensure_extra(c, plan.chunk_extra)) return rc;
+    static_cast<pt::WfGrids&>(wf) = c->grids;
+    static_cast<pt::PassPlan&>(wf) = plan;
+    static_cast<pt::PassKnobs&>(wf) = knobs;
+    if (plan.use_side) {
+        wf.side = c->side;
+        wf.ev_main = c->ev_main;
+        wf.ev_side[0] = c->ev_side[0];
+        wf.ev_side[1] = c->ev_side[1];
     }
-    if (pass->adaptive_samples < 0 || pass->firefly_samples < 0) return fail(PT_ERR_INVALID_ARG, "negative extra samples");
-    // The adaptive / firefly phases' chunks: as many of their camera samples as the queues may hold (the main
-    // loop's chunk is bounded by its own samples: C5's 1-spp pass at 4K gave the 32-sample adaptive phase 32
-    // chunks of 8.3M), up to PT_EXTRA_CHUNK_MAX samples, whole tiles' worth of entries.
-    uint64_t chunk_extra = chunk;
-    if (extra && !serial) {
-        const uint64_t k = (uint64_t)std::max(pass->adaptive_samples, 1);
-        const uint64_t all = (uint64_t)num_tiles * 1024u * k;
-        uint64_t ce = (uint64_t)std::min<double>((double)std::min<uint64_t>(all, (uint64_t)PT_EXTRA_CHUNK_MAX),
-                                                 std::floor(pmax / per_sample_nee / 256.0) * 256.0 * pt::kParts);
-        const uint64_t step = (uint64_t)pt::deal_run(spp_launch) * 256u * pt::kParts;
-        while (ce > step && group_max(ce) * std::max(1.0, per_sample_nee) > pmax) ce -= step;
-        while (ce > 256 && group_max(ce) * std::max(1.0, per_sample_nee) > pmax) ce -= 256;
-        ce = ce / (1024u * k) * (1024u * k);   // whole tiles of entries
-        if (ce > chunk_extra) chunk_extra = ce;
+    // PT_SHADOW_TAIL=early: k_wf_shadow_lanes hands stack entries to idle lanes from the first claim on, so the
+    // tail protocol runs all pass long (pt_stats.tail_handoffs counts it)
+    c->Q.tail_early = knobs.tail_early;
+    return PT_OK;
+}
+
+// After a gather or a loaded checkpoint the Buffer holds other ranks' tiles: a tile-subset pass clears them
+// before it adds to its own (k_clear_foreign).
+static int clear_foreign_tiles(Ctx* c, const pt_pass_params* pass, const pt::DevBuffer& B, int tiles_x, int image_tiles) {
+    if (!(c->gathered || (c->loaded && c->comm))) return PT_OK;
+    c->gathered = false;
+    c->loaded = false;
+    if (pass->num_tiles <= 0) return PT_OK;
+    std::vector<uint8_t> own((size_t)image_tiles, 0);
+    for (int i = 0; i < pass->num_tiles; i++) own[(size_t)pass->tiles[i]] = 1;
+    if (!c->d_own) PT_HIP(hipMalloc(&c->d_own, (size_t)image_tiles));
+    PT_HIP(hipMemcpyAsync(c->d_own, own.data(), (size_t)image_tiles, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(pt::k_clear_foreign, dim3(2048), dim3(256), 0, c->stream, B, c->width, c->height, tiles_x,
+                       (const uint8_t*)c->d_own);
+    PT_HIP(hipGetLastError());
+    PT_HIP(hipStreamSynchronize(c->stream));   // `own` is a host temporary
+    return PT_OK;
+}
+
+// Renderer.Render's extra phases (PT_PASS_SERIAL; Renderer.cs:80-198): after a pixel's main samples,
+// AdaptiveSamples individual samples if its σmax ≥ 1 (:153-175), then FireflySamples individual samples
+// if its σmax then exceeds 1 (:177-191).  Each decision reads the pixel's own Buffer
+// only, so the phases run over all pixels, one after the other.
+static int run_extra_serial(Ctx* c, const pt_pass_params* pass, const PassRun& r) {
+    const int32_t K[2] = {pass->adaptive_samples, pass->firefly_samples};
+    const uint32_t base[2] = {pt::kAdaptiveSampleBase, pt::kFireflySampleBase};
+    for (int ph = 0; ph < 2; ph++) {
+        if (K[ph] <= 0) continue;
+        PT_HIP(pt::select_pixels(r.P, r.B, ph == 0 ? 1 : 0, c->d_plist, c->d_fcount, c->stream));
+        uint32_t nsel = 0;
+        PT_HIP(hipMemcpyAsync(&nsel, c->d_fcount, sizeof nsel, hipMemcpyDeviceToHost, c->stream));
+        PT_HIP(hipStreamSynchronize(c->stream));
+        PT_HIP(pt::wavefront_extra(c->S, r.cam, r.smp, r.P, r.B, c->Q, r.wf, r.count, c->stream, r.tm,
+                                   ph == 0 ? pt::EXTRA_ADD : pt::EXTRA_ADD_SCALED, K[ph], base[ph], nsel,
+                                   c->d_plist, nullptr, nullptr, nullptr));
     }
-    int engine = pass->engine;
-    if (engine == PT_ENGINE_AUTO)
-        engine = extra || chunk >= 4096 || chunk >= cam_samples ? PT_ENGINE_WAVEFRONT : PT_ENGINE_MEGAKERNEL;
-    if (engine == PT_ENGINE_MEGAKERNEL && extra)
-        return fail(PT_ERR_UNSUPPORTED, "adaptive / firefly phases run on the wavefront engine");
-    if (engine == PT_ENGINE_WAVEFRONT && chunk < 1)
-        return fail(PT_ERR_UNSUPPORTED, "wavefront queues cannot hold one camera sample of this sampler (use the megakernel)");
-    if (engine != PT_ENGINE_WAVEFRONT && engine != PT_ENGINE_MEGAKERNEL) return fail(PT_ERR_INVALID_ARG, "bad engine");
-    if (batch > 1 && !(P.passes > 1 && engine == PT_ENGINE_WAVEFRONT)) {
-        // not one batch: the K passes one after another (or sub-batches of `sub` passes), the stats summed
-        const int32_t step = (sub > 1 && engine == PT_ENGINE_WAVEFRONT) ? sub : 1;
-        pt_pass_params one = *pass;
-        pt_stats sum = c->stats;
-        uint64_t rays = 0, shadow = 0, handoffs = 0;
-        double ms = 0.0;
-        for (int32_t k = 0; k < batch; k += step) {
-            one.pass_index = pass->pass_index + (uint32_t)k;
-            one.passes = std::min(step, batch - k);
-            if (int rc = render_pass_impl(c, camera, sampler, &one, nullptr)) return rc;
-            rays += c->stats.rays;
-            shadow += c->stats.shadow_rays;
-            handoffs += c->stats.tail_handoffs;
-            ms += c->stats.last_pass_ms;
-            for (int j = 0; j < PT_K_SLOTS; j++) {
-                sum.kernel_ms[j] = (k ? sum.kernel_ms[j] : 0.0) + c->stats.kernel_ms[j];
-                sum.kernel_launches[j] = (k ? sum.kernel_launches[j] : 0) + c->stats.kernel_launches[j];
-            }
-        }
-        std::memcpy(c->stats.kernel_ms, sum.kernel_ms, sizeof sum.kernel_ms);
-        std::memcpy(c->stats.kernel_launches, sum.kernel_launches, sizeof sum.kernel_launches);
-        c->stats.rays = rays;
-        c->stats.shadow_rays = shadow;
-        c->stats.tail_handoffs = handoffs;
-        c->stats.last_pass_ms = ms;
-        return PT_OK;
+    return PT_OK;
+}
+
+// RenderParallel's extra phases: every pixel's adaptive samples (Renderer.cs:340-410), then the firefly rounds
+// (Renderer.cs:412-470).
+static int run_extra_parallel(Ctx* c, const pt_pass_params* pass, const PassRun& r) {
+    if (pass->adaptive_samples > 0)
+        PT_HIP(pt::wavefront_extra(c->S, r.cam, r.smp, r.P, r.B, c->Q, r.wf, r.count, c->stream, r.tm, 0,
+                                   pass->adaptive_samples, pt::kAdaptiveSampleBase, (uint64_t)r.P.num_tiles * 1024u,
+                                   nullptr, nullptr, nullptr, nullptr));
+    if (pass->firefly_samples <= 0) return PT_OK;
+    PT_HIP(pt::select_pixels(r.P, r.B, 0, c->d_plist, c->d_fcount, c->stream));
+    uint32_t nsel = 0;
+    PT_HIP(hipMemcpyAsync(&nsel, c->d_fcount, sizeof nsel, hipMemcpyDeviceToHost, c->stream));
+    const size_t npx = (size_t)c->width * (size_t)c->height;
+    PT_HIP(hipMemcpyAsync(c->d_snap, c->d_m, npx * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (c->comm) {
+        // neighbours on other ranks' tiles: the disjoint M buffers sum to the full frame
+        ncclResult_t e = ncclAllReduce(c->d_snap, c->d_snap, npx * 3, ncclFloat64, ncclSum, c->comm, c->stream);
+        if (e != ncclSuccess) return fail(PT_ERR_RCCL, std::string("ncclAllReduce: ") + ncclGetErrorString(e));
     }
-    if (engine == PT_ENGINE_WAVEFRONT) {
-        plan.chunk = chunk;
-        plan.chunk_extra = chunk_extra;
-        // Shadow passes on the side stream, beside the next depth's closest-hit pass, when a
-        // chunk's widest depth is small enough for the launches' fill and drain to matter (one
-        // rank's 1/8 share of C4 passed one at a time, 33M rays: +6.5 %); a full C4 frame (265M)
-        // runs 0.3 % slower that way and C2's 16-child chunks (268M) 6.2 % slower (10632 vs 11332
-        // Mrays/s, profiles/r03c_c2_*.json): they keep one stream.  The bound is on rays, not
-        // camera samples (round 2 used 20M camera samples, which sent C2 to the side stream).
-        // PT_SIDE_STREAM=0|1 (environment; tests) forces one stream or the side stream.
-        bool side = (double)chunk * per_sample <= kSideStreamMaxRays;
-        if (const char* f = std::getenv("PT_SIDE_STREAM")) side = !std::strcmp(f, "1") ? true : !std::strcmp(f, "0") ? false : side;
-        if (side) {
-            plan.side = c->side;
-            plan.ev_main = c->ev_main;
-            plan.ev_side[0] = c->ev_side[0];
-            plan.ev_side[1] = c->ev_side[1];
-        }
-        const double group_samples = group_max(chunk_extra);   // (>= chunk's)
-        const double need = group_samples * per_sample;   // a partition's widest depth
-        const uint32_t pcap = (uint32_t)std::min(pmax, std::max(8192.0, std::max(group_samples, need)));
-        const uint32_t spcap = (uint32_t)std::min(pmax, std::max(8192.0, group_samples * per_sample_nee));
-        uint32_t cap = pcap * pt::kParts, scap = spcap * pt::kParts;
-        int rc = ensure_wavefront(c, cap, scap, P.passes, side);
-        if (rc) return rc;
-        if ((uint64_t)pass->adaptive_samples > chunk)
-            return fail(PT_ERR_UNSUPPORTED, "adaptive samples exceed one wavefront chunk");
-        if (serial && (uint64_t)pass->firefly_samples > chunk)
-            return fail(PT_ERR_UNSUPPORTED, "firefly samples exceed one wavefront chunk");
-        if (extra && (rc = ensure_extra(c, chunk_extra))) return rc;
+    PT_HIP(hipStreamSynchronize(c->stream));
+    // Renderer.cs:430-445 traces a candidate's samples one after another and stops at the first
+    // IsFirefly sample: rounds of one sample per still-active pixel, so exactly those samples are
+    // traced (and counted in Scene.rays), no more.
+    uint32_t* list = c->d_plist;
+    uint32_t* next = c->d_plist2;
+    for (int j = 0; j < pass->firefly_samples && nsel > 0; j++) {
+        PT_HIP(hipMemsetAsync(c->d_fcount + 1, 0, sizeof(uint32_t), c->stream));
+        PT_HIP(pt::wavefront_extra(c->S, r.cam, r.smp, r.P, r.B, c->Q, r.wf, r.count, c->stream, r.tm,
+                                   pt::EXTRA_FIREFLY_STOP, 1, pt::kFireflySampleBase + (uint32_t)j, nsel, list, c->d_snap,
+                                   next, c->d_fcount + 1));
+        PT_HIP(hipMemcpyAsync(&nsel, c->d_fcount + 1, sizeof nsel, hipMemcpyDeviceToHost, c->stream));
+        PT_HIP(hipStreamSynchronize(c->stream));
+        std::swap(list, next);
     }
-    c->last_engine = engine;
-    if (c->gathered || (c->loaded && c->comm)) {
-        c->gathered = false;
-        c->loaded = false;
-        if (pass->num_tiles > 0) {
-            const int ntiles = tiles_x * tiles_y;
-            std::vector<uint8_t> own((size_t)ntiles, 0);
-            for (int i = 0; i < pass->num_tiles; i++) own[(size_t)pass->tiles[i]] = 1;
-            if (!c->d_own) PT_HIP(hipMalloc(&c->d_own, (size_t)ntiles));
-            PT_HIP(hipMemcpyAsync(c->d_own, own.data(), (size_t)ntiles, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(pt::k_clear_foreign, dim3(2048), dim3(256), 0, c->stream, B, c->width, c->height, tiles_x,
-                               (const uint8_t*)c->d_own);
-            PT_HIP(hipGetLastError());
-            PT_HIP(hipStreamSynchronize(c->stream));   // `own` is a host temporary
-        }
-    }
-    const bool timing = (pass->flags & PT_PASS_KERNEL_TIMING) != 0;
+    return PT_OK;
+}
+
+// The pass' launches, between the two events that time it.
+static int run_pass(Ctx* c, const pt_pass_params* pass, int engine, const PassRun& r) {
     c->timer.reset(c->stream);
-    PT_HIP(hipMemsetAsync(c->d_counters, 0, (counted ? pt::kCounterAllocWords : pt::kCounterWords) * sizeof(unsigned long long),
+    PT_HIP(hipMemsetAsync(c->d_counters, 0, (r.count ? pt::kCounterAllocWords : pt::kCounterWords) * sizeof(unsigned long long),
                           c->stream));   // and the overflow flag; a counted pass' march clock slots too
     // a counted pass also counts the Volume / SDFShape march steps (counters 9, 10); the launches
     // take the scene by value, so the pointer is cleared again whichever way this call returns
@@ -845,72 +755,43 @@ static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* s
         pt::DevScene& S;
         ~MarchScope() { S.march = nullptr; }
     } march_scope{c->S};
-    c->S.march = counted ? c->d_counters + 9 : nullptr;
+    c->S.march = r.count ? c->d_counters + 9 : nullptr;
     PT_HIP(hipEventRecord(c->ev0, c->stream));
     if (engine == PT_ENGINE_WAVEFRONT) {
-        pt::LaunchTimer* tm = timing ? &c->timer : nullptr;
-        // PT_SHADOW_TAIL=early (environment; tests): k_wf_shadow_lanes hands stack entries to idle lanes from
-        // the first claim on, so the tail protocol runs all pass long (pt_stats.tail_handoffs counts it)
-        const char* tail_env = std::getenv("PT_SHADOW_TAIL");
-        c->Q.tail_early = (tail_env && !std::strcmp(tail_env, "early")) ? 1 : 0;
-        PT_HIP(pt::wavefront_pass(c->S, cam, smp, P, B, c->Q, plan, counted != nullptr, c->stream, tm));
-        if (serial) {
-            // Renderer.Render (Renderer.cs:80-198): after a pixel's main samples, AdaptiveSamples
-            // individual samples if its σmax ≥ 1 (:153-175), then FireflySamples individual samples
-            // if its σmax then exceeds 1 (:177-191).  Each decision reads the pixel's own Buffer
-            // only, so the phases run over all pixels, one after the other.
-            const int32_t K[2] = {pass->adaptive_samples, pass->firefly_samples};
-            const uint32_t base[2] = {pt::kAdaptiveSampleBase, pt::kFireflySampleBase};
-            for (int ph = 0; ph < 2; ph++) {
-                if (K[ph] <= 0) continue;
-                PT_HIP(pt::select_pixels(P, B, ph == 0 ? 1 : 0, c->d_plist, c->d_fcount, c->stream));
-                uint32_t nsel = 0;
-                PT_HIP(hipMemcpyAsync(&nsel, c->d_fcount, sizeof nsel, hipMemcpyDeviceToHost, c->stream));
-                PT_HIP(hipStreamSynchronize(c->stream));
-                PT_HIP(pt::wavefront_extra(c->S, cam, smp, P, B, c->Q, plan, counted != nullptr, c->stream, tm,
-                                           ph == 0 ? pt::EXTRA_ADD : pt::EXTRA_ADD_SCALED, K[ph], base[ph], nsel,
-                                           c->d_plist, nullptr, nullptr, nullptr));
-            }
-        }
-        if (!serial && pass->adaptive_samples > 0)  // Renderer.cs:340-410
-            PT_HIP(pt::wavefront_extra(c->S, cam, smp, P, B, c->Q, plan, counted != nullptr, c->stream, tm, 0,
-                                       pass->adaptive_samples, pt::kAdaptiveSampleBase, (uint64_t)num_tiles * 1024u,
-                                       nullptr, nullptr, nullptr, nullptr));
-        if (!serial && pass->firefly_samples > 0) {  // Renderer.cs:412-470
-            PT_HIP(pt::select_pixels(P, B, 0, c->d_plist, c->d_fcount, c->stream));
-            uint32_t nsel = 0;
-            PT_HIP(hipMemcpyAsync(&nsel, c->d_fcount, sizeof nsel, hipMemcpyDeviceToHost, c->stream));
-            const size_t npx = (size_t)c->width * (size_t)c->height;
-            PT_HIP(hipMemcpyAsync(c->d_snap, c->d_m, npx * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            if (c->comm) {
-                // neighbours on other ranks' tiles: the disjoint M buffers sum to the full frame
-                ncclResult_t r = ncclAllReduce(c->d_snap, c->d_snap, npx * 3, ncclFloat64, ncclSum, c->comm, c->stream);
-                if (r != ncclSuccess) return fail(PT_ERR_RCCL, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
-            }
-            PT_HIP(hipStreamSynchronize(c->stream));
-            // Renderer.cs:430-445 traces a candidate's samples one after another and stops at the first
-            // IsFirefly sample: rounds of one sample per still-active pixel, so exactly those samples are
-            // traced (and counted in Scene.rays), no more.
-            uint32_t* list = c->d_plist;
-            uint32_t* next = c->d_plist2;
-            for (int j = 0; j < pass->firefly_samples && nsel > 0; j++) {
-                PT_HIP(hipMemsetAsync(c->d_fcount + 1, 0, sizeof(uint32_t), c->stream));
-                PT_HIP(pt::wavefront_extra(c->S, cam, smp, P, B, c->Q, plan, counted != nullptr, c->stream, tm,
-                                           pt::EXTRA_FIREFLY_STOP, 1,
-                                           pt::kFireflySampleBase + (uint32_t)j, nsel, list, c->d_snap, next,
-                                           c->d_fcount + 1));
-                PT_HIP(hipMemcpyAsync(&nsel, c->d_fcount + 1, sizeof nsel, hipMemcpyDeviceToHost, c->stream));
-                PT_HIP(hipStreamSynchronize(c->stream));
-                std::swap(list, next);
-            }
-        }
+        PT_HIP(pt::wavefront_pass(c->S, r.cam, r.smp, r.P, r.B, c->Q, r.wf, r.count, c->stream, r.tm));
+        if (int rc = (pass->flags & PT_PASS_SERIAL) ? run_extra_serial(c, pass, r) : run_extra_parallel(c, pass, r)) return rc;
     } else {
-        if (timing) c->timer.begin(PT_K_MEGAKERNEL, c->stream);
-        PT_HIP(pt::launch_render_pass(c->S, cam, smp, P, B, num_tiles, counted != nullptr, c->stream));
-        if (timing) c->timer.end(PT_K_MEGAKERNEL, c->stream);
+        if (r.tm) r.tm->begin(PT_K_MEGAKERNEL, c->stream);
+        PT_HIP(pt::launch_render_pass(c->S, r.cam, r.smp, r.P, r.B, r.P.num_tiles, r.count, c->stream));
+        if (r.tm) r.tm->end(PT_K_MEGAKERNEL, c->stream);
     }
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     if (c->timer.failed) return fail(PT_ERR_HIP, "hipEventRecord (kernel timing) failed");
+    return PT_OK;
+}
+
+// A counted pass' counters as pt_render_pass_counted returns them.
+// counters: [0..2] closest-hit rays/nodes/prims, [3] shading fetches, [4..6] shadow rays/nodes/prims
+static void read_trace_counters(const unsigned long long* ctr, pt_trace_counters* counted) {
+    counted->rays = ctr[0] + ctr[4];
+    counted->nodes_visited = ctr[1] + ctr[5];
+    counted->prims_tested = ctr[2] + ctr[6];
+    counted->shading_fetches = ctr[3];
+    counted->shadow_rays = ctr[4];
+    counted->shadow_nodes = ctr[5];
+    counted->shadow_prims = ctr[6];
+    counted->lit_shadow_rays = ctr[7];
+    counted->accum_runs = ctr[8];
+    counted->volume_samples = ctr[9];
+    counted->sdf_evals = ctr[10];
+    for (int k = 0; k < 8; k++) {
+        counted->march_clock[k] = 0;
+        for (int j = 0; j < pt::kMarchSlots; j++) counted->march_clock[k] += ctr[pt::kMarchClockWord + 8 * j + k];
+    }
+}
+
+// Waits for the pass, reads its counters back and fills pt_stats (and `counted`).
+static int collect_stats(Ctx* c, int engine, int32_t passes, bool timing, pt_trace_counters* counted) {
     const unsigned long long* ctr = c->h_counters;
     PT_HIP(hipMemcpyAsync(c->h_counters, c->d_counters, (counted ? pt::kCounterAllocWords : pt::kCounterWords) * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, c->stream));
@@ -919,7 +800,6 @@ static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* s
         return fail(PT_ERR_OUT_OF_MEMORY, "wavefront queue overflow (pass results are incomplete)");
     float ms = 0.f;
     PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    // counters: [0..2] closest-hit rays/nodes/prims, [3] shading fetches, [4..6] shadow rays/nodes/prims
     const uint64_t rays = ctr[0] + ctr[4];
     c->stats.rays = rays;
     c->stats.shadow_rays = ctr[4];
@@ -927,37 +807,105 @@ static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* s
     c->stats.rays_total += rays;
     c->stats.last_pass_ms = ms;
     c->stats.total_ms += ms;
-    c->stats.passes += (uint64_t)P.passes;
+    c->stats.passes += (uint64_t)passes;
     for (int k = 0; k < PT_K_SLOTS; k++) { c->stats.kernel_ms[k] = 0.0; c->stats.kernel_launches[k] = 0; }
     if (timing) PT_HIP(c->timer.collect(c->stats.kernel_ms, c->stats.kernel_launches));
-    if (counted) {
-        counted->rays = rays;
-        counted->nodes_visited = ctr[1] + ctr[5];
-        counted->prims_tested = ctr[2] + ctr[6];
-        counted->shading_fetches = ctr[3];
-        counted->shadow_rays = ctr[4];
-        counted->shadow_nodes = ctr[5];
-        counted->shadow_prims = ctr[6];
-        counted->lit_shadow_rays = ctr[7];
-        counted->accum_runs = ctr[8];
-        counted->volume_samples = ctr[9];
-        counted->sdf_evals = ctr[10];
-        for (int k = 0; k < 8; k++) {
-            counted->march_clock[k] = 0;
-            for (int j = 0; j < pt::kMarchSlots; j++) counted->march_clock[k] += ctr[pt::kMarchClockWord + 8 * j + k];
-        }
-    }
+    if (counted) read_trace_counters(ctr, counted);
     return PT_OK;
 }
 
+static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* sampler, const pt_pass_params* pass,
+                            const pt::PassKnobs& knobs, pt_trace_counters* counted);
+
+// A call's K passes that do not run as one batch (pt::PassPlan::split_step): one after another, or in sub-batches
+// of `step` passes, the stats summed.
+static int render_passes_split(Ctx* c, const pt_camera* camera, const pt_sampler* sampler, const pt_pass_params* pass,
+                               const pt::PassKnobs& knobs, int32_t step) {
+    pt_pass_params one = *pass;
+    pt_stats sum = c->stats;
+    uint64_t rays = 0, shadow = 0, handoffs = 0;
+    double ms = 0.0;
+    for (int32_t k = 0; k < pass->passes; k += step) {
+        one.pass_index = pass->pass_index + (uint32_t)k;
+        one.passes = std::min(step, pass->passes - k);
+        if (int rc = render_pass_impl(c, camera, sampler, &one, knobs, nullptr)) return rc;
+        rays += c->stats.rays;
+        shadow += c->stats.shadow_rays;
+        handoffs += c->stats.tail_handoffs;
+        ms += c->stats.last_pass_ms;
+        for (int j = 0; j < PT_K_SLOTS; j++) {
+            sum.kernel_ms[j] = (k ? sum.kernel_ms[j] : 0.0) + c->stats.kernel_ms[j];
+            sum.kernel_launches[j] = (k ? sum.kernel_launches[j] : 0) + c->stats.kernel_launches[j];
+        }
+    }
+    std::memcpy(c->stats.kernel_ms, sum.kernel_ms, sizeof sum.kernel_ms);
+    std::memcpy(c->stats.kernel_launches, sum.kernel_launches, sizeof sum.kernel_launches);
+    c->stats.rays = rays;
+    c->stats.shadow_rays = shadow;
+    c->stats.tail_handoffs = handoffs;
+    c->stats.last_pass_ms = ms;
+    return PT_OK;
+}
+
+// One pt_render_pass call: validate, tile list, plan (pt_pass_plan.h), batch split, queues and buffers, foreign
+// tiles, run, stats.
+static int render_pass_impl(Ctx* c, const pt_camera* camera, const pt_sampler* sampler, const pt_pass_params* pass,
+                            const pt::PassKnobs& knobs, pt_trace_counters* counted) {
+    if (!c || !camera || !sampler || !pass) return fail(PT_ERR_INVALID_ARG, "NULL argument");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "pt_render_pass before pt_upload_scene");
+    if (c->width <= 1 || c->height <= 1)   // Camera.CastRay divides by w - 1 and h - 1 (Camera.cs:101-102)
+        return fail(PT_ERR_INVALID_ARG, "a pass needs width and height > 1");
+    const int tiles_x = (c->width + 31) / 32, image_tiles = tiles_x * ((c->height + 31) / 32);
+    pt::PassPlanInput in;
+    in.width = c->width; in.height = c->height;
+    in.num_tiles = pass->num_tiles > 0 ? pass->num_tiles : image_tiles;
+    in.spp = pass->spp; in.stratified = pass->stratified; in.engine = pass->engine; in.flags = pass->flags;
+    in.adaptive_samples = pass->adaptive_samples; in.firefly_samples = pass->firefly_samples; in.passes = pass->passes;
+    in.first_hit_samples = sampler->first_hit_samples; in.max_bounces = sampler->max_bounces;
+    in.light_mode = sampler->light_mode; in.specular_mode = sampler->specular_mode;
+    in.num_lights = c->S.num_lights;
+    in.counted = counted != nullptr;
+    in.knobs = knobs;
+    // (plan_pass makes these checks first too; here they also come before the tile list's, as they always have)
+    pt::PassPlan plan = pt::check_pass_params(in);
+    if (plan.rc != PT_OK) return fail(plan.rc, plan.message);
+    PT_HIP(hipSetDevice(c->device));
+    const int32_t* d_tiles = nullptr;
+    if (int rc = upload_tile_list(c, pass, image_tiles, &d_tiles)) return rc;
+    in.wf_max_cap = wf_max_cap(c, knobs);
+    if (pass->passes > 1) in.batch_passes_max = batch_passes_max(c, knobs);
+    plan = pt::plan_pass(in);
+    if (plan.rc != PT_OK) return fail(plan.rc, plan.message);
+    if (plan.split_step > 0) return render_passes_split(c, camera, sampler, pass, knobs, plan.split_step);
+    PassRun r;
+    std::memcpy(r.cam.p, camera->p, sizeof r.cam.p); std::memcpy(r.cam.u, camera->u, sizeof r.cam.u);
+    std::memcpy(r.cam.v, camera->v, sizeof r.cam.v); std::memcpy(r.cam.w, camera->w, sizeof r.cam.w);
+    r.cam.m = camera->m; r.cam.focal_distance = camera->focal_distance; r.cam.aperture_radius = camera->aperture_radius;
+    r.smp = pt::DevSampler{sampler->first_hit_samples, sampler->max_bounces, sampler->direct_lighting, sampler->soft_shadows,
+                           sampler->light_mode, sampler->specular_mode};
+    r.P = pt::DevPass{c->width, c->height, pass->spp, pass->stratified, pass->seed, pass->pass_index, tiles_x, d_tiles,
+                      in.num_tiles};
+    r.P.passes = plan.passes_per_launch;
+    r.P.acc_stride = (uint32_t)((size_t)c->width * (size_t)c->height);
+    r.B = pt::DevBuffer{c->d_m, c->d_v, c->d_n, c->d_counters};
+    r.count = counted != nullptr;
+    r.tm = (pass->flags & PT_PASS_KERNEL_TIMING) ? &c->timer : nullptr;
+    if (plan.engine == PT_ENGINE_WAVEFRONT)
+        if (int rc = prepare_wavefront(c, pass, plan, knobs, r.wf)) return rc;
+    c->last_engine = plan.engine;
+    if (int rc = clear_foreign_tiles(c, pass, r.B, tiles_x, image_tiles)) return rc;
+    if (int rc = run_pass(c, pass, plan.engine, r)) return rc;
+    return collect_stats(c, plan.engine, r.P.passes, r.tm != nullptr, counted);
+}
+
 int pt_render_pass(void* ctx, const pt_camera* camera, const pt_sampler* sampler, const pt_pass_params* pass) {
-    return render_pass_impl((Ctx*)ctx, camera, sampler, pass, nullptr);
+    return render_pass_impl((Ctx*)ctx, camera, sampler, pass, read_pass_knobs(), nullptr);
 }
 
 int pt_render_pass_counted(void* ctx, const pt_camera* camera, const pt_sampler* sampler, const pt_pass_params* pass,
                            pt_trace_counters* out) {
     if (!out) return fail(PT_ERR_INVALID_ARG, "out is NULL");
-    return render_pass_impl((Ctx*)ctx, camera, sampler, pass, out);
+    return render_pass_impl((Ctx*)ctx, camera, sampler, pass, read_pass_knobs(), out);
 }
 
 int pt_synchronize(void* ctx) {

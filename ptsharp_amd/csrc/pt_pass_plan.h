@@ -1,0 +1,125 @@
+// pt_pass_plan.h — how a render pass runs, decided on the host before anything is allocated or launched
+// (pt_pass_plan.cpp): engine, chunk sizes, queue capacities, batch split, side stream.  Plain arithmetic over
+// plain values: no HIP header, no HIP call, no environment (pt_api.hip reads the switches into PassKnobs and
+// the device's memory into wf_max_cap / batch_passes_max), so tests/native/pass_plan_check.cpp drives it on
+// the CPU.  The deal functions below are shared with the device code (pt_wavefront.h includes this header).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/ptsharp_hip.h"
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define PT_PLAN_HD __host__ __device__
+#else
+#define PT_PLAN_HD
+#endif
+
+namespace pt {
+
+// Partitions of every wavefront queue, one per XCD group (pt_wavefront.h WfQueues).
+constexpr int kParts = 8;
+
+// k_wf_camera deals a chunk's camera samples to the partitions in runs of deal_run 256-sample
+// blocks, the runs round-robin (pt_wavefront.hip): one block (16 pixels' samples) per run.  Runs of
+// one 32x32 tile's samples, so that each XCD traces compact patches of the scene, measured slower
+// (C4 5899 → 5831 Mrays/s; profiles/r03e_ab_deal.txt).
+PT_PLAN_HD inline uint32_t deal_run(int32_t) { return 1u; }
+// Camera samples the fullest partition receives from a chunk of `samples`.
+PT_PLAN_HD inline uint64_t deal_group_max(uint64_t samples, int32_t spp_launch) {
+    const uint64_t run = deal_run(spp_launch), nblk = (samples + 255) / 256, nruns = (nblk + run - 1) / run;
+    return (nruns + kParts - 1) / kParts * run * 256;
+}
+
+// Queue capacity bound (entries per queue).  A pass is rendered in chunks of camera
+// samples whose widest depth fits the queues; every chunk pays the fill and drain of
+// 16 persistent launches, so fewer, larger chunks are faster (C4, 16 spp per pass: 8
+// chunks of 32M-entry queues 2574 Mrays/s, 2 chunks 2809, one chunk 2853).  The bound is
+// the largest power of two in [2^20, 2^29] whose queues, at kWfBytesPerEntry, fit the budget: half of the
+// device's memory and half of what is free at the context's first pass (2^29: 123 GB of the MI355X's 288 GB:
+// C2's 33M camera samples × 16 children in one chunk).  kWfBytesPerEntry, 229 B, counts what every scene
+// allocates per entry (pt_api.hip ensure_wavefront): two extension queues of o, d, throughput r g,
+// key + throughput b (2 × 64 B), the hits (16 B), one shadow set (o, n, two weights, lit: 65 B) and the head
+// pass' two lists (4 B per extension ray, 16 B per shadow ray).  Not counted, so on top of the budget:
+//   * the second shadow set of a context that has run a side-stream pass (65 B per shadow entry; it stays
+//     allocated for the context's later passes);
+//   * for row-4 scenes only (counted in, they halved C4-sized queues from 2^28 to 2^27 entries and split the
+//     pass in two chunks, -3 %): the two deferred-record queues of a scene with SDF shapes or Volumes (sdfq,
+//     sdfq_sh: 32 B per entry), with Volumes their record words (volq, volq_sh: 8 B), and under the routed
+//     split the heavy queues (hq, hq_sh: 8 B): at most 48 B per entry, 25.8 GB at 2^29 entries;
+//   * the per-pixel accumulators (72 B per pixel and pass of a batch, batch_passes_for) and the adaptive /
+//     firefly phases' per-sample accumulators (72 B per camera sample of chunk_extra).
+// All of it comes out of the half of the device the budget leaves free.
+constexpr uint32_t kWfMinCapLimit = 1u << 20, kWfMaxCapLimit = 1u << 29;
+constexpr size_t kWfBytesPerEntry = 2 * (16 + 16 + 16 + 16) + 16 + (64 + 1) + (4 + 16);
+uint32_t wf_cap_for_budget(size_t budget_bytes);
+// PT_WF_MAX_CAP (entries; tests use it to force many chunks): the largest power of two up to it, at least one
+// 1024-entry block per partition.
+uint32_t wf_cap_for_limit(unsigned long long entries);
+
+// Passes one batch may hold: its accumulator sets (bytes_per_pass each) within an eighth of the device's
+// memory; knob_max_passes (PassKnobs::batch_max_passes, 0: none) lowers it.
+int32_t batch_passes_for(size_t total_bytes, size_t bytes_per_pass, int64_t knob_max_passes);
+
+#ifndef PT_EXTRA_CHUNK_MAX
+#define PT_EXTRA_CHUNK_MAX (64ull << 20)   // camera samples per chunk of the adaptive / firefly phases, at most (round 6: 32M → 64M with the 2^29-entry queues, C5 +1.8 %, profiles/r06ec_ab_extra_chunk.txt)
+#endif
+constexpr double kSideStreamMaxRays = (double)(64ull << 20);   // a chunk's widest depth, extension rays
+
+// The debug / test switches of a pass, as pt_api.hip read_pass_knobs() finds them in the environment at each
+// pt_render_pass call (tests flip them between the passes of one process).
+struct PassKnobs {
+    int32_t shade_form = 0;     // PT_SHADE_FORM=direct|scan: 1, 2; else 0, chosen per depth from the kept count
+    int32_t lanes = -1;         // PT_LANES=0|1: refill traversal kernels never / always; else -1, by BVH size
+    int32_t head = 1;           // PT_HEAD=0: no head pass and list-fed refill kernels; else 1, where they apply
+    int32_t head_stats = 0;     // PT_HEAD_STATS=1: the lists' counts per depth to stderr (it synchronizes)
+    int32_t linear = -1;        // PT_LINEAR=0: no linear kernels; else -1, where they apply
+    int32_t side_stream = -1;   // PT_SIDE_STREAM=0|1: one stream / the side stream; else -1, by the chunk's rays
+    int32_t tail_early = 0;     // PT_SHADOW_TAIL=early: 1 (WfQueues::tail_early)
+    int64_t batch_max_passes = 0;          // PT_BATCH_MAX_PASSES: its value, at least 1; 0: not set
+    bool wf_max_cap_set = false;           // PT_WF_MAX_CAP is set, to
+    unsigned long long wf_max_cap = 0;     // this many entries (read once per context: wf_max_cap() in pt_api.hip)
+};
+
+struct PassPlanInput {
+    int32_t width = 0, height = 0;   // the image
+    int32_t num_tiles = 0;           // 32x32 tiles of this pass: its tile list's, or all of the image's
+    // pt_pass_params
+    int32_t spp = 0, stratified = 0, engine = 0, flags = 0, adaptive_samples = 0, firefly_samples = 0, passes = 0;
+    // pt_sampler
+    int32_t first_hit_samples = 0, max_bounces = 0, light_mode = 0, specular_mode = 0;
+    int32_t num_lights = 0;          // of the uploaded scene (LightModeAll: shadow-ray slots per child)
+    bool counted = false;            // pt_render_pass_counted
+    uint32_t wf_max_cap = 0;         // queue capacity bound of the context (wf_cap_for_budget / wf_cap_for_limit)
+    int32_t batch_passes_max = 1;    // batch_passes_for; read only when passes > 1
+    PassKnobs knobs;
+};
+
+struct PassPlan {
+    int rc = PT_OK;                  // a pt_status; when not PT_OK the pass is refused with `message` and
+    const char* message = "";        // no other field means anything
+    int32_t engine = 0;              // PT_ENGINE_WAVEFRONT or PT_ENGINE_MEGAKERNEL
+    uint64_t chunk = 0;              // camera samples per chunk
+    uint64_t chunk_extra = 0;        // camera samples per chunk of the adaptive / firefly phases (>= chunk: their
+                                     // queues and per-sample accumulators are sized for it)
+    uint32_t root_children = 0;      // ⌊√FH⌋² · modes at depth 0
+    uint32_t children = 0;           // modes at depth >= 1 (1, or 2 under SpecularModeAll)
+    uint32_t lights_per_child = 0;   // shadow-ray slots per diffuse child: 1, or #lights under LightModeAll
+    int32_t passes_per_launch = 1;   // > 1: the call's K passes as one batch (one launch sequence, one accumulator
+                                     // set per pass)
+    // > 0: the call's K passes do not run as one batch but as consecutive calls of split_step passes each (1: pass
+    // by pass; more: sub-batches); each of those is planned again: passes_per_launch then means nothing, and cap,
+    // scap and use_side below stay unset
+    int32_t split_step = 0;
+    uint32_t cap = 0, scap = 0;      // wavefront engine: entries of a ray queue and of a shadow-ray set
+    bool use_side = false;           // wavefront engine: shadow passes on the side stream
+};
+
+// The checks of a pass' parameters that come before anything else is looked at (plan_pass makes them first; a
+// caller with refusals of its own in between calls this ahead of them to keep their order).
+PassPlan check_pass_params(const PassPlanInput& in);
+
+// Never fails otherwise than by a refusal in the result; every input is allowed.
+PassPlan plan_pass(const PassPlanInput& in);
+
+}  // namespace pt

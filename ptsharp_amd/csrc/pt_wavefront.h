@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "pt_accum.h"
+#include "pt_pass_plan.h"
 #include "pt_scene.h"
 
 namespace pt {
@@ -14,8 +15,7 @@ namespace pt {
 // its L2): group g consumes partition g and appends the children and NEE
 // requests it makes to partition g of the next queues, so each XCD's L2 keeps
 // working on one region of the image at every depth, and the reservation
-// atomics spread over kParts counter words.
-constexpr int kParts = 8;
+// atomics spread over kParts counter words (kParts: pt_pass_plan.h, with the camera samples' deal).
 constexpr uint32_t kNoRecord = 0xFFFFFFFFu;
 struct WfQueues {
     float4* q_o[2];      // {origin.xyz, pixel}
@@ -113,43 +113,30 @@ constexpr int list_sh_fetch_word(int q, int g) { return count_word(kListShFetchS
 #endif
 constexpr int kLdsStack = PT_LDS_STACK;          // LDS stack entries per lane (traversal kernels)
 constexpr uint32_t kWfMaxBlocks = 256 * 8;        // grid cap of the traversal kernels
-
-// k_wf_camera deals a chunk's camera samples to the partitions in runs of deal_run 256-sample
-// blocks, the runs round-robin (pt_wavefront.hip): one block (16 pixels' samples) per run.  Runs of
-// one 32x32 tile's samples, so that each XCD traces compact patches of the scene, measured slower
-// (C4 5899 → 5831 Mrays/s; profiles/r03e_ab_deal.txt).
-__host__ __device__ inline uint32_t deal_run(int32_t) { return 1u; }
-// Camera samples the fullest partition receives from a chunk of `samples`.
-__host__ __device__ inline uint64_t deal_group_max(uint64_t samples, int32_t spp_launch) {
-    const uint64_t run = deal_run(spp_launch), nblk = (samples + 255) / 256, nruns = (nblk + run - 1) / run;
-    return (nruns + kParts - 1) / kParts * run * 256;
-}
 constexpr uint32_t kWfMaxThreads = kWfMaxBlocks * 256;
 
-struct WfPlan {
-    uint64_t chunk;            // camera samples per chunk
-    uint64_t chunk_extra;      // camera samples per chunk of the adaptive / firefly phases (>= chunk: their
-                               // queues and per-sample accumulators are sized for it)
-    uint32_t root_children;    // ⌊√FH⌋² · modes at depth 0
-    uint32_t children;         // modes at depth >= 1 (1, or 2 under SpecularModeAll)
-    uint32_t lights_per_child; // shadow-ray slots per diffuse child: 1, or #lights under LightModeAll
-    uint32_t trace_blocks;     // persistent grids: resident capacity of each kernel (lockstep traversal,
-    uint32_t shade_blocks;     // shade, lockstep shadow; the refill and FULL traversal kernels below)
+// Persistent grids: the resident capacity of each kernel on this device (wavefront_grids, once per context).
+struct WfGrids {
+    uint32_t trace_blocks;     // lockstep traversal,
+    uint32_t shade_blocks;     // shade, lockstep shadow; the refill and FULL traversal kernels below
     uint32_t shadow_blocks;
     uint32_t lanes_trace_blocks, lanes_shadow_blocks, full_trace_blocks, full_shadow_blocks;
-    uint32_t linear_trace_blocks, linear_shadow_blocks;   // k_wf_trace_linear / k_wf_shadow_linear (resident)
-    uint32_t head_trace_blocks, head_shadow_blocks;       // k_wf_trace_head / k_wf_shadow_head (resident)
-    uint32_t list_trace_blocks, list_shadow_blocks;       // the list-fed forms of the refill kernels (resident)
-    int32_t shade_form;        // k_wf_shade form: 0 chosen per depth from the kept count, 1 direct, 2 SCAN
-                               // (PT_SHADE_FORM=direct|scan in the environment; tests)
-    int32_t lanes;             // refill traversal kernels: -1 by BVH size, 0 never, 1 always
-                               // (PT_LANES=0|1 in the environment; tests)
-    int32_t head;              // head pass + list-fed refill kernels where they apply (unsplit refill kernels, a
-                               // triangles-only step loop): 1, or 0 never (PT_HEAD=0 in the environment; tests, A/B)
-    int32_t head_stats;        // PT_HEAD_STATS=1: the lists' counts per depth to stderr (a diagnostic: it synchronizes)
-    int32_t linear;            // linear kernels (few analytic records, no triangles): -1 where they apply, 0 never
-                               // (PT_LINEAR=0 in the environment; tests)
-    // Optional second stream: each depth's shadow pass runs there, beside the next depth's
+    uint32_t linear_trace_blocks, linear_shadow_blocks;   // k_wf_trace_linear / k_wf_shadow_linear
+    uint32_t head_trace_blocks, head_shadow_blocks;       // k_wf_trace_head / k_wf_shadow_head
+    uint32_t list_trace_blocks, list_shadow_blocks;       // the list-fed forms of the refill kernels
+    // a zero grid: a kernel whose occupancy query was never made
+    bool complete() const {
+        return trace_blocks && shade_blocks && shadow_blocks && lanes_trace_blocks && lanes_shadow_blocks && full_trace_blocks &&
+               full_shadow_blocks && linear_trace_blocks && linear_shadow_blocks && head_trace_blocks && head_shadow_blocks &&
+               list_trace_blocks && list_shadow_blocks;
+    }
+};
+
+// One pass on the wavefront engine, as its launches take it: the context's grids, the host's plan (chunk,
+// chunk_extra, the children per sample) and the switches that choose kernels (shade_form, lanes, head, head_stats,
+// linear), all by value (pt_pass_plan.h), and the side stream's handles.
+struct WfPlan : WfGrids, PassPlan, PassKnobs {
+    // Optional second stream (PassPlan::use_side): each depth's shadow pass runs there, beside the next depth's
     // closest-hit pass (independent queues), so one fills the other's ramp and tail.
     // ev_main orders shade(d) → shadow(d); ev_side[q], recorded after the light terms of
     // shadow set q were added, orders them before shade(d + 2) rewrites set q.  Null: one stream.
@@ -183,7 +170,7 @@ hipError_t wavefront_extra(const DevScene& S, const DevCamera& cam, const DevSam
                            const uint32_t* plist, const double* snap, uint32_t* next_list, uint32_t* next_count);
 
 // Persistent grid sizes (resident capacity on this device) of the traversal / shade kernels.
-hipError_t wavefront_grids(WfPlan& plan);
+hipError_t wavefront_grids(WfGrids& grids);
 
 // Pixels of the pass whose StandardDeviation().MaxComponent() exceeds 1 (kind 0: the firefly
 // candidates, Renderer.cs:179,426) or is at least 1 (kind 1: Render's adaptive branch, where
