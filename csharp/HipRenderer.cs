@@ -181,6 +181,18 @@ namespace PTSharpCore
             public IntPtr v1, v2, v3, n1, n2, n3, t1, t2, t3;   // [n][3] float, owned by the library
         }
 
+        [StructLayout(LayoutKind.Sequential)]
+        public struct pt_shape_update
+        {
+            public int num_spheres, num_cubes, num_transformed, reserved;   // reserved = 0
+            public IntPtr sphere_center;   // [num_spheres][3] float; null = spheres stay
+            public IntPtr sphere_radius;   // [num_spheres] double;   null = radii stay
+            public IntPtr cube_min;        // [num_cubes][3] float;   both or neither
+            public IntPtr cube_max;
+            public IntPtr xform_matrix;    // [num_transformed][16] double, row-major; both or neither
+            public IntPtr xform_inverse;
+        }
+
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_get_version();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_device_count(out int count);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_create(ref pt_device_opts opts, out IntPtr ctx);
@@ -211,6 +223,9 @@ namespace PTSharpCore
         public const int PT_NORMALS_FACE = 1, PT_NORMALS_SMOOTH = 2;   // pt_normals_mode
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_triangles_normals(IntPtr ctx, int numTriangles, float[] v1, float[] v2, float[] v3, int mode, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tri_normals(IntPtr ctx, float[] n1, float[] n2, float[] n3);
+        // new sphere, cube and TransformedShape parameters: the analytic BVH refitted on the device
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_shapes(IntPtr ctx, ref pt_shape_update u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_shape_bvh(IntPtr ctx, long[] counts, uint[] nodes, uint[] recs, uint[] heavy, double[] lights);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr pt_last_error();
@@ -650,6 +665,44 @@ namespace PTSharpCore
             var box = new float[6];
             PtHip.Check(PtHip.pt_read_tri_bvh(ctx, counts, nodes, chunks, records, box), "pt_read_tri_bvh");
             return (nodes, chunks, records, box);
+        }
+
+        /// <summary>New parameters for the spheres, cubes and transformed shapes of the uploaded scene, in the
+        /// upload's order (pt_update_shapes): centres [n * 3] with optional radii [n], cube corners [n * 3] each,
+        /// matrices and inverses [n * 16] row-major; a null group stays.  The analytic BVH is refitted on the
+        /// device, nothing is rebuilt.  The caller keeps its own scene in step.  Returns the device time of the
+        /// kernels in ms.</summary>
+        public double UpdateShapes(float[] sphereCenter = null, double[] sphereRadius = null, float[] cubeMin = null,
+                                   float[] cubeMax = null, double[] matrices = null, double[] inverses = null)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            IntPtr PinHeld(Array a)
+            {
+                if (a == null) return IntPtr.Zero;
+                var h = GCHandle.Alloc(a, GCHandleType.Pinned);
+                held.Add(h);
+                return h.AddrOfPinnedObject();
+            }
+            try
+            {
+                var u = new PtHip.pt_shape_update
+                {
+                    num_spheres = sphereCenter == null ? 0 : sphereCenter.Length / 3,
+                    num_cubes = cubeMin == null ? 0 : cubeMin.Length / 3,
+                    num_transformed = matrices == null ? 0 : matrices.Length / 16,
+                    reserved = 0,
+                    sphere_center = PinHeld(sphereCenter), sphere_radius = PinHeld(sphereRadius),
+                    cube_min = PinHeld(cubeMin), cube_max = PinHeld(cubeMax),
+                    xform_matrix = PinHeld(matrices), xform_inverse = PinHeld(inverses),
+                };
+                PtHip.Check(PtHip.pt_update_shapes(ctx, ref u, out double ms), "pt_update_shapes");
+                return ms;
+            }
+            finally
+            {
+                foreach (var h in held) h.Free();
+            }
         }
 
         /// <summary>The first-hit features of the whole frame (pt_render_features): one ray through each

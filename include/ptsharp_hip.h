@@ -18,6 +18,8 @@
  *   / pt_read_tri_bvh  the triangle BVH refitted on the device, no rebuild  scene for every frame of its loop
  *   pt_update_triangles_normals  the same with the normals derived on the   Triangle.FixNormals, Mesh.SmoothNormals
  *   / pt_read_tri_normals        device: face or smooth                     Triangle.cs:224-237, Mesh.cs:191-229
+ *   pt_update_shapes   (new) new sphere, cube and TransformedShape          Example.cs:163-223 ("beads"): that loop
+ *   / pt_read_shape_bvh parameters: the analytic BVH refitted on the device  moves 31,920 spheres, and no triangle
  *   pt_render_pass     one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
@@ -511,7 +513,9 @@ int pt_tile_lists_check(const int32_t* ids, int64_t n, int32_t image_tiles);
  *                 pt_shape_kind (a mesh triangle is PT_SHAPE_TRIANGLE) or -1.
  *   pt_occluded   the shadow query after the light's own t (Sampler.cs:261-265 as the wavefront engine
  *                 answers it): out_blocked[i] = 1 if some shape is hit strictly nearer
- *                 than t_max[i].
+ *                 than t_max[i].  Its walk of the analytic BVH does not cull boxes against t_max: a hit
+ *                 distance carries the rounding of the shape's fp32 intersection and can fall short of
+ *                 the entry distance of the shape's own box; a render's shadow rays cull.
  * flags choose how a ray's Volume (Volume.Intersect, Volume.cs:168-197) is marched; every choice
  * returns the same bits, which is what the flags are for: 0 as in a render (a wave's lanes march
  * together unless fewer than 8 are active), PT_MARCH_LANE every lane its own march, PT_MARCH_WAVE
@@ -578,6 +582,40 @@ int pt_update_triangles_normals(void* ctx, int32_t num_triangles,
  * in no shape of the scene has none: zeros).  Valid any time after an upload; synchronises and changes nothing.
  * A NULL ctx or output: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3);
+
+/* New parameters for the spheres, cubes and transformed shapes of the uploaded scene: a
+ * sphere's centre and radius, a cube's corners, the matrix of a pt_transformed_shape (an instanced mesh
+ * included: the instance moves rigidly, its BLAS stays).  A group is given when its first pointer is non-NULL;
+ * a given group's count must equal the uploaded scene's; arrays are in pt_scene_desc order and are copied during
+ * the call.  The analytic BVH is refitted on the device with its topology kept: afterwards every ray query,
+ * feature pass and render pass sees the scene a fresh pt_upload_scene of the same pt_scene_desc with these
+ * arrays substituted would see, up to the exact-t tie order of DESIGN.md §5.  Records, ext records,
+ * transforms, the boxes the routed split tests and the lights that are spheres, cubes or transformed shapes
+ * follow.  The triangle BVH, BLASes, materials, textures, SDF programs, volumes, planes, the Buffer, the pass
+ * state and the counters are untouched.  Runs on the context's stream after every pass issued before it and
+ * synchronises before returning; out_kernel_ms (may be NULL) is the device time of its kernels.  It composes
+ * with pt_update_triangles in either order.  Non-finite values: what they do to the boxes is unspecified; no
+ * access leaves its array.
+ * Errors (nothing launched, the scene untouched): a NULL ctx or u, reserved != 0, cube_min / cube_max or
+ * xform_matrix / xform_inverse half given, sphere_radius without sphere_center, a given group's count
+ * different from the scene's: PT_ERR_INVALID_ARG (the values themselves are checked as pt_upload_scene checks
+ * them: not at all); no scene: PT_ERR_NO_SCENE; the workspace (kept until the next upload) not allocated:
+ * PT_ERR_OUT_OF_MEMORY.  No group given, or a scene without analytic records: PT_OK, nothing launched. */
+typedef struct pt_shape_update {
+    int32_t num_spheres, num_cubes, num_transformed, reserved;   /* reserved = 0 */
+    const float*  sphere_center;   /* [num_spheres][3]; NULL = spheres stay */
+    const double* sphere_radius;   /* [num_spheres];    NULL = radii stay   */
+    const float*  cube_min;        /* [num_cubes][3];   both or neither     */
+    const float*  cube_max;
+    const double* xform_matrix;    /* [num_transformed][16] row-major; both or neither */
+    const double* xform_inverse;
+} pt_shape_update;
+int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms);
+/* The context's analytic BVH as it stands on the device (tests and tools): counts[0..3] = BVH4 nodes, analytic
+ * records, heavy records, lights; each non-NULL array receives 32 words per node, 12 words per record, 8 words
+ * per heavy record, 4 doubles per light (centre x, y, z widened to double, then the radius).  Any argument but
+ * ctx may be NULL.  Synchronises and changes nothing. */
+int pt_read_shape_bvh(void* ctx, int64_t counts[4], uint32_t* nodes, uint32_t* recs, uint32_t* heavy, double* lights);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

@@ -136,6 +136,12 @@ class pt_denoise_guided_params(C.Structure):
                 ("sigma_normal", C.c_double), ("sigma_albedo", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class pt_shape_update(C.Structure):
+    _fields_ = [("num_spheres", C.c_int32), ("num_cubes", C.c_int32), ("num_transformed", C.c_int32),
+                ("reserved", C.c_int32), ("sphere_center", _f), ("sphere_radius", _d), ("cube_min", _f),
+                ("cube_max", _f), ("xform_matrix", _d), ("xform_inverse", _d)]
+
+
 class pt_trace_counters(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
                 ("shading_fetches", C.c_uint64), ("shadow_rays", C.c_uint64), ("shadow_nodes", C.c_uint64),
@@ -162,6 +168,9 @@ SIGNATURES = {
     "pt_read_tri_normals": (C.c_int, [C.c_void_p, _f, _f, _f]),
     "pt_read_tri_bvh": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32), _f]),
+    "pt_update_shapes": (C.c_int, [C.c_void_p, C.POINTER(pt_shape_update), _d]),
+    "pt_read_shape_bvh": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32), _d]),
     "pt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_sampler), C.POINTER(pt_pass_params)]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_reset_buffer": (C.c_int, [C.c_void_p]),

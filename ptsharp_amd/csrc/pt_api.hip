@@ -29,6 +29,7 @@
 #include "pt_pass_plan.h"
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
+#include "pt_shape_refit.h"
 #include "pt_wavefront.h"
 
 #pragma clang fp contract(off)
@@ -98,6 +99,12 @@ hipError_t launch_refit(int64_t num_chunks, int64_t num_levels, const uint32_t* 
                         uint32_t* nodes, uint32_t* chunks, uint32_t* recs, const int32_t* src_of_pos, const float* v1,
                         const float* v2, const float* v3, const float* n1, const float* n2, const float* n3,
                         float* node_box, float* chunk_box, hipStream_t stream);
+// pt_shape_refit.hip
+hipError_t launch_shape_refit(const ShapeParams& P, int64_t num_nodes, int64_t num_recs, int64_t num_heavy, int64_t num_levels,
+                              const uint32_t* level_off, const uint32_t* level_nodes, uint32_t* nodes, uint32_t* recs,
+                              uint32_t* ext_recs, DevXform* xforms, uint32_t* heavy, const int32_t* inner_kind,
+                              const int32_t* inner_index, const float* inner_box, float* xbox, float* rec_box, float* node_box,
+                              hipStream_t stream);
 // pt_normals.hip
 hipError_t normals_sort_temp_bytes(int64_t corners, int32_t num_groups, size_t* out);
 hipError_t launch_normals(bool smooth, int64_t n, const float* v1, const float* v2, const float* v3, float* n1, float* n2,
@@ -235,6 +242,11 @@ struct Ctx {
     // sort's temporary, one allocation that comes with the first such call and goes with the scene
     DeviceArray normals_dev;
     size_t normals_temp_bytes = 0;
+    // pt_update_shapes: the host tables of the last upload with the parameters the device holds now; the device side
+    // (one allocation: the staged parameters, a box per transformed shape, record and node, the level list and the
+    // static tables) comes with the first update
+    pt::ShapeRefitTables shape_refit;
+    DeviceArray shapes_dev;
 };
 
 #ifndef PT_VOL_DEFER
@@ -409,6 +421,8 @@ void free_scene(Ctx* c) {
     c->refit_dev.release();
     c->normals_dev.release();
     c->normals_temp_bytes = 0;
+    c->shapes_dev.release();
+    c->shape_refit = pt::ShapeRefitTables{};
     c->refit = pt::RefitTables{};
     c->h_lights.clear();
     c->has_blas = false;
@@ -572,6 +586,7 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     c->S = S;
     c->has_scene = true;
     c->refit = std::move(H.refit);
+    c->shape_refit = std::move(H.shape_refit);
     c->h_lights = std::move(H.lights);
     c->has_blas = !H.blas.empty();
     c->stats.bvh_nodes = H.bvh_nodes;
@@ -1437,6 +1452,170 @@ int pt_read_tri_bvh(void* ctx, int64_t counts[3], uint32_t* nodes, uint32_t* chu
     if (records && !T.src_of_pos.empty())
         PT_HIP(hipMemcpyAsync(records, c->S.tri_recs, T.src_of_pos.size() * line, hipMemcpyDeviceToHost, c->stream));
     PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// ---- moving spheres, cubes and transformed shapes
+namespace {
+// The parts of Ctx::shapes_dev, each 256-B aligned: [the staged parameters | xbox | rec_box | node_box | level_nodes |
+// the transformed shapes' inner kind, index and box]
+struct ShapesDev {
+    float* sphere_center;
+    double* sphere_radius;
+    float* cube_min;
+    float* cube_max;
+    double* xf_matrix;
+    double* xf_inverse;
+    float* xbox;
+    float* rec_box;
+    float* node_box;
+    uint32_t* level_nodes;
+    int32_t* xf_kind;
+    int32_t* xf_index;
+    float* xf_inner_box;
+    size_t bytes;
+};
+ShapesDev shapes_layout(const pt::ShapeRefitTables& T, void* base) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    ShapesDev r{};
+    size_t at = 0;
+    char* p = (char*)base;
+    const size_t ns = (size_t)T.num_spheres, nc = (size_t)T.num_cubes, nx = (size_t)T.num_transformed;
+    r.sphere_center = (float*)(p + at); at += up(ns * 3 * sizeof(float));
+    r.sphere_radius = (double*)(p + at); at += up(ns * sizeof(double));
+    r.cube_min = (float*)(p + at); at += up(nc * 3 * sizeof(float));
+    r.cube_max = (float*)(p + at); at += up(nc * 3 * sizeof(float));
+    r.xf_matrix = (double*)(p + at); at += up(nx * 16 * sizeof(double));
+    r.xf_inverse = (double*)(p + at); at += up(nx * 16 * sizeof(double));
+    r.xbox = (float*)(p + at); at += up(nx * 6 * sizeof(float));
+    r.rec_box = (float*)(p + at); at += up((size_t)T.num_recs * 6 * sizeof(float));
+    r.node_box = (float*)(p + at); at += up((size_t)T.num_nodes * 6 * sizeof(float));
+    r.level_nodes = (uint32_t*)(p + at); at += up(T.level_nodes.size() * sizeof(uint32_t));
+    r.xf_kind = (int32_t*)(p + at); at += up(nx * sizeof(int32_t));
+    r.xf_index = (int32_t*)(p + at); at += up(nx * sizeof(int32_t));
+    r.xf_inner_box = (float*)(p + at); at += up(nx * 6 * sizeof(float));
+    r.bytes = at + 256;   // never an empty allocation
+    return r;
+}
+hipError_t shapes_copy_bytes(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    if (!bytes) return hipSuccess;
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+}
+#define shapes_copy(dst, vec, s) shapes_copy_bytes((dst), (vec).data(), (vec).size() * sizeof((vec)[0]), (s))
+// Ctx::shapes_dev, allocated and its tables uploaded (on the context's stream) at the first use after an upload
+int ensure_shapes_dev(Ctx* c, ShapesDev& D) {
+    const pt::ShapeRefitTables& T = c->shape_refit;
+    D = shapes_layout(T, nullptr);
+    const bool first = !c->shapes_dev.ptr;
+    if (first) {
+        if (hipMalloc(&c->shapes_dev.ptr, D.bytes) != hipSuccess) {
+            c->shapes_dev.ptr = nullptr;
+            (void)hipGetLastError();
+            return fail(PT_ERR_OUT_OF_MEMORY, "shape refit workspace allocation");
+        }
+        c->shapes_dev.bytes = D.bytes;
+    }
+    D = shapes_layout(T, c->shapes_dev.ptr);
+    if (first) {
+        PT_HIP(shapes_copy(D.level_nodes, T.level_nodes, c->stream));
+        PT_HIP(shapes_copy(D.xf_kind, T.xf_kind, c->stream));
+        PT_HIP(shapes_copy(D.xf_index, T.xf_index, c->stream));
+        PT_HIP(shapes_copy(D.xf_inner_box, T.xf_inner_box, c->stream));
+        PT_HIP(shapes_copy(D.rec_box, T.rec_box, c->stream));   // top-level SDF and Volume records keep these
+    }
+    return PT_OK;
+}
+}  // namespace
+
+int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!u) return fail(PT_ERR_INVALID_ARG, "update shapes: u is NULL");
+    if (u->reserved != 0) return fail(PT_ERR_INVALID_ARG, "update shapes: reserved must be 0");
+    if ((u->cube_min != nullptr) != (u->cube_max != nullptr))
+        return fail(PT_ERR_INVALID_ARG, "update shapes: cube_min and cube_max must be both set or both NULL");
+    if ((u->xform_matrix != nullptr) != (u->xform_inverse != nullptr))
+        return fail(PT_ERR_INVALID_ARG, "update shapes: xform_matrix and xform_inverse must be both set or both NULL");
+    if (u->sphere_radius && !u->sphere_center)
+        return fail(PT_ERR_INVALID_ARG, "update shapes: sphere_radius needs sphere_center");
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    pt::ShapeRefitTables& T = c->shape_refit;
+    auto count_is = [&](const char* what, int32_t given, int32_t have) -> int {
+        if (given == have) return PT_OK;
+        return fail(PT_ERR_INVALID_ARG, std::string("update shapes: ") + what + " is " + std::to_string(given) +
+                                            ", the uploaded scene has " + std::to_string(have));
+    };
+    if (u->sphere_center) if (const int rc = count_is("num_spheres", u->num_spheres, T.num_spheres)) return rc;
+    if (u->cube_min) if (const int rc = count_is("num_cubes", u->num_cubes, T.num_cubes)) return rc;
+    if (u->xform_matrix) if (const int rc = count_is("num_transformed", u->num_transformed, T.num_transformed)) return rc;
+    // (pt_upload_scene's validate_scene checks no sphere, cube or matrix value: nor does an update)
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if ((!u->sphere_center && !u->cube_min && !u->xform_matrix) || T.num_recs == 0) return PT_OK;
+    PT_HIP(hipSetDevice(c->device));
+    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
+    ShapesDev D{};
+    if (const int rc = ensure_shapes_dev(c, D)) return rc;   // before the first change: a failed allocation leaves the scene untouched
+    // the given groups into the current parameters
+    if (u->sphere_center) T.sphere_center.assign(u->sphere_center, u->sphere_center + 3 * (size_t)T.num_spheres);
+    if (u->sphere_radius) T.sphere_radius.assign(u->sphere_radius, u->sphere_radius + (size_t)T.num_spheres);
+    if (u->cube_min) {
+        T.cube_min.assign(u->cube_min, u->cube_min + 3 * (size_t)T.num_cubes);
+        T.cube_max.assign(u->cube_max, u->cube_max + 3 * (size_t)T.num_cubes);
+    }
+    if (u->xform_matrix) {
+        T.xf_matrix.assign(u->xform_matrix, u->xform_matrix + 16 * (size_t)T.num_transformed);
+        T.xf_inverse.assign(u->xform_inverse, u->xform_inverse + 16 * (size_t)T.num_transformed);
+    }
+    PT_HIP(shapes_copy(D.sphere_center, T.sphere_center, c->stream));
+    PT_HIP(shapes_copy(D.sphere_radius, T.sphere_radius, c->stream));
+    PT_HIP(shapes_copy(D.cube_min, T.cube_min, c->stream));
+    PT_HIP(shapes_copy(D.cube_max, T.cube_max, c->stream));
+    PT_HIP(shapes_copy(D.xf_matrix, T.xf_matrix, c->stream));
+    PT_HIP(shapes_copy(D.xf_inverse, T.xf_inverse, c->stream));
+    const pt::ShapeParams P{T.num_spheres, T.num_cubes, T.num_transformed, D.sphere_center, D.sphere_radius,
+                            D.cube_min, D.cube_max, D.xf_matrix, D.xf_inverse};
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_shape_refit(P, T.num_nodes, T.num_recs, T.num_heavy, (int64_t)T.level_off.size() - 1, T.level_off.data(),
+                                  D.level_nodes, (uint32_t*)const_cast<float4*>(c->S.ana_nodes),
+                                  (uint32_t*)const_cast<float4*>(c->S.ana_recs), (uint32_t*)const_cast<float4*>(c->S.ext_recs),
+                                  const_cast<pt::DevXform*>(c->S.xforms), (uint32_t*)const_cast<float4*>(c->S.heavy), D.xf_kind,
+                                  D.xf_index, D.xf_inner_box, D.xbox, D.rec_box, D.node_box, c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    // lights that are spheres, cubes or transformed shapes: their sphere from the new parameters
+    if (pt::shape_refit_lights(T, c->h_lights))
+        PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
+                              hipMemcpyHostToDevice, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    if (out_kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *out_kernel_ms = ms;
+    }
+    return PT_OK;
+}
+
+int pt_read_shape_bvh(void* ctx, int64_t counts[4], uint32_t* nodes, uint32_t* recs, uint32_t* heavy, double* lights) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::ShapeRefitTables& T = c->shape_refit;
+    const size_t nl = c->h_lights.size();
+    if (counts) { counts[0] = T.num_nodes; counts[1] = T.num_recs; counts[2] = T.num_heavy; counts[3] = (int64_t)nl; }
+    PT_HIP(hipSetDevice(c->device));
+    const size_t word = sizeof(uint32_t);
+    if (nodes && T.num_nodes)
+        PT_HIP(hipMemcpyAsync(nodes, c->S.ana_nodes, (size_t)T.num_nodes * pt::kShapeNodeWords * word, hipMemcpyDeviceToHost, c->stream));
+    if (recs && T.num_recs)
+        PT_HIP(hipMemcpyAsync(recs, c->S.ana_recs, (size_t)T.num_recs * pt::kShapeRecWords * word, hipMemcpyDeviceToHost, c->stream));
+    if (heavy && T.num_heavy)
+        PT_HIP(hipMemcpyAsync(heavy, c->S.heavy, (size_t)T.num_heavy * pt::kShapeHeavyWords * word, hipMemcpyDeviceToHost, c->stream));
+    std::vector<pt::DevLight> dl(lights ? nl : 0);   // what the device holds, not the host's copy
+    if (!dl.empty()) PT_HIP(hipMemcpyAsync(dl.data(), c->S.lights, nl * sizeof(pt::DevLight), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < dl.size(); i++) {
+        for (int k = 0; k < 3; k++) lights[4 * i + k] = (double)dl[i].center[k];
+        lights[4 * i + 3] = dl[i].radius;
+    }
     return PT_OK;
 }
 

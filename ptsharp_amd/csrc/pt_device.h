@@ -323,15 +323,18 @@ __device__ __forceinline__ void sdf_pending(const DevScene& S, v3 o, v3 d, int32
 // ANY: stop at the first primitive with t < best.t (shadow visibility).
 // pend (FULL, analytic BVH): the first Volume record reached is not marched here but left in
 // *pend for the wave's cooperative march after the traversal (march_pending).
+// far_cull = false (pt_occluded): boxes are not culled against best.t.  A shape's hit distance carries the
+// rounding of its fp32 intersection, and from a far origin it can fall short of the entry distance of the
+// shape's own padded box: culled at t_max = nextafter(hit), the query would miss a hit strictly nearer.
 template <bool TRI, bool COUNT, bool ANY, bool FULL, class STK>
 __device__ __forceinline__ bool traverse(const DevScene& S, const float4* __restrict__ nodes, int32_t num_nodes,
                                          const float4* __restrict__ recs, v3 o, v3 d, v3 invd, HitRec& best,
                                          const STK& stack, Counters& ctr, int32_t* pend = nullptr,
-                                         int32_t* pend_sdf = nullptr) {
+                                         int32_t* pend_sdf = nullptr, bool far_cull = true) {
     if (num_nodes <= 0) return false;
     uint32_t ref = 0;  // root: always an inner node
     int sp = 0;
-    float tmax = tmax_bound(best.t);  // fp32 cull bound, refreshed when best.t changes
+    float tmax = far_cull ? tmax_bound(best.t) : __int_as_float(0x7f7fffff);  // fp32 cull bound, refreshed when best.t changes
     for (;;) {
         if (!(ref & 0x80000000u)) {
             const float4* c = nodes + 8 * (size_t)ref;
@@ -836,7 +839,8 @@ __device__ __forceinline__ double light_t(const DevScene& S, const DevLight& L, 
 // Is any primitive strictly nearer than tl along (o, d)?  The any-hit half of the shadow query
 // (light_visible) after the light's own t; pt_occluded runs it for a host's rays.
 template <bool COUNT, bool FULL, class STK>
-__device__ __forceinline__ bool any_nearer(const DevScene& S, v3 o, v3 d, double tl, const STK& stack, Counters& ctr) {
+__device__ __forceinline__ bool any_nearer(const DevScene& S, v3 o, v3 d, double tl, const STK& stack, Counters& ctr,
+                                           bool far_cull = true) {
     HitRec best{tl, -1, -1};
     for (int i = 0; i < S.num_planes; i++) {
         float4 a = S.planes[2 * i], b = S.planes[2 * i + 1];
@@ -851,7 +855,7 @@ __device__ __forceinline__ bool any_nearer(const DevScene& S, v3 o, v3 d, double
             if (prim_t<false, FULL>(S, S.ana_recs, (uint32_t)p, o, d, kind) < tl) return true;
         }
     } else if (traverse<false, COUNT, true, FULL>(S, S.ana_nodes, S.ana_num_nodes, S.ana_recs, o, d, invd, best, stack,
-                                                 ctr, FULL ? &pend : nullptr)) {
+                                                 ctr, FULL ? &pend : nullptr, nullptr, far_cull)) {
         return true;
     }
     if (traverse_tri<COUNT, true>(S, o, d, invd, best, stack, ctr)) return true;

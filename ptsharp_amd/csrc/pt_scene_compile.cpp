@@ -13,6 +13,7 @@
 #include "pt_bvh.h"
 #include "pt_ext.h"
 #include "pt_math.h"
+#include "pt_shape_refit.h"
 
 static_assert(sizeof(float4) == 16, "float4 rows are 16 bytes in host and device objects alike");
 
@@ -620,6 +621,36 @@ void Compiler::transformed() {
                    mk((double)ib.mx.x + mp, (double)ib.mx.y + mp, (double)ib.mx.z + mp)};
         xform_bvh_boxes[i] = box_mul(x.matrix, pb);
     }
+    // what a later pt_update_shapes needs (ShapeRefitTables): the inner shapes, and the boxes of those that never move
+    ShapeRefitTables& T = H.shape_refit;
+    T.num_spheres = std::max(d->num_spheres, 0);
+    T.num_cubes = std::max(d->num_cubes, 0);
+    T.num_transformed = (int32_t)H.xforms.size();
+    T.xf_kind.resize(H.xforms.size());
+    T.xf_index.resize(H.xforms.size());
+    T.xf_inner_box.assign(H.xforms.size() * 6, 0.f);
+    T.xf_matrix.resize(H.xforms.size() * 16);
+    T.xf_inverse.resize(H.xforms.size() * 16);
+    for (size_t i = 0; i < H.xforms.size(); i++) {
+        const pt_transformed_shape& x = d->transformed[i];
+        T.xf_kind[i] = H.xforms[i].kind;
+        T.xf_index[i] = x.shape_index;
+        if (x.shape_kind != PT_SHAPE_SPHERE && x.shape_kind != PT_SHAPE_CUBE) {
+            const HostBox ib = shape_box(x.shape_kind, x.shape_index);
+            const float b[6] = {ib.mn.x, ib.mn.y, ib.mn.z, ib.mx.x, ib.mx.y, ib.mx.z};
+            std::memcpy(&T.xf_inner_box[6 * i], b, sizeof b);
+        }
+        std::memcpy(&T.xf_matrix[16 * i], x.matrix, 16 * sizeof(double));
+        std::memcpy(&T.xf_inverse[16 * i], x.inverse, 16 * sizeof(double));
+    }
+    if (T.num_spheres > 0) {
+        T.sphere_center.assign(d->sphere_center, d->sphere_center + 3 * (size_t)T.num_spheres);
+        T.sphere_radius.assign(d->sphere_radius, d->sphere_radius + (size_t)T.num_spheres);
+    }
+    if (T.num_cubes > 0) {
+        T.cube_min.assign(d->cube_min, d->cube_min + 3 * (size_t)T.num_cubes);
+        T.cube_max.assign(d->cube_max, d->cube_max + 3 * (size_t)T.num_cubes);
+    }
 }
 
 // The triangle BVH (built once per process for the same geometry: tri_bvh_shared) and one 128-B shading
@@ -714,7 +745,19 @@ int Compiler::ana_bvh() {
     }
     H.S.ana_count = (int32_t)na;
     H.S.heavy_count = (int32_t)(H.heavy.size() / 2);
-    return pack_nodes(ab, ana_nodes, H.S.ana_num_nodes, err);
+    if (int rc = pack_nodes(ab, ana_nodes, H.S.ana_num_nodes, err)) return rc;
+    // what a later pt_update_shapes needs (ShapeRefitTables): the records' boxes in record order, the nodes by depth
+    ShapeRefitTables& T = H.shape_refit;
+    T.num_recs = (int64_t)na;
+    T.num_heavy = H.S.heavy_count;
+    T.num_nodes = H.S.ana_num_nodes;
+    T.rec_box.resize(na * 6);
+    for (size_t i = 0; i < na; i++) {
+        const size_t src = ab.order[i];
+        for (int q = 0; q < 3; q++) { T.rec_box[6 * i + q] = amin[3 * src + q]; T.rec_box[6 * i + 3 + q] = amax[3 * src + q]; }
+    }
+    shape_levels((const uint32_t*)ana_nodes.data(), T.num_nodes, T.level_nodes, T.level_off);
+    return PT_OK;
 }
 
 void Compiler::planes() {
@@ -740,9 +783,7 @@ void Compiler::lights() {
         L.kind = k; L.mat = mat; L.phantom = 0;
         if (k == PT_SHAPE_SPHERE) {   // Sampler.cs:218-223
             L.index = ana_pos[PT_SHAPE_SPHERE][(size_t)j];
-            const float* cc = d->sphere_center + 3 * j;
-            L.center[0] = cc[0]; L.center[1] = cc[1]; L.center[2] = cc[2];
-            L.radius = d->sphere_radius[j];
+            sphere_light_sphere(d->sphere_center + 3 * j, d->sphere_radius[j], L);
         } else if (k == PT_SHAPE_PLANE) {
             L.index = plane_pos[(size_t)j];
             light_sphere_of_box(mk(-1e9, -1e9, -1e9), mk(1e9, 1e9, 1e9), L);  // Plane.BoundingBox
@@ -760,6 +801,9 @@ void Compiler::lights() {
         }
         H.lights.push_back(L);
         H.refit.light_tri.push_back(k == PT_SHAPE_TRIANGLE ? j : -1);
+        const bool moves = k == PT_SHAPE_SPHERE || k == PT_SHAPE_CUBE || k == PT_SHAPE_TRANSFORMED;
+        H.shape_refit.light_kind.push_back(moves ? k : -1);
+        H.shape_refit.light_index.push_back(moves ? j : -1);
     }
     H.S.num_lights = (int32_t)H.lights.size();
 }
@@ -855,6 +899,69 @@ void tri_root_box(const uint32_t* root, float box[6]) { root_box_of(root, box); 
 void tri_light_sphere(const float* p1, const float* p2, const float* p3, DevLight& L) {
     v3 a = ld3(p1), b = ld3(p2), cc = ld3(p3);
     light_sphere_of_box(vmin(vmin(a, b), cc), vmax(vmax(a, b), cc), L);
+}
+
+void sphere_light_sphere(const float* center, double radius, DevLight& L) {
+    L.center[0] = center[0]; L.center[1] = center[1]; L.center[2] = center[2];
+    L.radius = radius;
+}
+
+void box_light_sphere(const float* mn, const float* mx, DevLight& L) { light_sphere_of_box(ld3(mn), ld3(mx), L); }
+
+bool shape_refit_lights(const ShapeRefitTables& T, std::vector<DevLight>& lights) {
+    bool any = false;
+    for (size_t i = 0; i < lights.size() && i < T.light_kind.size(); i++) {
+        const int k = T.light_kind[i];
+        const int64_t j = T.light_index[i];
+        if (k == PT_SHAPE_SPHERE && j >= 0 && j < T.num_spheres) {
+            sphere_light_sphere(&T.sphere_center[3 * (size_t)j], T.sphere_radius[(size_t)j], lights[i]);
+        } else if (k == PT_SHAPE_CUBE && j >= 0 && j < T.num_cubes) {
+            box_light_sphere(&T.cube_min[3 * (size_t)j], &T.cube_max[3 * (size_t)j], lights[i]);
+        } else if (k == PT_SHAPE_TRANSFORMED && j >= 0 && j < T.num_transformed) {   // light.BoundingBox(): the unpadded box
+            const int32_t ik = T.xf_kind[(size_t)j];
+            const int64_t ij = T.xf_index[(size_t)j];
+            const float* ib = &T.xf_inner_box[6 * (size_t)j];
+            v3 imn = ld3(ib), imx = ld3(ib + 3), bmn, bmx;
+            if (ik == kShapeSphere && ij >= 0 && ij < T.num_spheres)
+                shape_sphere_bounds(&T.sphere_center[3 * (size_t)ij], T.sphere_radius[(size_t)ij], imn, imx);
+            else if (ik == kShapeCube && ij >= 0 && ij < T.num_cubes) {
+                imn = ld3(&T.cube_min[3 * (size_t)ij]);
+                imx = ld3(&T.cube_max[3 * (size_t)ij]);
+            }
+            float lo[3], hi[3];
+            shape_xform_boxes(&T.xf_matrix[16 * (size_t)j], ik, imn, imx, lo, hi, bmn, bmx);
+            const float mn[3] = {bmn.x, bmn.y, bmn.z}, mx[3] = {bmx.x, bmx.y, bmx.z};
+            box_light_sphere(mn, mx, lights[i]);
+        } else {
+            continue;
+        }
+        any = true;
+    }
+    return any;
+}
+
+void shape_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {
+    level_nodes.clear();
+    level_off.assign(1, 0u);
+    if (num_nodes <= 0) return;
+    std::vector<uint8_t> seen((size_t)num_nodes, 0);
+    level_nodes.push_back(0u);
+    seen[0] = 1;
+    size_t begin = 0;
+    while (begin < level_nodes.size()) {   // one level per round: the children of [begin, end)
+        const size_t end = level_nodes.size();
+        level_off.push_back((uint32_t)end);
+        for (size_t q = begin; q < end; q++) {
+            const uint32_t* w = nodes + (size_t)level_nodes[q] * kNode4Words;
+            for (int k = 0; k < 4; k++) {
+                const uint32_t ref = w[24 + k];
+                if (ref == kEmpty4 || (ref & 0x80000000u) || (int64_t)ref >= num_nodes || seen[ref]) continue;
+                seen[ref] = 1;
+                level_nodes.push_back(ref);
+            }
+        }
+        begin = end;
+    }
 }
 
 void refit_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {

@@ -63,6 +63,32 @@ void tri_root_box(const uint32_t* root, float box[6]);
 // Centre and radius of a loose emissive triangle's light, as the compile's light stage computes them.
 void tri_light_sphere(const float* p1, const float* p2, const float* p3, DevLight& L);
 
+// What pt_update_shapes needs beside the device arrays: host tables kept from the upload, and the
+// parameters the device holds now (a group an update does not give is refitted from these).
+struct ShapeRefitTables {
+    int32_t num_spheres = 0, num_cubes = 0, num_transformed = 0;   // pt_scene_desc's counts: the lengths an update takes
+    int64_t num_nodes = 0, num_recs = 0, num_heavy = 0;            // analytic BVH4 nodes, analytic records, heavy records
+    std::vector<uint32_t> level_nodes;   // the BVH4's node indices grouped by depth, the root's level first
+    std::vector<uint32_t> level_off;     // level l is level_nodes[level_off[l] .. level_off[l + 1])
+    std::vector<int32_t> xf_kind, xf_index;   // per transformed shape: its inner shape (kind as DevXform::kind)
+    std::vector<float> xf_inner_box;     // per transformed shape: 6 floats, the inner box before march_pad of the kinds
+                                         // that never move (SDF, Volume, Mesh, Plane); zeros for a sphere or cube
+    std::vector<float> rec_box;          // per analytic record: 6 floats, its BVH box at the upload
+    std::vector<int32_t> light_kind, light_index;   // per HostScene::lights entry: its source (PT_SHAPE_SPHERE, _CUBE or
+                                                    // _TRANSFORMED and the scene index), or -1 (a light no update moves)
+    std::vector<float> sphere_center, cube_min, cube_max;   // the current parameters, in pt_scene_desc order
+    std::vector<double> sphere_radius, xf_matrix, xf_inverse;   // matrices [num_transformed][16] row-major
+};
+// The nodes of a BVH4 (kNode4Words words each) grouped by depth: a breadth-first walk from node 0 over words 24-27.
+void shape_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off);
+// Centre and radius of a sphere light (Sampler.cs:218-223) and of a light with a bounding box (Box.Center,
+// Box.OuterRadius), as the compile's light stage computes them.
+void sphere_light_sphere(const float* center, double radius, DevLight& L);
+void box_light_sphere(const float* mn, const float* mx, DevLight& L);
+// The lights that follow T's current parameters, recomputed in place (lights: HostScene::lights' order); true
+// when the scene has one.
+bool shape_refit_lights(const ShapeRefitTables& T, std::vector<DevLight>& lights);
+
 // A compiled scene on the host: every array pt_upload_scene uploads, and the DevScene with every
 // non-pointer field filled.
 struct HostScene {
@@ -91,6 +117,7 @@ struct HostScene {
     std::shared_ptr<const TriBvhBuild> tri_build;   // the shared triangle build `lines` was filled from
     double tri_build_ms = 0;                        // host time to build (or wait for, or find) it
     RefitTables refit;
+    ShapeRefitTables shape_refit;
 };
 
 // Validates and compiles.  PT_OK, or an error code with its message in err (H is then partly filled; its

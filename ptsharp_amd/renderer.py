@@ -456,6 +456,77 @@ class Renderer:
                                              box.ctypes.data_as(C.POINTER(C.c_float))), "pt_read_tri_bvh")
         return out[0], out[1], out[2], box
 
+    def UpdateShapes(self, sphere_center=None, sphere_radius=None, cube_min=None, cube_max=None, matrices=None,
+                     inverses=None) -> float:
+        """New parameters for the spheres, cubes and transformed shapes of the scene, in the order of the compiled
+        scene's sphere_center, cube_min and transformed (pt_update_shapes): centres [n, 3] float32 (with radii [n]
+        float64, or the radii stay), both cube corners [n, 3] float32, matrices [n, 4, 4] float64 with their inverses
+        (derived with Matrix.Inverse when not given).  A group left None stays.  The analytic BVH is refitted on the
+        device with its topology kept; nothing is rebuilt or re-uploaded.  The arrays are then written into the
+        uploaded FlatScene in place, so it describes what the device holds.  Returns the device time of the kernels
+        in ms."""
+        self._ensure_scene()
+        flat = self._uploaded
+        if sphere_radius is not None and sphere_center is None:
+            raise ValueError("sphere_radius needs sphere_center")
+        if (cube_min is None) != (cube_max is None):
+            raise ValueError("cube_min and cube_max must be both given or both None")
+        if inverses is not None and matrices is None:
+            raise ValueError("inverses needs matrices")
+        u = _abi.pt_shape_update()
+        fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+        keep = []
+
+        def arr(a, dtype, shape, n, what):
+            a = np.ascontiguousarray(a, dtype).reshape(shape)
+            if len(a) != n:
+                raise ValueError(f"the scene has {n} {what}")
+            keep.append(a)
+            return a
+
+        sc = sr = ca = cb = m = inv = None
+        if sphere_center is not None:
+            sc = arr(sphere_center, np.float32, (-1, 3), len(flat.sphere_radius), "spheres")
+            u.num_spheres, u.sphere_center = len(sc), sc.ctypes.data_as(fp)
+            if sphere_radius is not None:
+                sr = arr(sphere_radius, np.float64, (-1,), len(sc), "spheres")
+                u.sphere_radius = sr.ctypes.data_as(dp)
+        if cube_min is not None:
+            ca = arr(cube_min, np.float32, (-1, 3), len(flat.cube_material), "cubes")
+            cb = arr(cube_max, np.float32, (-1, 3), len(flat.cube_material), "cubes")
+            u.num_cubes, u.cube_min, u.cube_max = len(ca), ca.ctypes.data_as(fp), cb.ctypes.data_as(fp)
+        if matrices is not None:
+            nx = flat.counts_ext[3]
+            m = arr(matrices, np.float64, (-1, 4, 4), nx, "transformed shapes")
+            if inverses is None:
+                from .geometry import Matrix
+                inverses = [Matrix(k).Inverse().m for k in m] if nx else np.zeros((0, 4, 4))
+            inv = arr(inverses, np.float64, (-1, 4, 4), nx, "transformed shapes")
+            u.num_transformed, u.xform_matrix, u.xform_inverse = len(m), m.ctypes.data_as(dp), inv.ctypes.data_as(dp)
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_update_shapes(self._ctx, C.byref(u), C.byref(ms)), "pt_update_shapes")
+        for dst, a in ((flat.sphere_center, sc), (flat.sphere_radius, sr), (flat.cube_min, ca), (flat.cube_max, cb)):
+            if a is not None:
+                dst[...] = a
+        if m is not None:
+            for i in range(len(m)):
+                flat.transformed[i].matrix[:] = m[i].reshape(-1).tolist()
+                flat.transformed[i].inverse[:] = inv[i].reshape(-1).tolist()
+        return float(ms.value)
+
+    def ReadShapeBvh(self):
+        """The context's analytic BVH as it stands on the device (pt_read_shape_bvh): (nodes [N, 32], records
+        [R, 12], heavy records [H, 8], all uint32, and the lights [L, 4] float64: centre x, y, z and radius)."""
+        self._ensure_scene()
+        counts = (C.c_int64 * 4)()
+        _abi.check(self._lib.pt_read_shape_bvh(self._ctx, counts, None, None, None, None), "pt_read_shape_bvh")
+        out = [np.zeros((int(c), w), np.uint32) for c, w in zip(counts[:3], (32, 12, 8))]
+        lights = np.zeros((int(counts[3]), 4), np.float64)
+        up = C.POINTER(C.c_uint32)
+        _abi.check(self._lib.pt_read_shape_bvh(self._ctx, counts, *[a.ctypes.data_as(up) for a in out],
+                                               lights.ctypes.data_as(C.POINTER(C.c_double))), "pt_read_shape_bvh")
+        return out[0], out[1], out[2], lights
+
     def ResetBuffer(self) -> None:
         _abi.check(self._lib.pt_reset_buffer(self._ctx), "pt_reset_buffer")
         self._pass = 0
