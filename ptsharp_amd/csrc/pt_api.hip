@@ -566,6 +566,8 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     opt.vol_cells = !env_off("PT_VOL_CELLS");
     opt.vol_lds = !env_off("PT_VOL_LDS");
     opt.route = !env_off("PT_ROUTE");
+    if (const char* f = std::getenv("PT_POP_CULL_BITS")) opt.pop_cull_bits = std::max(0, std::min(opt.pop_cull_bits, std::atoi(f)));
+    if (env_off("PT_POP_CULL")) opt.pop_cull_bits = 0;
     PT_HIP(hipSetDevice(c->device));
     auto t0 = std::chrono::steady_clock::now();
     free_scene(c);

@@ -8,6 +8,7 @@
 #include "pt_bvh.h"
 #include "pt_math.h"
 #include "pt_scene.h"
+#include "pt_stack_key.h"
 
 #pragma clang fp contract(off)
 
@@ -215,9 +216,13 @@ __device__ __forceinline__ void halves(float w, float& a, float& b) {
 __device__ __forceinline__ uint32_t node8_ref(uint32_t k, uint32_t nin, uint32_t base_in, uint32_t leaf0) {
     return k < nin ? base_in + k : leaf0 + k;
 }
-template <class STK>
+// KEYED (the closest-hit refill kernels, pt_wavefront.hip trace_lanes): a pushed entry carries the top bits of
+// its entry distance under key_mask (pt_stack_key.h), so the pop can cull it against the bound of that time;
+// the descended child's ref is bare.  A missed slot's entry is written with a garbage key and never kept.
+template <bool KEYED = false, class STK>
 __device__ __forceinline__ bool node8_step(float4 q0, float4 q1, float4 q2, float4 q3, float4 q4, float4 q5, float4 q6,
-                                           float4 q7, v3 o, v3 invd, float tmax, const STK& st, int& sp, uint32_t& ref) {
+                                           float4 q7, v3 o, v3 invd, float tmax, const STK& st, int& sp, uint32_t& ref,
+                                           uint32_t key_mask = 0u) {
     const uint32_t hdr = __float_as_uint(q0.w);
     const float sx = __uint_as_float((hdr & 0xFFu) << 23), sy = __uint_as_float(((hdr >> 8) & 0xFFu) << 23);
     const float sz = __uint_as_float(((hdr >> 16) & 0xFFu) << 23);
@@ -256,13 +261,18 @@ __device__ __forceinline__ bool node8_step(float4 q0, float4 q1, float4 q2, floa
     if (__builtin_expect(sp <= STK::kLds - 8, 1)) {   // every slot written, sp advanced by the other hits
 #pragma unroll
         for (int j = 7; j >= 0; j--) {
-            st.lds[sp * STK::kStride] = node8_ref((uint32_t)j, nin, base_in, leaf0);
+            const uint32_t r = node8_ref((uint32_t)j, nin, base_in, leaf0);
+            st.lds[sp * STK::kStride] = KEYED ? stack_entry(r, key[j], key_mask) : r;
             sp += (key[j] != 0xFFFFFFFFu && (uint32_t)j != near) ? 1 : 0;
         }
     } else {
 #pragma unroll
         for (int j = 7; j >= 0; j--)
-            if (key[j] != 0xFFFFFFFFu && (uint32_t)j != near) { st.put(sp, node8_ref((uint32_t)j, nin, base_in, leaf0)); sp++; }
+            if (key[j] != 0xFFFFFFFFu && (uint32_t)j != near) {
+                const uint32_t r = node8_ref((uint32_t)j, nin, base_in, leaf0);
+                st.put(sp, KEYED ? stack_entry(r, key[j], key_mask) : r);
+                sp++;
+            }
     }
     return true;
 }

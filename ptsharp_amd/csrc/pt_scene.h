@@ -68,6 +68,10 @@ struct DevScene {
     // the triangle BVH's root box (the union of the root node's child boxes): a refill traversal
     // whose ray misses it skips the triangle phase instead of spending a step on the root node
     float tri_box[6];          // lo.xyz, hi.xyz
+    // the key field of the closest-hit refill kernels' stack entries in the triangle phase (pt_stack_key.h): the
+    // bits between the leaf flag and the widest node or chunk index, at most kStackKeyMaxBits of them; 0: bare
+    // refs, nothing is culled at pop.  Node and chunk counts stand across refits, and so does this.
+    uint32_t stack_key_mask;
     // planes (unbounded: tested outside the BVHs)
     const float4* planes;      // 2 float4: {point.xyz, mat} {normal.xyz, scene index}
     int32_t num_planes;

@@ -14,6 +14,7 @@
 #include "pt_ext.h"
 #include "pt_math.h"
 #include "pt_shape_refit.h"
+#include "pt_stack_key.h"
 
 static_assert(sizeof(float4) == 16, "float4 rows are 16 bytes in host and device objects alike");
 
@@ -820,6 +821,8 @@ int Compiler::lines() {
     H.S.lines_n = (uint32_t)(H.lines.size() / 8);
     H.S.tri_node_line0 = (uint32_t)(ana_nodes.size() / 8);
     H.S.tri_chunk_line0 = (uint32_t)((ana_nodes.size() + tri_nodes.size()) / 8);
+    // the stack entries' key field: what the widest triangle-phase index leaves of the 31 bits below the leaf flag
+    H.S.stack_key_mask = stack_key_mask(stack_key_choose(tri_nodes.size() / 8, tri_chunks.size() / 8, opt.pop_cull_bits));
     H.bvh_nodes = (uint64_t)H.S.tri_num_nodes + (uint64_t)H.S.ana_num_nodes;
     H.traversal_bytes = (H.lines.size() + H.ana_recs.size()) * sizeof(float4);
     H.bvh_bytes = H.lines.size() * sizeof(float4) + (H.tri_sh.size() + H.ana_recs.size()) * sizeof(float4);

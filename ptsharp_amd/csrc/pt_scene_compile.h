@@ -20,6 +20,7 @@ struct CompileOptions {
     bool vol_cells = true;   // PT_VOL_CELLS=0: no cell-major Volume corners, the march reads the grid
     bool vol_lds = true;     // PT_VOL_LDS=0: the scene's one Volume is not staged in LDS
     bool route = true;       // PT_ROUTE=0: every ray through the FULL analytic half
+    int pop_cull_bits = 15;  // PT_POP_CULL=0: 0 (bare stack entries); PT_POP_CULL_BITS=n: at most n key bits
 };
 
 // The triangle BVH of one geometry, shared by every context of the process that uploads it (tri_bvh_shared).

@@ -855,7 +855,7 @@ __device__ __forceinline__ void trace_lanes(const DevScene& S, const WfQueues& Q
         if (!leaf) {
             if (COUNT) ctr.nodes++;
             if (tri) {   // the triangle BVH: 8-wide quantized nodes (pt_device.h node8_step)
-                pop = !node8_step(q0, q1, q2, q3, q4, q5, q6, q7, o, invd, tmax, stack, sp, ref);
+                pop = !node8_step<true>(q0, q1, q2, q3, q4, q5, q6, q7, o, invd, tmax, stack, sp, ref, S.stack_key_mask);
             } else {     // the analytic BVH4
                 float k0, k1, k2, k3;
                 uint32_t v0, v1, v2, v3r;
@@ -898,10 +898,26 @@ __device__ __forceinline__ void trace_lanes(const DevScene& S, const WfQueues& Q
             }
         }
         if (pop) {
-            if (sp > 0) {
+            if (tri) {
+                // Keyed entries (pt_stack_key.h): an entry pushed under an earlier bound whose entry distance
+                // is beyond the bound of now is dropped here, and the lane pops again, instead of spending a
+                // step on a line none of whose children (or triangles) can win.  The bound is recomputed
+                // here, not held across the step (a register).  The analytic phase's stack is empty when a
+                // lane enters this phase, so every entry met here is a keyed one.
+                const uint32_t km = S.stack_key_mask, bound = stack_bound_bits(tmax);
+                uint32_t e = 0u;
+                bool got = false;
+                while (sp > 0) {
+                    sp--;
+                    e = stack.get(sp);
+                    if (!stack_entry_culled(e, km, bound)) { got = true; break; }
+                }
+                if (got) ref = stack_entry_ref(e, km);
+                else finish();
+            } else if (sp > 0) {   // the analytic BVH4's bare refs (their leaf refs use bits 29-30)
                 sp--;
                 ref = stack.get(sp);
-            } else if (!tri && !(i >> 31)) {
+            } else if (!(i >> 31)) {
                 tri = true;
                 ref = 0;
             } else {

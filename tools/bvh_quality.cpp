@@ -11,6 +11,9 @@
 // and reports steps, node steps, leaf steps and triangle tests per ray, by depth, plus the tree's
 // SAH cost.  Input: tools/dump_c4_mesh.py's file (triangles after FitInside, camera basis).
 //   usage: bvh_quality MESH.bin [stride] [variant ...]   variant: greedy | sah
+// The wide variants (p8: the library's BVH8; wNqB) take env POPCULL: stack entries keyed by their entry
+// distance and culled at pop against the bound of that moment (pt_stack_key.h): 0 off, 1 the exact fp32
+// distance, n >= 2: 8 exponent + n mantissa bits; culled pops per ray are printed.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -23,6 +26,7 @@
 
 #include "../ptsharp_amd/csrc/pt_bvh.h"
 #include "../ptsharp_amd/csrc/pt_math.h"
+#include "../ptsharp_amd/csrc/pt_stack_key.h"
 
 using namespace pt;
 
@@ -58,7 +62,8 @@ struct Tree {
 
 struct Count {
     double rays = 0, nodes = 0, leaves = 0, tris = 0, inside = 0;   // inside: steps whose box holds the origin
-    void add(const Count& o) { rays += o.rays; nodes += o.nodes; leaves += o.leaves; tris += o.tris; inside += o.inside; }
+    double culled = 0;   // WideTracer, POPCULL: stack entries dropped at pop by their entry distance
+    void add(const Count& o) { rays += o.rays; nodes += o.nodes; leaves += o.leaves; tris += o.tris; inside += o.inside; culled += o.culled; }
 };
 
 struct Tracer {
@@ -315,6 +320,12 @@ struct WideTracer {
         prim = -1;
         float tmax = (float)best;
         std::vector<uint32_t> stack;
+        // POPCULL (closest-hit rays): every stack entry keeps the top bits of its entry distance (pt_stack_key.h,
+        // kept beside the model's refs, whose leaf refs use bits 29-30) and a pop drops the entries beyond the
+        // bound of that moment.  0: off; 1: the exact fp32 distance; n >= 2: 8 exponent + n mantissa bits.
+        static const int popcull = std::getenv("POPCULL") ? std::atoi(std::getenv("POPCULL")) : 0;
+        const uint32_t km = (popcull == 0 || any) ? 0u : stack_key_mask(popcull == 1 ? 31 : std::min(31, 8 + popcull));
+        std::vector<uint32_t> keys;
         uint32_t ref = 0;
         for (;;) {
             if (!(ref & 0x80000000u)) {
@@ -351,7 +362,10 @@ struct WideTracer {
                     for (int a = 0; a < m; a++) ch[1 + a] = c2[a];
                 }
                 if (nh > 0) {
-                    for (int k = nh - 1; k >= 1; k--) stack.push_back(ch[k]);
+                    for (int k = nh - 1; k >= 1; k--) {
+                        stack.push_back(ch[k]);
+                        keys.push_back(stack_entry(0u, stack_f32_bits(key[k]) & 0x7FFFFFFFu, km));
+                    }
                     max_stack = std::max(max_stack, (int)stack.size());
                     ref = ch[0];
                     continue;
@@ -371,9 +385,15 @@ struct WideTracer {
                     }
                 }
             }
+            while (!stack.empty() && stack_entry_culled(keys.back(), km, stack_bound_bits(tmax))) {
+                stack.pop_back();
+                keys.pop_back();
+                c.culled++;
+            }
             if (stack.empty()) break;
             ref = stack.back();
             stack.pop_back();
+            keys.pop_back();
         }
         return best;
     }
@@ -717,9 +737,9 @@ static void run_wide(const Mesh& m, int W, int Q, int stride) {
                 T.leaves, T.fill, T.depth, max_stack, bs);
     auto row = [](const char* name, const Count& c, double tests) {
         if (c.rays == 0) return;
-        std::printf("  %-9s rays %9.0f  steps/ray %6.3f  nodes/ray %6.3f  leaves/ray %6.3f  tris/ray %6.3f  origin-box %6.3f  box tests/ray %6.2f\n",
+        std::printf("  %-9s rays %9.0f  steps/ray %6.3f  nodes/ray %6.3f  leaves/ray %6.3f  tris/ray %6.3f  origin-box %6.3f  box tests/ray %6.2f  culled pops/ray %6.3f\n",
                     name, c.rays, (c.nodes + c.leaves) / c.rays, c.nodes / c.rays, c.leaves / c.rays, c.tris / c.rays,
-                    c.inside / c.rays, tests / c.rays);
+                    c.inside / c.rays, tests / c.rays, c.culled / c.rays);
     };
     row("closest", all, tests_c);
     for (int k = 0; k <= kDepth; k++) {
