@@ -193,6 +193,16 @@ namespace PTSharpCore
             public IntPtr xform_inverse;
         }
 
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_mesh_update
+        {
+            public int num_triangles;      // must equal the uploaded scene's
+            public int normals_mode;       // 0: n1..n3 given or kept (all null); PT_NORMALS_FACE; PT_NORMALS_SMOOTH
+            public fixed int reserved[2];  // 0
+            public IntPtr v1, v2, v3;      // [n][3] float, required
+            public IntPtr n1, n2, n3;      // [n][3] float; only with normals_mode 0
+        }
+
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_get_version();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_device_count(out int count);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_create(ref pt_device_opts opts, out IntPtr ctx);
@@ -226,6 +236,9 @@ namespace PTSharpCore
         // new sphere, cube and TransformedShape parameters: the analytic BVH refitted on the device
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_shapes(IntPtr ctx, ref pt_shape_update u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_shape_bvh(IntPtr ctx, long[] counts, uint[] nodes, uint[] recs, uint[] heavy, double[] lights);
+        // pt_update_triangles / _normals for a scene with instanced meshes too: their BLASes refitted on the device
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_meshes(IntPtr ctx, ref pt_mesh_update u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_blas(IntPtr ctx, long[] counts, int[] blas, uint[] nodes, uint[] recs, uint[] shade, float[] innerBoxes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr pt_last_error();
@@ -703,6 +716,55 @@ namespace PTSharpCore
             {
                 foreach (var h in held) h.Free();
             }
+        }
+
+        /// <summary>UpdateTriangles / UpdateTrianglesNormals for a scene that may hold instanced meshes
+        /// (pt_update_meshes; those two refuse such a scene): new positions for every triangle, instanced meshes'
+        /// included, the normals given (all three), kept (all null) or derived (normalsMode PtHip.PT_NORMALS_FACE
+        /// or PT_NORMALS_SMOOTH).  Every BLAS is refitted on the device, the instances' boxes and the analytic BVH
+        /// follow; nothing is rebuilt.  Returns the device time of the kernels in ms.</summary>
+        public double UpdateMeshes(float[] v1, float[] v2, float[] v3, float[] n1 = null, float[] n2 = null, float[] n3 = null,
+                                   int normalsMode = 0)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            IntPtr PinHeld(Array a)
+            {
+                if (a == null) return IntPtr.Zero;
+                var h = GCHandle.Alloc(a, GCHandleType.Pinned);
+                held.Add(h);
+                return h.AddrOfPinnedObject();
+            }
+            try
+            {
+                var u = new PtHip.pt_mesh_update
+                {
+                    num_triangles = v1.Length / 3, normals_mode = normalsMode,
+                    v1 = PinHeld(v1), v2 = PinHeld(v2), v3 = PinHeld(v3), n1 = PinHeld(n1), n2 = PinHeld(n2), n3 = PinHeld(n3),
+                };
+                PtHip.Check(PtHip.pt_update_meshes(ctx, ref u, out double ms), "pt_update_meshes");
+                return ms;
+            }
+            finally
+            {
+                foreach (var h in held) h.Free();
+            }
+        }
+
+        /// <summary>The context's BLASes as they stand on the device (pt_read_blas): 4 ints per BLAS, 32 words per
+        /// node, 12 words per triangle in recs and in shade, 6 floats per BLAS (the mesh's unpadded box).</summary>
+        public (int[] blas, uint[] nodes, uint[] recs, uint[] shade, float[] innerBoxes) ReadBlas()
+        {
+            if (!uploaded) Upload();
+            var counts = new long[3];
+            PtHip.Check(PtHip.pt_read_blas(ctx, counts, null, null, null, null, null), "pt_read_blas");
+            var blas = new int[counts[0] * 4];
+            var nodes = new uint[counts[1] * 32];
+            var recs = new uint[counts[2] * 12];
+            var shade = new uint[counts[2] * 12];
+            var boxes = new float[counts[0] * 6];
+            PtHip.Check(PtHip.pt_read_blas(ctx, counts, blas, nodes, recs, shade, boxes), "pt_read_blas");
+            return (blas, nodes, recs, shade, boxes);
         }
 
         /// <summary>The first-hit features of the whole frame (pt_render_features): one ray through each

@@ -20,6 +20,9 @@
  *   / pt_read_tri_normals        device: face or smooth                     Triangle.cs:224-237, Mesh.cs:191-229
  *   pt_update_shapes   (new) new sphere, cube and TransformedShape          Example.cs:163-223 ("beads"): that loop
  *   / pt_read_shape_bvh parameters: the analytic BVH refitted on the device  moves 31,920 spheres, and no triangle
+ *   pt_update_meshes   (new) pt_update_triangles / _normals for a scene with  Mesh.cs:88-120 (Mesh.BoundingBox),
+ *   / pt_read_blas     instanced meshes too: their BLASes refitted on the   TransformedShape.cs:36-39
+ *                      device, the instances' boxes and lights following
  *   pt_render_pass     one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
@@ -616,6 +619,45 @@ int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms)
  * per heavy record, 4 doubles per light (centre x, y, z widened to double, then the radius).  Any argument but
  * ctx may be NULL.  Synchronises and changes nothing. */
 int pt_read_shape_bvh(void* ctx, int64_t counts[4], uint32_t* nodes, uint32_t* recs, uint32_t* heavy, double* lights);
+
+/* pt_update_triangles and pt_update_triangles_normals in one struct-based entry point that also serves a scene
+ * with instanced meshes (those two still refuse such a scene).  New positions for every triangle of
+ * the uploaded scene, in pt_scene_desc order, the triangles of instanced meshes included, whether or not the mesh
+ * is also a top-level shape; the normals given (normals_mode 0, n1..n3 all set), kept (normals_mode 0, n1..n3 all
+ * NULL) or derived (PT_NORMALS_FACE, PT_NORMALS_SMOOTH: as pt_update_triangles_normals derives them, an instanced
+ * mesh being a mesh like any other).
+ * A scene without an instanced mesh: everything on the device is, word for word, what those two calls leave.
+ * A scene with instanced meshes: besides the world triangle BVH, every BLAS (the object-space BVH of an instanced
+ * mesh) is refitted with its topology kept: its triangles' geometry rows, their normal rows when normals are given
+ * or derived (the material word kept), every node's child boxes; then each mesh's unpadded Mesh.BoundingBox, the
+ * inner box of every pt_transformed_shape over it; then, through pt_update_shapes' refit from the current sphere,
+ * cube and matrix values, those shapes' world boxes, the analytic BVH, the boxes the routed split tests and the
+ * lights made from such shapes.  Afterwards every ray query, feature pass and render pass sees the scene a fresh
+ * pt_upload_scene of the same pt_scene_desc with these arrays and the current shape parameters would see, up to the
+ * exact-t tie order of DESIGN.md §5.  Texture coordinates, materials, topology, the Buffer, the pass state and the
+ * counters are untouched.  Runs on the context's stream after every pass issued before it and synchronises before
+ * returning; out_kernel_ms (may be NULL) covers every kernel of the call.  It composes with pt_update_shapes in
+ * either order.  Non-finite positions: boxes and normals are unspecified; no access leaves its array.
+ * Errors (nothing launched, the scene untouched): a NULL ctx, u, v1, v2 or v3, reserved != 0, a normals_mode outside
+ * {0, 1, 2}, normals partly NULL or given with normals_mode != 0, num_triangles different from the uploaded scene's:
+ * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; a workspace (kept until the next upload) not allocated:
+ * PT_ERR_OUT_OF_MEMORY; PT_NORMALS_SMOOTH with 3 * num_triangles >= 2^31: PT_ERR_UNSUPPORTED. */
+typedef struct pt_mesh_update {
+    int32_t num_triangles;     /* must equal the uploaded scene's */
+    int32_t normals_mode;      /* 0: n1..n3 given (all three) or kept (all NULL); PT_NORMALS_FACE; PT_NORMALS_SMOOTH */
+    int32_t reserved[2];       /* 0 */
+    const float *v1, *v2, *v3; /* [n][3], required, pt_scene_desc order */
+    const float *n1, *n2, *n3; /* [n][3]; only with normals_mode 0 */
+} pt_mesh_update;
+int pt_update_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms);
+/* The context's BLASes as they stand on the device (tests and tools): counts[0..2] = BLASes, BLAS nodes in total,
+ * BLAS triangles in total; blas receives 4 int32 per BLAS (first node, nodes, first triangle, 0), nodes 32 words
+ * per node (child references and leaf firsts are relative to the BLAS's first node / triangle), recs and shade 12
+ * words per triangle position each, inner_boxes 6 floats per BLAS: the unpadded mesh box (min, max) the device holds
+ * after a pt_update_meshes, the upload's before.  A triangle that is only instanced reads as zeros in
+ * pt_read_tri_normals; its normals are in shade.  Any argument but ctx may be NULL.  Synchronises and changes
+ * nothing.  A NULL ctx: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+int pt_read_blas(void* ctx, int64_t counts[3], int32_t* blas, uint32_t* nodes, uint32_t* recs, uint32_t* shade, float* inner_boxes);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/ptsharp_hip.h"
+#include "pt_blas_refit.h"
 #include "pt_bvh.h"
 #include "pt_device.h"
 #include "pt_math.h"
@@ -105,6 +106,15 @@ hipError_t launch_shape_refit(const ShapeParams& P, int64_t num_nodes, int64_t n
                               uint32_t* ext_recs, DevXform* xforms, uint32_t* heavy, const int32_t* inner_kind,
                               const int32_t* inner_index, const float* inner_box, float* xbox, float* rec_box, float* node_box,
                               hipStream_t stream);
+// pt_blas_refit.hip
+int64_t blas_bounds_span();
+hipError_t launch_blas_refit(int64_t num_blas, int64_t num_pos, int64_t num_nodes, int64_t num_triangles, int64_t num_transformed,
+                             int64_t num_blocks, int64_t num_levels, const uint32_t* level_off, const uint32_t* level_nodes,
+                             const int32_t* level_blas, const int32_t* desc, const int32_t* src_of_pos, const int32_t* block_blas,
+                             const int32_t* block_first, const int32_t* blas_block_off, const int32_t* xf_blas, uint32_t* nodes,
+                             uint32_t* recs, uint32_t* shade, const float* v1, const float* v2, const float* v3, const float* n1,
+                             const float* n2, const float* n3, float* tri_box, float* node_box, float* block_part, float* blas_box,
+                             float* xf_inner_box, hipStream_t stream);
 // pt_normals.hip
 hipError_t normals_sort_temp_bytes(int64_t corners, int32_t num_groups, size_t* out);
 hipError_t launch_normals(bool smooth, int64_t n, const float* v1, const float* v2, const float* v3, float* n1, float* n2,
@@ -247,6 +257,13 @@ struct Ctx {
     // static tables) comes with the first update
     pt::ShapeRefitTables shape_refit;
     DeviceArray shapes_dev;
+    // pt_update_meshes on a scene with instanced meshes: the host tables of the last upload; the device side (one
+    // allocation: the tables, a box per BLAS triangle and node, the bounds' block partials, a box per BLAS) comes with
+    // the first update
+    pt::BlasRefitTables blas_refit;
+    DeviceArray blas_dev;
+    size_t blas_num_blocks = 0;          // blocks of the bounds kernel (blas_dev's block tables)
+    bool blas_boxes_on_device = false;   // blas_dev holds the meshes' boxes (after the first pt_update_meshes)
 };
 
 #ifndef PT_VOL_DEFER
@@ -423,6 +440,10 @@ void free_scene(Ctx* c) {
     c->normals_temp_bytes = 0;
     c->shapes_dev.release();
     c->shape_refit = pt::ShapeRefitTables{};
+    c->blas_dev.release();
+    c->blas_num_blocks = 0;
+    c->blas_boxes_on_device = false;
+    c->blas_refit = pt::BlasRefitTables{};
     c->refit = pt::RefitTables{};
     c->h_lights.clear();
     c->has_blas = false;
@@ -589,6 +610,7 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     c->has_scene = true;
     c->refit = std::move(H.refit);
     c->shape_refit = std::move(H.shape_refit);
+    c->blas_refit = std::move(H.blas_refit);
     c->h_lights = std::move(H.lights);
     c->has_blas = !H.blas.empty();
     c->stats.bvh_nodes = H.bvh_nodes;
@@ -1289,7 +1311,7 @@ int ensure_refit_dev(Ctx* c, RefitDev& D) {
         c->refit_dev.bytes = D.bytes;
     }
     D = refit_layout(T, c->refit_dev.ptr);
-    if (first) {
+    if (first && !T.src_of_pos.empty()) {
         PT_HIP(hipMemcpyAsync(D.src_of_pos, T.src_of_pos.data(), T.src_of_pos.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         PT_HIP(hipMemcpyAsync(D.level_nodes, T.level_nodes.data(), T.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     }
@@ -1319,9 +1341,17 @@ NormalsDev normals_layout(const pt::RefitTables& T, size_t temp_bytes, void* bas
     return r;
 }
 
-// pt_update_triangles (mode 0: the normals given, or kept) and pt_update_triangles_normals (mode: a pt_normals_mode)
+// pt_update_meshes' part for instanced meshes (below, with the shape refit it ends in): both workspaces, before the
+// first copy; the kernels on the context's stream, after the arrays were staged in `in` (in[3..5] NULL: normals kept);
+// the meshes' boxes back into the host tables and the lights, which ends in a synchronise.
+int blas_refit_prepare(Ctx* c);
+int blas_refit_launch(Ctx* c, int32_t num_triangles, const float* const in[6]);
+int blas_refit_finish(Ctx* c);
+
+// pt_update_triangles (mode 0: the normals given, or kept), pt_update_triangles_normals (mode: a pt_normals_mode) and
+// pt_update_meshes (meshes: instanced meshes are refitted too, not refused)
 int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
-                     const float* n2, const float* n3, bool derive, int32_t mode, double* out_kernel_ms) {
+                     const float* n2, const float* n3, bool derive, int32_t mode, bool meshes, double* out_kernel_ms) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!v1 || !v2 || !v3) return fail(PT_ERR_INVALID_ARG, "update: v1, v2 and v3 are required");
@@ -1334,11 +1364,12 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
     if (num_triangles != T.num_triangles)
         return fail(PT_ERR_INVALID_ARG, "update: num_triangles is " + std::to_string(num_triangles) + ", the uploaded scene has " +
                                             std::to_string(T.num_triangles));
-    if (c->has_blas)
+    if (c->has_blas && !meshes)
         return fail(PT_ERR_UNSUPPORTED, "update: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
                                         "its BLAS is not refitted");
     if (out_kernel_ms) *out_kernel_ms = 0.0;
-    if (T.num_chunks == 0) return PT_OK;   // no triangle in the BVH (num_triangles == 0, or none of them in Scene.Shapes)
+    const bool blas = c->has_blas && num_triangles > 0;
+    if (T.num_chunks == 0 && !blas) return PT_OK;   // no triangle in a BVH (num_triangles == 0, or none of them in Scene.Shapes)
     PT_HIP(hipSetDevice(c->device));
     const bool smooth = derive && mode == PT_NORMALS_SMOOTH;
     if (smooth && (int64_t)num_triangles * 3 > (int64_t)INT32_MAX)
@@ -1366,6 +1397,7 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
     }
     RefitDev D{};
     if (const int rc = ensure_refit_dev(c, D)) return rc;
+    if (blas) if (const int rc = blas_refit_prepare(c)) return rc;
     const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
     const float* src[6] = {v1, v2, v3, n1, n2, n3};
     for (int k = 0; k < (n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
@@ -1379,10 +1411,15 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
                             (uint32_t*)const_cast<float4*>(c->S.tri_chunks), (uint32_t*)const_cast<float4*>(c->S.tri_recs),
                             D.src_of_pos, D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
                             normals ? D.in[5] : nullptr, D.node_box, D.chunk_box, c->stream));
+    if (blas) {
+        const float* const in[6] = {D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
+                                    normals ? D.in[5] : nullptr};
+        if (const int rc = blas_refit_launch(c, num_triangles, in)) return rc;
+    }
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     // the root box follows (pt_wavefront.hip's refill kernels skip the triangle phase of a ray that misses it)
     uint32_t root[pt::kNode8Words];
-    PT_HIP(hipMemcpyAsync(root, nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
+    if (T.num_chunks > 0) PT_HIP(hipMemcpyAsync(root, nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
     // lights that are loose emissive triangles: their sphere from the new vertices
     bool lights_moved = false;
     for (size_t i = 0; i < c->h_lights.size() && i < T.light_tri.size(); i++) {
@@ -1394,8 +1431,9 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
     if (lights_moved)
         PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
                               hipMemcpyHostToDevice, c->stream));
+    if (blas) if (const int rc = blas_refit_finish(c)) return rc;
     PT_HIP(hipStreamSynchronize(c->stream));
-    pt::tri_root_box(root, c->S.tri_box);
+    if (T.num_chunks > 0) pt::tri_root_box(root, c->S.tri_box);
     if (out_kernel_ms) {
         float ms = 0.f;
         PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
@@ -1407,12 +1445,12 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
 
 int pt_update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
                         const float* n2, const float* n3, double* out_kernel_ms) {
-    return update_triangles(ctx, num_triangles, v1, v2, v3, n1, n2, n3, false, 0, out_kernel_ms);
+    return update_triangles(ctx, num_triangles, v1, v2, v3, n1, n2, n3, false, 0, false, out_kernel_ms);
 }
 
 int pt_update_triangles_normals(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, int32_t mode,
                                 double* out_kernel_ms) {
-    return update_triangles(ctx, num_triangles, v1, v2, v3, nullptr, nullptr, nullptr, true, mode, out_kernel_ms);
+    return update_triangles(ctx, num_triangles, v1, v2, v3, nullptr, nullptr, nullptr, true, mode, false, out_kernel_ms);
 }
 
 int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3) {
@@ -1527,7 +1565,200 @@ int ensure_shapes_dev(Ctx* c, ShapesDev& D) {
     }
     return PT_OK;
 }
+// The current parameters (ShapeRefitTables) into their staged copies, on the context's stream
+int stage_shape_params(Ctx* c, const ShapesDev& D) {
+    const pt::ShapeRefitTables& T = c->shape_refit;
+    PT_HIP(shapes_copy(D.sphere_center, T.sphere_center, c->stream));
+    PT_HIP(shapes_copy(D.sphere_radius, T.sphere_radius, c->stream));
+    PT_HIP(shapes_copy(D.cube_min, T.cube_min, c->stream));
+    PT_HIP(shapes_copy(D.cube_max, T.cube_max, c->stream));
+    PT_HIP(shapes_copy(D.xf_matrix, T.xf_matrix, c->stream));
+    PT_HIP(shapes_copy(D.xf_inverse, T.xf_inverse, c->stream));
+    return PT_OK;
+}
+// The shape refit from the staged parameters
+int launch_shapes(Ctx* c, const ShapesDev& D) {
+    const pt::ShapeRefitTables& T = c->shape_refit;
+    const pt::ShapeParams P{T.num_spheres, T.num_cubes, T.num_transformed, D.sphere_center, D.sphere_radius,
+                            D.cube_min, D.cube_max, D.xf_matrix, D.xf_inverse};
+    PT_HIP(pt::launch_shape_refit(P, T.num_nodes, T.num_recs, T.num_heavy, (int64_t)T.level_off.size() - 1, T.level_off.data(),
+                                  D.level_nodes, (uint32_t*)const_cast<float4*>(c->S.ana_nodes),
+                                  (uint32_t*)const_cast<float4*>(c->S.ana_recs), (uint32_t*)const_cast<float4*>(c->S.ext_recs),
+                                  const_cast<pt::DevXform*>(c->S.xforms), (uint32_t*)const_cast<float4*>(c->S.heavy), D.xf_kind,
+                                  D.xf_index, D.xf_inner_box, D.xbox, D.rec_box, D.node_box, c->stream));
+    return PT_OK;
+}
+
+// The parts of Ctx::blas_dev, each 256-B aligned: [the tables | tri_box | node_box | block_part | blas_box]
+struct BlasDev {
+    int32_t* desc;
+    int32_t* src_of_pos;
+    uint32_t* level_nodes;
+    int32_t* level_blas;
+    int32_t* block_blas;
+    int32_t* block_first;
+    int32_t* blas_block_off;
+    int32_t* xf_blas;
+    float* tri_box;
+    float* node_box;
+    float* block_part;
+    float* blas_box;
+    size_t bytes;
+};
+// k_blas_bounds' blocks: each folds up to pt::blas_bounds_span() positions of one BLAS
+struct BlasBlocks {
+    std::vector<int32_t> blas, first, off;   // per block its BLAS and first position; per BLAS its first block (and the end)
+};
+void blas_blocks(const pt::BlasRefitTables& T, BlasBlocks& B) {
+    const int64_t span = pt::blas_bounds_span();
+    for (size_t b = 0; b < T.num_blas(); b++) {
+        B.off.push_back((int32_t)B.blas.size());
+        const int64_t r0 = T.desc[4 * b + 2], n = T.desc[4 * b + 3];
+        for (int64_t at = 0; at < n; at += span) {
+            B.blas.push_back((int32_t)b);
+            B.first.push_back((int32_t)(r0 + at));
+        }
+    }
+    B.off.push_back((int32_t)B.blas.size());
+}
+BlasDev blas_layout(const pt::BlasRefitTables& T, size_t num_blocks, void* base) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    BlasDev r{};
+    size_t at = 0;
+    char* p = (char*)base;
+    const size_t i4 = sizeof(int32_t), nb = T.num_blas();
+    r.desc = (int32_t*)(p + at); at += up(T.desc.size() * i4);
+    r.src_of_pos = (int32_t*)(p + at); at += up(T.src_of_pos.size() * i4);
+    r.level_nodes = (uint32_t*)(p + at); at += up(T.level_nodes.size() * i4);
+    r.level_blas = (int32_t*)(p + at); at += up(T.level_blas.size() * i4);
+    r.block_blas = (int32_t*)(p + at); at += up(num_blocks * i4);
+    r.block_first = (int32_t*)(p + at); at += up(num_blocks * i4);
+    r.blas_block_off = (int32_t*)(p + at); at += up((nb + 1) * i4);
+    r.xf_blas = (int32_t*)(p + at); at += up(T.xf_blas.size() * i4);
+    r.tri_box = (float*)(p + at); at += up((size_t)T.num_tris * 6 * sizeof(float));
+    r.node_box = (float*)(p + at); at += up((size_t)T.num_nodes * 6 * sizeof(float));
+    r.block_part = (float*)(p + at); at += up(num_blocks * 6 * sizeof(float));
+    r.blas_box = (float*)(p + at); at += up(nb * 6 * sizeof(float));
+    r.bytes = at + 256;   // never an empty allocation
+    return r;
+}
+// Ctx::blas_dev, allocated and its tables uploaded (on the context's stream) at the first use after an upload
+int ensure_blas_dev(Ctx* c, BlasDev& D) {
+    const pt::BlasRefitTables& T = c->blas_refit;
+    if (!c->blas_dev.ptr) {
+        BlasBlocks B;
+        blas_blocks(T, B);
+        D = blas_layout(T, B.blas.size(), nullptr);
+        if (hipMalloc(&c->blas_dev.ptr, D.bytes) != hipSuccess) {
+            c->blas_dev.ptr = nullptr;
+            (void)hipGetLastError();
+            return fail(PT_ERR_OUT_OF_MEMORY, "BLAS refit workspace allocation");
+        }
+        c->blas_dev.bytes = D.bytes;
+        c->blas_num_blocks = B.blas.size();
+        D = blas_layout(T, c->blas_num_blocks, c->blas_dev.ptr);
+        PT_HIP(shapes_copy(D.desc, T.desc, c->stream));
+        PT_HIP(shapes_copy(D.src_of_pos, T.src_of_pos, c->stream));
+        PT_HIP(shapes_copy(D.level_nodes, T.level_nodes, c->stream));
+        PT_HIP(shapes_copy(D.level_blas, T.level_blas, c->stream));
+        PT_HIP(shapes_copy(D.block_blas, B.blas, c->stream));
+        PT_HIP(shapes_copy(D.block_first, B.first, c->stream));
+        PT_HIP(shapes_copy(D.blas_block_off, B.off, c->stream));
+        PT_HIP(shapes_copy(D.xf_blas, T.xf_blas, c->stream));
+        PT_HIP(hipStreamSynchronize(c->stream));   // B's arrays go out of scope
+    }
+    D = blas_layout(T, c->blas_num_blocks, c->blas_dev.ptr);
+    return PT_OK;
+}
+
+int blas_refit_prepare(Ctx* c) {
+    ShapesDev S{};
+    if (const int rc = ensure_shapes_dev(c, S)) return rc;
+    BlasDev D{};
+    if (const int rc = ensure_blas_dev(c, D)) return rc;
+    return stage_shape_params(c, S);   // the shape refit the BLAS refit ends in runs from the current parameters
+}
+
+int blas_refit_launch(Ctx* c, int32_t num_triangles, const float* const in[6]) {
+    const pt::BlasRefitTables& T = c->blas_refit;
+    ShapesDev S{};
+    if (const int rc = ensure_shapes_dev(c, S)) return rc;
+    BlasDev D{};
+    if (const int rc = ensure_blas_dev(c, D)) return rc;
+    PT_HIP(pt::launch_blas_refit((int64_t)T.num_blas(), T.num_tris, T.num_nodes, num_triangles, (int64_t)T.xf_blas.size(),
+                                 (int64_t)c->blas_num_blocks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes,
+                                 D.level_blas, D.desc, D.src_of_pos, D.block_blas, D.block_first, D.blas_block_off, D.xf_blas,
+                                 (uint32_t*)const_cast<float4*>(c->S.blas_nodes), (uint32_t*)const_cast<float4*>(c->S.blas_recs),
+                                 (uint32_t*)const_cast<float4*>(c->S.blas_shade), in[0], in[1], in[2], in[3], in[4], in[5],
+                                 D.tri_box, D.node_box, D.block_part, D.blas_box, S.xf_inner_box, c->stream));
+    c->blas_boxes_on_device = true;
+    return launch_shapes(c, S);
+}
+
+int blas_refit_finish(Ctx* c) {
+    const pt::BlasRefitTables& T = c->blas_refit;
+    pt::ShapeRefitTables& ST = c->shape_refit;
+    BlasDev D{};
+    if (const int rc = ensure_blas_dev(c, D)) return rc;
+    std::vector<float> boxes(T.num_blas() * 6);
+    PT_HIP(hipMemcpyAsync(boxes.data(), D.blas_box, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));   // the lights below need the boxes
+    for (size_t t = 0; t < T.xf_blas.size() && 6 * t + 6 <= ST.xf_inner_box.size(); t++) {
+        const int64_t b = T.xf_blas[t];
+        if (b < 0 || (size_t)b >= T.num_blas()) continue;
+        std::memcpy(&ST.xf_inner_box[6 * t], &boxes[6 * (size_t)b], 6 * sizeof(float));
+    }
+    // lights that are transformed shapes over a mesh follow its box
+    if (pt::shape_refit_lights(ST, c->h_lights))
+        PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
+                              hipMemcpyHostToDevice, c->stream));
+    return PT_OK;
+}
 }  // namespace
+
+int pt_update_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms) {
+    if (!ctx) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!u) return fail(PT_ERR_INVALID_ARG, "update meshes: u is NULL");
+    if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "update meshes: reserved must be 0");
+    if (u->normals_mode != 0 && u->normals_mode != PT_NORMALS_FACE && u->normals_mode != PT_NORMALS_SMOOTH)
+        return fail(PT_ERR_INVALID_ARG, "update meshes: normals_mode " + std::to_string(u->normals_mode) + " is not 0 or a pt_normals_mode");
+    if (u->normals_mode != 0 && (u->n1 || u->n2 || u->n3))
+        return fail(PT_ERR_INVALID_ARG, "update meshes: n1/n2/n3 are given and normals_mode derives them");
+    return update_triangles(ctx, u->num_triangles, u->v1, u->v2, u->v3, u->n1, u->n2, u->n3, u->normals_mode != 0, u->normals_mode,
+                            true, out_kernel_ms);
+}
+
+int pt_read_blas(void* ctx, int64_t counts[3], int32_t* blas, uint32_t* nodes, uint32_t* recs, uint32_t* shade, float* inner_boxes) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::BlasRefitTables& T = c->blas_refit;
+    const size_t nb = T.num_blas();
+    if (counts) { counts[0] = (int64_t)nb; counts[1] = T.num_nodes; counts[2] = T.num_tris; }
+    PT_HIP(hipSetDevice(c->device));
+    const size_t word = sizeof(uint32_t);
+    if (blas && nb) PT_HIP(hipMemcpyAsync(blas, c->S.blas, nb * sizeof(pt::DevBlas), hipMemcpyDeviceToHost, c->stream));
+    if (nodes && T.num_nodes)
+        PT_HIP(hipMemcpyAsync(nodes, c->S.blas_nodes, (size_t)T.num_nodes * pt::kShapeNodeWords * word, hipMemcpyDeviceToHost, c->stream));
+    if (recs && T.num_tris)
+        PT_HIP(hipMemcpyAsync(recs, c->S.blas_recs, (size_t)T.num_tris * pt::kBlasRecWords * word, hipMemcpyDeviceToHost, c->stream));
+    if (shade && T.num_tris)
+        PT_HIP(hipMemcpyAsync(shade, c->S.blas_shade, (size_t)T.num_tris * pt::kBlasRecWords * word, hipMemcpyDeviceToHost, c->stream));
+    if (inner_boxes && nb) {
+        if (c->blas_boxes_on_device && c->blas_dev.ptr) {
+            const BlasDev D = blas_layout(T, c->blas_num_blocks, c->blas_dev.ptr);
+            PT_HIP(hipMemcpyAsync(inner_boxes, D.blas_box, nb * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        } else {   // no update yet: the upload's, from the host table
+            std::memset(inner_boxes, 0, nb * 6 * sizeof(float));
+            for (size_t t = 0; t < T.xf_blas.size() && 6 * t + 6 <= c->shape_refit.xf_inner_box.size(); t++) {
+                const int64_t b = T.xf_blas[t];
+                if (b >= 0 && (size_t)b < nb) std::memcpy(inner_boxes + 6 * b, &c->shape_refit.xf_inner_box[6 * t], 6 * sizeof(float));
+            }
+        }
+    }
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
 
 int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms) {
     Ctx* c = (Ctx*)ctx;
@@ -1568,20 +1799,9 @@ int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms)
         T.xf_matrix.assign(u->xform_matrix, u->xform_matrix + 16 * (size_t)T.num_transformed);
         T.xf_inverse.assign(u->xform_inverse, u->xform_inverse + 16 * (size_t)T.num_transformed);
     }
-    PT_HIP(shapes_copy(D.sphere_center, T.sphere_center, c->stream));
-    PT_HIP(shapes_copy(D.sphere_radius, T.sphere_radius, c->stream));
-    PT_HIP(shapes_copy(D.cube_min, T.cube_min, c->stream));
-    PT_HIP(shapes_copy(D.cube_max, T.cube_max, c->stream));
-    PT_HIP(shapes_copy(D.xf_matrix, T.xf_matrix, c->stream));
-    PT_HIP(shapes_copy(D.xf_inverse, T.xf_inverse, c->stream));
-    const pt::ShapeParams P{T.num_spheres, T.num_cubes, T.num_transformed, D.sphere_center, D.sphere_radius,
-                            D.cube_min, D.cube_max, D.xf_matrix, D.xf_inverse};
+    if (const int rc = stage_shape_params(c, D)) return rc;
     PT_HIP(hipEventRecord(c->ev0, c->stream));
-    PT_HIP(pt::launch_shape_refit(P, T.num_nodes, T.num_recs, T.num_heavy, (int64_t)T.level_off.size() - 1, T.level_off.data(),
-                                  D.level_nodes, (uint32_t*)const_cast<float4*>(c->S.ana_nodes),
-                                  (uint32_t*)const_cast<float4*>(c->S.ana_recs), (uint32_t*)const_cast<float4*>(c->S.ext_recs),
-                                  const_cast<pt::DevXform*>(c->S.xforms), (uint32_t*)const_cast<float4*>(c->S.heavy), D.xf_kind,
-                                  D.xf_index, D.xf_inner_box, D.xbox, D.rec_box, D.node_box, c->stream));
+    if (const int rc = launch_shapes(c, D)) return rc;
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     // lights that are spheres, cubes or transformed shapes: their sphere from the new parameters
     if (pt::shape_refit_lights(T, c->h_lights))

@@ -593,10 +593,21 @@ int Compiler::blases() {
             pack_tri_geom(d, src, &H.blas_recs[3 * (r0 + (size_t)t)]);
             pack_tri_shade(d, src, &H.blas_shade[3 * (r0 + (size_t)t)]);
             pack_tri_uv(d, src, &H.blas_uv[2 * (r0 + (size_t)t)]);
+            H.blas_refit.src_of_pos.push_back(src);
         }
+        const int32_t desc[4] = {B.node_off, B.num_nodes, B.rec_off, n};
+        H.blas_refit.desc.insert(H.blas_refit.desc.end(), desc, desc + 4);
         blas_of_mesh[(size_t)x.shape_index] = (int32_t)H.blas.size();
         H.blas.push_back(B);
     }
+    // what a later pt_update_meshes needs (BlasRefitTables)
+    BlasRefitTables& T = H.blas_refit;
+    T.num_nodes = (int64_t)(H.blas_nodes.size() / 8);
+    T.num_tris = (int64_t)(H.blas_recs.size() / 3);
+    blas_levels((const uint32_t*)H.blas_nodes.data(), T);
+    T.xf_blas.assign((size_t)std::max(d->num_transformed, 0), -1);
+    for (int i = 0; i < d->num_transformed; i++)
+        if (d->transformed[i].shape_kind == PT_SHAPE_MESH) T.xf_blas[(size_t)i] = blas_of_mesh[(size_t)d->transformed[i].shape_index];
     return PT_OK;
 }
 
@@ -964,6 +975,30 @@ void shape_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t
             }
         }
         begin = end;
+    }
+}
+
+void blas_levels(const uint32_t* nodes, BlasRefitTables& T) {
+    T.level_nodes.clear();
+    T.level_blas.clear();
+    T.level_off.assign(1, 0u);
+    std::vector<std::vector<uint32_t>> ln(T.num_blas()), lo(T.num_blas());
+    size_t depth = 0;
+    for (size_t b = 0; b < T.num_blas(); b++) {
+        const int64_t n0 = T.desc[4 * b], nn = T.desc[4 * b + 1];
+        if (n0 < 0 || nn < 0 || n0 + nn > T.num_nodes) { lo[b].assign(1, 0u); continue; }
+        shape_levels(nodes + (size_t)n0 * kNode4Words, nn, ln[b], lo[b]);
+        depth = std::max(depth, lo[b].size() - 1);
+    }
+    for (size_t l = 0; l < depth; l++) {
+        for (size_t b = 0; b < T.num_blas(); b++) {
+            if (l + 1 >= lo[b].size()) continue;
+            for (uint32_t q = lo[b][l]; q < lo[b][l + 1]; q++) {
+                T.level_nodes.push_back(ln[b][q]);
+                T.level_blas.push_back((int32_t)b);
+            }
+        }
+        T.level_off.push_back((uint32_t)T.level_nodes.size());
     }
 }
 

@@ -90,6 +90,22 @@ void box_light_sphere(const float* mn, const float* mx, DevLight& L);
 // when the scene has one.
 bool shape_refit_lights(const ShapeRefitTables& T, std::vector<DevLight>& lights);
 
+// What pt_update_meshes needs beside the device arrays to refit the BLASes of instanced meshes: host
+// tables kept from the upload.
+struct BlasRefitTables {
+    int64_t num_nodes = 0, num_tris = 0;   // BLAS nodes and BLAS triangle positions in total
+    std::vector<int32_t> desc;          // per BLAS four int32 (pt_blas_refit.h BlasDesc): node_off, num_nodes, rec_off, num_tris
+    std::vector<int32_t> src_of_pos;    // source triangle of BLAS triangle position i: mesh_first + order[i - rec_off]
+    std::vector<uint32_t> level_nodes;  // every BLAS's node indices (relative to its node_off) grouped by depth over all
+    std::vector<int32_t> level_blas;    // BLASes, the roots' level first; per entry its BLAS
+    std::vector<uint32_t> level_off;    // level l is entries [level_off[l], level_off[l + 1])
+    std::vector<int32_t> xf_blas;       // per transformed shape: the BLAS of its mesh, or -1
+    size_t num_blas() const { return desc.size() / 4; }
+};
+// Fills T.level_* from the BLASes' nodes (kNode4Words words each, all BLASes back to back) and T.desc: shape_levels'
+// breadth-first walk from each BLAS's node 0.
+void blas_levels(const uint32_t* nodes, BlasRefitTables& T);
+
 // A compiled scene on the host: every array pt_upload_scene uploads, and the DevScene with every
 // non-pointer field filled.
 struct HostScene {
@@ -119,6 +135,7 @@ struct HostScene {
     double tri_build_ms = 0;                        // host time to build (or wait for, or find) it
     RefitTables refit;
     ShapeRefitTables shape_refit;
+    BlasRefitTables blas_refit;
 };
 
 // Validates and compiles.  PT_OK, or an error code with its message in err (H is then partly filled; its

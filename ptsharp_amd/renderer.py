@@ -527,6 +527,83 @@ class Renderer:
                                                lights.ctypes.data_as(C.POINTER(C.c_double))), "pt_read_shape_bvh")
         return out[0], out[1], out[2], lights
 
+    def UpdateMeshes(self, v1, v2, v3, n1=None, n2=None, n3=None, normals=None) -> float:
+        """UpdateTriangles for a scene that may hold instanced meshes (pt_update_meshes; UpdateTriangles refuses
+        such a scene): new vertex positions for every triangle of the scene, instanced meshes' included, with the
+        normals given (n1..n3), kept, or derived on the device (normals="face" or "smooth").  The world triangle BVH
+        and every instanced mesh's BLAS are refitted on the device, the instances' boxes, the analytic BVH and the
+        lights follow; nothing is rebuilt or re-uploaded.  The arrays (and the derived normals, read back) are then
+        written into the uploaded FlatScene in place, so it describes what the device holds.  Returns the device time
+        of the kernels in ms."""
+        self._ensure_scene()
+        flat = self._uploaded
+        n = len(flat.tri_material)
+        if (n1 is None) != (n2 is None) or (n1 is None) != (n3 is None):
+            raise ValueError("n1, n2 and n3 must be all given or all None")
+        if normals is not None and n1 is not None:
+            raise ValueError("normals= derives the normals: n1, n2 and n3 cannot be given with it")
+        if normals not in (None, "face", "smooth"):
+            raise ValueError('normals is None, "face" or "smooth"')
+        arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (v1, v2, v3)]
+        if n1 is not None:
+            arrs += [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (n1, n2, n3)]
+        if any(len(a) != n for a in arrs):
+            raise ValueError(f"the scene has {n} triangles")
+        fp = C.POINTER(C.c_float)
+        u = _abi.pt_mesh_update()
+        u.num_triangles = n
+        u.normals_mode = 0 if normals is None else _abi.NORMALS_FACE if normals == "face" else _abi.NORMALS_SMOOTH
+        for name, a in zip(("v1", "v2", "v3", "n1", "n2", "n3"), arrs):
+            setattr(u, name, a.ctypes.data_as(fp))
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_update_meshes(self._ctx, C.byref(u), C.byref(ms)), "pt_update_meshes")
+        if normals is not None:
+            arrs += self._derived_normals(arrs)
+        for dst, a in zip((flat.tri_v1, flat.tri_v2, flat.tri_v3, flat.tri_n1, flat.tri_n2, flat.tri_n3), arrs):
+            dst[...] = a
+        return float(ms.value)
+
+    def _derived_normals(self, verts):
+        """The normals the device derived, in the scene's order: pt_read_tri_normals', and for the triangles of
+        instanced meshes (zeros there unless the mesh is a top-level shape too) the BLAS shade rows, matched to their
+        source triangles by the geometry rows, which hold {v1, v2 - v1, v3 - v1} exactly."""
+        flat = self._uploaded
+        out = [a.copy() for a in self.ReadTriNormals()]
+        blas, _, recs, shade, _ = self.ReadBlas()
+        meshes = []   # the BLASes' meshes, in the compile's order: first use by a transformed shape
+        for x in flat.transformed[:flat.counts_ext[3]]:
+            if x.shape_kind == 4 and x.shape_index not in meshes:
+                meshes.append(x.shape_index)
+        v1, v2, v3 = verts[:3]
+        for b, j in enumerate(meshes[:len(blas)]):
+            f, cnt, r0 = int(flat.mesh_first[j]), int(flat.mesh_count[j]), int(blas[b, 2])
+            at = {recs[r0 + t, :9].tobytes(): r0 + t for t in range(cnt)}
+            keys = np.concatenate([v1[f:f + cnt], v2[f:f + cnt] - v1[f:f + cnt], v3[f:f + cnt] - v1[f:f + cnt]],
+                                  axis=1).astype(np.float32).view(np.uint32)
+            for t in range(cnt):
+                pos = at.get(keys[t].tobytes())
+                if pos is not None:
+                    nn = shade[pos, :9].view(np.float32)
+                    out[0][f + t], out[1][f + t], out[2][f + t] = nn[0:3], nn[3:6], nn[6:9]
+        return out
+
+    def ReadBlas(self):
+        """The context's BLASes, the object-space BVHs of instanced meshes, as they stand on the device
+        (pt_read_blas): (blas [B, 4] int32: first node, nodes, first triangle, 0; nodes [N, 32], recs [T, 12] and
+        shade [T, 12], all uint32; the meshes' unpadded boxes [B, 6] float32)."""
+        self._ensure_scene()
+        counts = (C.c_int64 * 3)()
+        _abi.check(self._lib.pt_read_blas(self._ctx, counts, None, None, None, None, None), "pt_read_blas")
+        nb, nn, nt = (int(c) for c in counts)
+        blas = np.zeros((nb, 4), np.int32)
+        nodes, recs, shade = np.zeros((nn, 32), np.uint32), np.zeros((nt, 12), np.uint32), np.zeros((nt, 12), np.uint32)
+        boxes = np.zeros((nb, 6), np.float32)
+        up = C.POINTER(C.c_uint32)
+        _abi.check(self._lib.pt_read_blas(self._ctx, counts, blas.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          nodes.ctypes.data_as(up), recs.ctypes.data_as(up), shade.ctypes.data_as(up),
+                                          boxes.ctypes.data_as(C.POINTER(C.c_float))), "pt_read_blas")
+        return blas, nodes, recs, shade, boxes
+
     def ResetBuffer(self) -> None:
         _abi.check(self._lib.pt_reset_buffer(self._ctx), "pt_reset_buffer")
         self._pass = 0

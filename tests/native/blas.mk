@@ -1,0 +1,27 @@
+# The BLAS refit check (blas_check.cpp: ptsharp_amd/csrc/pt_blas_refit.h driven on the host against the scene
+# compile), with scene_compile_check's flags, and once more under AddressSanitizer + UndefinedBehaviorSanitizer.
+#   make -f blas.mk            _build/blas_check
+#   make -f blas.mk asan       _build/blas_check_asan
+CXX ?= g++
+OUT := _build
+CSRC := ../../ptsharp_amd/csrc
+ROCM ?= /opt/rocm
+HIPINC := -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Wno-unknown-pragmas -Wno-attributes
+DEPS := blas_check.cpp scene_fixture.h $(CSRC)/pt_blas_refit.h $(CSRC)/pt_shape_refit.h $(CSRC)/pt_refit.h $(CSRC)/pt_scene_compile.cpp \
+        $(CSRC)/pt_scene_compile.h $(CSRC)/pt_scene.h $(CSRC)/pt_ext.h $(CSRC)/pt_math.h $(CSRC)/pt_bvh.cpp $(CSRC)/pt_bvh.h \
+        ../../include/ptsharp_hip.h blas.mk
+SRC := blas_check.cpp $(CSRC)/pt_scene_compile.cpp $(CSRC)/pt_bvh.cpp
+FLAGS := -std=c++17 -O2 -ffp-contract=off -fno-fast-math -pthread -Wall $(HIPINC)
+
+blas_check: $(OUT)/blas_check
+asan: $(OUT)/blas_check_asan
+
+$(OUT)/blas_check: $(DEPS)
+	@mkdir -p $(OUT)
+	$(CXX) $(FLAGS) -o $@ $(SRC)
+
+$(OUT)/blas_check_asan: $(DEPS)
+	@mkdir -p $(OUT)
+	$(CXX) $(FLAGS) -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $(SRC)
+
+.PHONY: blas_check asan
