@@ -216,6 +216,15 @@ __device__ __forceinline__ void halves(float w, float& a, float& b) {
 __device__ __forceinline__ uint32_t node8_ref(uint32_t k, uint32_t nin, uint32_t base_in, uint32_t leaf0) {
     return k < nin ? base_in + k : leaf0 + k;
 }
+// The offset (origin - o) / d of an axis, given its step / d.  Where a direction component is tiny but not 0
+// (|d| below about 1e-38 |origin - o|: 1e-38 itself, or 1e-33 in a scene of 1e6 units) the offset overflows to
+// +-inf while step / d stays finite; every fma of that axis would then be the same infinity, and the children that
+// hold the ray's plane would miss with all the others.  Such an offset says nothing about any child, so it becomes
+// NaN and the axis drops out of fminf / fmaxf, which only widens the interval (as slab1's NaN slabs do).  With
+// step / d infinite as well (d = 0) the products already sort themselves: inf - inf is NaN, inf + inf a true miss.
+__device__ __forceinline__ float node8_offset(float a, float b) {
+    return (__builtin_isinf(a) && !__builtin_isinf(b)) ? __int_as_float(0x7fc00000) : a;
+}
 // KEYED (the closest-hit refill kernels, pt_wavefront.hip trace_lanes): a pushed entry carries the top bits of
 // its entry distance under key_mask (pt_stack_key.h), so the pop can cull it against the bound of that time;
 // the descended child's ref is bare.  A missed slot's entry is written with a garbage key and never kept.
@@ -226,8 +235,9 @@ __device__ __forceinline__ bool node8_step(float4 q0, float4 q1, float4 q2, floa
     const uint32_t hdr = __float_as_uint(q0.w);
     const float sx = __uint_as_float((hdr & 0xFFu) << 23), sy = __uint_as_float(((hdr >> 8) & 0xFFu) << 23);
     const float sz = __uint_as_float(((hdr >> 16) & 0xFFu) << 23);
-    const float ax = (q0.x - o.x) * invd.x, ay = (q0.y - o.y) * invd.y, az = (q0.z - o.z) * invd.z;
     const float bx = sx * invd.x, by = sy * invd.y, bz = sz * invd.z;
+    const float ax = node8_offset((q0.x - o.x) * invd.x, bx), ay = node8_offset((q0.y - o.y) * invd.y, by);
+    const float az = node8_offset((q0.z - o.z) * invd.z, bz);
     const bool fx = invd.x < 0.f, fy = invd.y < 0.f, fz = invd.z < 0.f;   // the near bound is hi on that axis
     const float4 nx = fx ? q3 : q2, gx = fx ? q2 : q3;
     const float4 ny = fy ? q5 : q4, gy = fy ? q4 : q5;
@@ -418,13 +428,15 @@ __device__ __forceinline__ bool traverse(const DevScene& S, const float4* __rest
 // triangles, so an inner step and a leaf step read the same 128-B line's 16-B pieces and a
 // wave whose lanes are split between nodes and leaves pays for one set of load
 // instructions, not for the node loads plus a per-triangle load loop.
+// far_cull = false (pt_occluded, with ANY): as traverse's.  A triangle's fp32 hit distance can fall short of the
+// entry distance of its own padded box too (by 1e-5 of it at coordinates of 1e6, for a ray that grazes an edge).
 template <bool COUNT, bool ANY, class STK>
 __device__ __forceinline__ bool traverse_tri(const DevScene& S, v3 o, v3 d, v3 invd, HitRec& best, const STK& stack,
-                                             Counters& ctr) {
+                                             Counters& ctr, bool far_cull = true) {
     if (S.tri_num_nodes <= 0) return false;
     uint32_t ref = 0;  // root: always an inner node
     int sp = 0;
-    float tmax = tmax_bound(best.t);
+    float tmax = far_cull ? tmax_bound(best.t) : __int_as_float(0x7f7fffff);
     for (;;) {
         const bool leaf = (ref & 0x80000000u) != 0;
         const float4* c = (leaf ? S.tri_chunks : S.tri_nodes) + 8 * (size_t)(ref & 0x1FFFFFFFu);
@@ -868,7 +880,7 @@ __device__ __forceinline__ bool any_nearer(const DevScene& S, v3 o, v3 d, double
                                                  ctr, FULL ? &pend : nullptr, nullptr, far_cull)) {
         return true;
     }
-    if (traverse_tri<COUNT, true>(S, o, d, invd, best, stack, ctr)) return true;
+    if (traverse_tri<COUNT, true>(S, o, d, invd, best, stack, ctr, far_cull)) return true;
     if (FULL) {   // the lanes still unblocked march their pending Volume together
         bool blocked = false;
         march_pending<true, COUNT>(S, o, d, pend, best, &blocked);

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(kBlock) void k_render_pass(DevScene S, DevCamera ca
 // Scene.Intersect (Scene.cs:75-79) of a host's rays (pt_intersect), or the any-hit shadow query against
 // a given t (pt_occluded, light_visible's any_nearer): one lane per ray, the megakernel's trace() with its
 // LDS stack.  S.coop_min_lanes (set by the host) picks how a pending Volume is marched.  The any-hit query walks
-// the analytic BVH without the cull against t (pt_device.h traverse, far_cull).
+// both BVHs without the cull against t (pt_device.h traverse and traverse_tri, far_cull).
 template <bool FULL, bool ANY>
 __global__ __launch_bounds__(kBlock) void k_intersect(DevScene S, uint32_t n, const float* __restrict__ o3,
                                                       const float* __restrict__ d3, const double* __restrict__ tl,

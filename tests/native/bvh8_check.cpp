@@ -7,7 +7,9 @@
 //   * the device's slab arithmetic (pt_device.h node8_step: fma(q, step/d, (origin - o)/d) in fp32, near /
 //     far by direction sign, the far distance widened by 2^-21 relative) restated here: a ray whose exact
 //     fp64 slab test enters a primitive's box before tmax also enters every quantized box on that
-//     primitive's path — the quantized tree never culls a box the exact one keeps.
+//     primitive's path — the quantized tree never culls a box the exact one keeps.  Every 7th ray has a
+//     direction component of 0, every 11th a tiny one (1e-30 .. 1e-45, both signs), at which the offset
+//     (origin - o) / d overflows (node8_offset).
 // usage: bvh8_check [rays_per_case]      exit 0 = every check held
 #include <cmath>
 #include <cstdint>
@@ -51,7 +53,9 @@ static bool slab8(const uint32_t* w, int k, const float o[3], const float invd[3
         uint32_t sb = eb << 23;
         float s;
         std::memcpy(&s, &sb, 4);
-        const float a = (org - o[ax]) * invd[ax], b = s * invd[ax];
+        float a = (org - o[ax]) * invd[ax];
+        const float b = s * invd[ax];
+        if (std::isinf(a) && !std::isinf(b)) a = NAN;   // node8_offset: an overflowed offset beside a finite step
         const bool flip = invd[ax] < 0.f;
         const float qn = q_of(w, flip ? 12 + 8 * ax : 8 + 8 * ax, k), qf = q_of(w, flip ? 8 + 8 * ax : 12 + 8 * ax, k);
         tns[ax] = std::fmaf(qn, b, a);
@@ -188,7 +192,12 @@ static void run_case(const char* name, std::vector<float>& lo, std::vector<float
         if (r % 7 == 0) d[r % 3] = 0.f;   // a zero direction component
         const float len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
         if (len == 0.f) continue;
-        for (int k = 0; k < 3; k++) { d[k] /= len; invd[k] = 1.f / d[k]; }
+        for (int k = 0; k < 3; k++) d[k] /= len;
+        if (r % 11 == 0) {   // a tiny direction component: (origin - o) / d overflows, step / d may not
+            static const float tiny[] = {1e-38f, -1e-38f, 1.2e-38f, -3e-39f, 1e-45f, -1e-36f, 1e-30f};
+            d[(r / 11) % 3] = tiny[(r / 33) % 7];
+        }
+        for (int k = 0; k < 3; k++) invd[k] = 1.f / d[k];
         const float tmax = (r % 2) ? INFINITY : (float)(0.1 + 3.0 * U(rng));
         // a sample of primitives: the target and 64 random ones
         for (int j = 0; j < 65; j++) {

@@ -184,7 +184,8 @@ def test_bytes_after_a_pose(gpu, name):
 
 # ------------------------------------------------------------------ 3. rays
 def rays_at(lo, hi, n, seed):
-    """Rays from a shell around the box [lo, hi] to points inside it, and a few along the axes."""
+    """Rays from a shell around the box [lo, hi] to points inside it (rays along the axes, in the boxes' planes and
+    through vertices are tests/degenerate_rays.py's)."""
     rng = np.random.default_rng(seed)
     c, ext = (lo + hi) / 2, np.maximum((hi - lo) / 2, 0.5)
     u = rng.standard_normal((n, 3))
