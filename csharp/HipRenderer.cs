@@ -203,6 +203,16 @@ namespace PTSharpCore
             public IntPtr n1, n2, n3;      // [n][3] float; only with normals_mode 0
         }
 
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_mesh_pose
+        {
+            public int num_meshes;         // must equal the uploaded scene's num_meshes
+            public int normals_mode;       // 0: Mesh.Transform's (MulDirection of the rest normals); PT_NORMALS_FACE; PT_NORMALS_SMOOTH
+            public fixed int reserved[2];  // 0
+            public IntPtr matrices;        // [num_meshes][16] double, row-major, required
+            public IntPtr mesh_mask;       // [num_meshes] int or null (= all); 0: the mesh takes its rest values verbatim
+        }
+
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_get_version();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_device_count(out int count);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_create(ref pt_device_opts opts, out IntPtr ctx);
@@ -239,6 +249,10 @@ namespace PTSharpCore
         // pt_update_triangles / _normals for a scene with instanced meshes too: their BLASes refitted on the device
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_meshes(IntPtr ctx, ref pt_mesh_update u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_blas(IntPtr ctx, long[] counts, int[] blas, uint[] nodes, uint[] recs, uint[] shade, float[] innerBoxes);
+        // Mesh.Transform on the device: a rest pose kept there, one matrix per mesh per call, then pt_update_meshes' refits
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_set_rest_pose(IntPtr ctx, int numTriangles, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_pose_meshes(IntPtr ctx, ref pt_mesh_pose u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_pose(IntPtr ctx, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr pt_last_error();
@@ -749,6 +763,52 @@ namespace PTSharpCore
             {
                 foreach (var h in held) h.Free();
             }
+        }
+
+        /// <summary>Installs the rest pose PoseMeshes poses from (pt_set_rest_pose): positions and normals of every
+        /// triangle of the uploaded scene, kept on the device until the next upload.</summary>
+        public void SetRestPose(float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3)
+        {
+            if (!uploaded) Upload();
+            PtHip.Check(PtHip.pt_set_rest_pose(ctx, v1.Length / 3, v1, v2, v3, n1, n2, n3), "pt_set_rest_pose");
+        }
+
+        /// <summary>Mesh.Transform(matrices[j]) of every mesh j of the uploaded scene on the device, from the rest pose
+        /// SetRestPose installed (pt_pose_meshes): matrices holds 16 doubles per mesh, row-major, in the scene's mesh
+        /// order; mask (optional, one int per mesh) is 0 for a mesh that takes its rest values.  normalsMode 0
+        /// transforms the rest normals as Mesh.Transform does, PtHip.PT_NORMALS_FACE or PT_NORMALS_SMOOTH derives
+        /// them from the posed positions.  The BVHs, the instances' boxes and the lights follow as in UpdateMeshes.
+        /// Returns the device time of the kernels in ms.</summary>
+        public double PoseMeshes(double[] matrices, int[] mask = null, int normalsMode = 0)
+        {
+            if (!uploaded) Upload();
+            var hm = GCHandle.Alloc(matrices, GCHandleType.Pinned);
+            var hk = mask == null ? default(GCHandle) : GCHandle.Alloc(mask, GCHandleType.Pinned);
+            try
+            {
+                var u = new PtHip.pt_mesh_pose
+                {
+                    num_meshes = matrices.Length / 16, normals_mode = normalsMode,
+                    matrices = hm.AddrOfPinnedObject(), mesh_mask = mask == null ? IntPtr.Zero : hk.AddrOfPinnedObject(),
+                };
+                PtHip.Check(PtHip.pt_pose_meshes(ctx, ref u, out double ms), "pt_pose_meshes");
+                return ms;
+            }
+            finally
+            {
+                hm.Free();
+                if (mask != null) hk.Free();
+            }
+        }
+
+        /// <summary>The six arrays the last PoseMeshes left on the device (pt_read_pose), 3 floats per triangle each:
+        /// v1, v2, v3, n1, n2, n3, derived normals included.</summary>
+        public float[][] ReadPose(int numTriangles)
+        {
+            var a = new float[6][];
+            for (int k = 0; k < 6; k++) a[k] = new float[numTriangles * 3];
+            PtHip.Check(PtHip.pt_read_pose(ctx, a[0], a[1], a[2], a[3], a[4], a[5]), "pt_read_pose");
+            return a;
         }
 
         /// <summary>The context's BLASes as they stand on the device (pt_read_blas): 4 ints per BLAS, 32 words per

@@ -23,7 +23,10 @@
  *   pt_update_meshes   (new) pt_update_triangles / _normals for a scene with  Mesh.cs:88-120 (Mesh.BoundingBox),
  *   / pt_read_blas     instanced meshes too: their BLASes refitted on the   TransformedShape.cs:36-39
  *                      device, the instances' boxes and lights following
- *   pt_render_pass     one Renderer.RenderParallel() pass                  Renderer.cs:199-338
+ *   pt_set_rest_pose   (new) Mesh.Transform(matrix) of every mesh of the      Mesh.cs:254-274 (Mesh.Transform; MoveTo
+ *   / pt_pose_meshes   uploaded scene on the device, from a rest pose kept    and FitInside, Mesh.cs:237-252, end in it),
+ *   / pt_read_pose     there: one matrix per mesh per call, then the refits   Matrix.cs:134-150
+ *   pt_render_pass    one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
  *                        → Scene.Intersect → Tree/IShape.Intersect        Scene.cs:75-79, Tree.cs:31-128
@@ -658,6 +661,51 @@ int pt_update_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms);
  * pt_read_tri_normals; its normals are in shade.  Any argument but ctx may be NULL.  Synchronises and changes
  * nothing.  A NULL ctx: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_read_blas(void* ctx, int64_t counts[3], int32_t* blas, uint32_t* nodes, uint32_t* recs, uint32_t* shade, float* inner_boxes);
+
+/* Posing meshes by matrix on the device: Mesh.Transform (Mesh.cs:254-274) of every mesh of the
+ * uploaded scene, top-level, instanced or both, from a rest pose kept on the device, so that a frame sends one 4x4
+ * matrix per mesh and not every vertex.
+ *
+ * pt_set_rest_pose installs the rest pose: positions and normals of every triangle, pt_scene_desc order, copied to a
+ * device buffer (72 B per triangle) kept until the next pt_upload_scene.  All six arrays are required.  It changes
+ * nothing a ray sees.  Errors: a NULL ctx or array, num_triangles different from the uploaded scene's:
+ * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; the buffer not allocated: PT_ERR_OUT_OF_MEMORY. */
+int pt_set_rest_pose(void* ctx, int32_t num_triangles,
+                     const float* v1, const float* v2, const float* v3,
+                     const float* n1, const float* n2, const float* n3);
+/* pt_pose_meshes poses the rest pose and refits.  A source triangle belongs to the last mesh_first / mesh_count range
+ * of the uploaded pt_scene_desc that contains it (as for PT_NORMALS_SMOOTH), or to none (a loose triangle).  The
+ * triangles of an unmasked mesh g get V' = Matrix.MulPosition(matrices[g], V_rest) and, with normals_mode 0,
+ * N' = Matrix.MulDirection(matrices[g], N_rest): Matrix.cs:134-150 exactly, fp64 products summed left to right, one
+ * conversion to fp32, then the fp32 Normalize (the fourth row of a matrix is not read).  Loose triangles and the
+ * triangles of a masked mesh take their rest values bit for bit.  With PT_NORMALS_FACE or PT_NORMALS_SMOOTH the
+ * normals of every triangle are derived from the posed positions as pt_update_meshes derives them; the mask then
+ * governs positions only.  A pose is always made from the rest pose, never from the current state: repeated poses do
+ * not drift, a pose after a pt_update_* discards that update's geometry, a later pt_update_* overwrites the pose.
+ * The posed arrays then go through what pt_update_meshes runs, so everything on the device is, word for word, what
+ * pt_update_meshes with the same arrays computed on the host, normals given, leaves: the world triangle BVH, every
+ * BLAS, the meshes' inner boxes, the instances' world boxes, the analytic BVH, the boxes the routed split tests and the
+ * lights (a light that is a loose emissive triangle returns to its rest vertices).  An instanced mesh is posed in its
+ * object space; its instance matrix stays pt_update_shapes' business, and the two compose in either order.  Runs on the
+ * context's stream after every pass issued before it and synchronises before returning; the Buffer, the pass state
+ * and the counters are untouched; out_kernel_ms (may be NULL) covers the pose kernel, the normals kernels and the
+ * refits.  Non-finite values: boxes (and derived normals) are unspecified; no access leaves its array.
+ * Errors (nothing launched, the scene untouched): a NULL ctx, u or matrices, reserved != 0, a normals_mode outside
+ * {0, 1, 2}, num_meshes different from the uploaded scene's, no rest pose installed: PT_ERR_INVALID_ARG; no scene:
+ * PT_ERR_NO_SCENE; a workspace not allocated: PT_ERR_OUT_OF_MEMORY; PT_NORMALS_SMOOTH with 3 * num_triangles >= 2^31:
+ * PT_ERR_UNSUPPORTED.  A scene with no triangle in any BVH: PT_OK, nothing launched. */
+typedef struct pt_mesh_pose {
+    int32_t num_meshes;        /* must equal the uploaded scene's num_meshes */
+    int32_t normals_mode;      /* 0: Mesh.Transform's (MulDirection of the rest normals); PT_NORMALS_FACE; PT_NORMALS_SMOOTH */
+    int32_t reserved[2];       /* 0 */
+    const double* matrices;    /* [num_meshes][16] row-major, required */
+    const int32_t* mesh_mask;  /* [num_meshes] or NULL (= all); 0: the mesh takes its rest values verbatim */
+} pt_mesh_pose;
+int pt_pose_meshes(void* ctx, const pt_mesh_pose* u, double* out_kernel_ms);
+/* The six arrays the last pt_pose_meshes left staged on the device (derived normals included), [n][3] each in
+ * pt_scene_desc order; any pointer may be NULL.  They stay until a pt_update_* or pt_read_tri_normals reuses the
+ * staged arrays.  A NULL ctx, or no pose staged: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n2, float* n3);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

@@ -147,6 +147,11 @@ class pt_mesh_update(C.Structure):
                 ("v1", _f), ("v2", _f), ("v3", _f), ("n1", _f), ("n2", _f), ("n3", _f)]
 
 
+class pt_mesh_pose(C.Structure):
+    _fields_ = [("num_meshes", C.c_int32), ("normals_mode", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("matrices", _d), ("mesh_mask", _i)]
+
+
 class pt_trace_counters(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
                 ("shading_fetches", C.c_uint64), ("shadow_rays", C.c_uint64), ("shadow_nodes", C.c_uint64),
@@ -179,6 +184,9 @@ SIGNATURES = {
     "pt_update_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_update), _d]),
     "pt_read_blas": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), _i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                C.POINTER(C.c_uint32), _f]),
+    "pt_set_rest_pose": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, _f, _f, _f]),
+    "pt_pose_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_pose), _d]),
+    "pt_read_pose": (C.c_int, [C.c_void_p, _f, _f, _f, _f, _f, _f]),
     "pt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_sampler), C.POINTER(pt_pass_params)]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_reset_buffer": (C.c_int, [C.c_void_p]),

@@ -122,6 +122,9 @@ hipError_t launch_normals(bool smooth, int64_t n, const float* v1, const float* 
                           uint32_t* vals_a, uint32_t* vals_b, void* temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_normals_gather(int64_t num_pos, const uint32_t* recs, const int32_t* src_of_pos, float* n1, float* n2,
                                  float* n3, hipStream_t stream);
+// pt_pose.hip
+hipError_t launch_pose(int64_t n, int32_t num_meshes, const int32_t* group, const int32_t* mask, const double* matrices,
+                       bool normals, const float* const rest[6], float* const out[6], hipStream_t stream);
 }
 
 namespace {
@@ -264,6 +267,12 @@ struct Ctx {
     DeviceArray blas_dev;
     size_t blas_num_blocks = 0;          // blocks of the bounds kernel (blas_dev's block tables)
     bool blas_boxes_on_device = false;   // blas_dev holds the meshes' boxes (after the first pt_update_meshes)
+    // pt_pose_meshes: the rest pose (six arrays), the triangles' groups and a call's matrices and mask, one allocation
+    // that comes with pt_set_rest_pose and goes with the scene; the rest vertices of the lights that are loose
+    // triangles (9 floats per h_lights entry) stay on the host
+    DeviceArray pose_dev;
+    std::vector<float> rest_light_verts;
+    bool pose_staged = false;            // refit_dev's staged arrays hold the last pt_pose_meshes' (pt_read_pose)
 };
 
 #ifndef PT_VOL_DEFER
@@ -444,6 +453,9 @@ void free_scene(Ctx* c) {
     c->blas_num_blocks = 0;
     c->blas_boxes_on_device = false;
     c->blas_refit = pt::BlasRefitTables{};
+    c->pose_dev.release();
+    c->rest_light_verts.clear();
+    c->pose_staged = false;
     c->refit = pt::RefitTables{};
     c->h_lights.clear();
     c->has_blas = false;
@@ -1348,15 +1360,26 @@ int blas_refit_prepare(Ctx* c);
 int blas_refit_launch(Ctx* c, int32_t num_triangles, const float* const in[6]);
 int blas_refit_finish(Ctx* c);
 
-// pt_update_triangles (mode 0: the normals given, or kept), pt_update_triangles_normals (mode: a pt_normals_mode) and
-// pt_update_meshes (meshes: instanced meshes are refitted too, not refused)
-int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
-                     const float* n2, const float* n3, bool derive, int32_t mode, bool meshes, double* out_kernel_ms) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
-    if (!v1 || !v2 || !v3) return fail(PT_ERR_INVALID_ARG, "update: v1, v2 and v3 are required");
-    if ((n1 != nullptr) != (n2 != nullptr) || (n1 != nullptr) != (n3 != nullptr))
-        return fail(PT_ERR_INVALID_ARG, "update: n1/n2/n3 must be all set or all NULL");
+// What an update runs from, made by update_prepare before anything is staged
+struct UpdateDev {
+    RefitDev D;
+    NormalsDev N;
+    bool blas, smooth;
+};
+// The vertices of the lights that are loose emissive triangles: the caller's arrays (in pt_scene_desc order), or with
+// `kept` the rest vertices pt_set_rest_pose kept, 9 floats per light
+struct LightVerts {
+    const float *v1, *v2, *v3;
+    const float* kept;
+};
+
+// The first part of pt_update_triangles, pt_update_triangles_normals, pt_update_meshes (meshes: instanced meshes are
+// refitted too, not refused) and pt_pose_meshes, after their own argument checks: the checks against the scene, then
+// every workspace, before the first copy (a failed allocation leaves the scene untouched).  *launch is false when
+// the scene holds no triangle in any BVH: PT_OK, nothing to run.
+int update_prepare(Ctx* c, int32_t num_triangles, bool derive, int32_t mode, bool meshes, double* out_kernel_ms, UpdateDev& U,
+                   bool* launch) {
+    *launch = false;
     if (derive && mode != PT_NORMALS_FACE && mode != PT_NORMALS_SMOOTH)
         return fail(PT_ERR_INVALID_ARG, "update: mode " + std::to_string(mode) + " is not a pt_normals_mode");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
@@ -1368,50 +1391,55 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
         return fail(PT_ERR_UNSUPPORTED, "update: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
                                         "its BLAS is not refitted");
     if (out_kernel_ms) *out_kernel_ms = 0.0;
-    const bool blas = c->has_blas && num_triangles > 0;
-    if (T.num_chunks == 0 && !blas) return PT_OK;   // no triangle in a BVH (num_triangles == 0, or none of them in Scene.Shapes)
+    U.blas = c->has_blas && num_triangles > 0;
+    if (T.num_chunks == 0 && !U.blas) return PT_OK;   // no triangle in a BVH (num_triangles == 0, or none of them in Scene.Shapes)
     PT_HIP(hipSetDevice(c->device));
-    const bool smooth = derive && mode == PT_NORMALS_SMOOTH;
-    if (smooth && (int64_t)num_triangles * 3 > (int64_t)INT32_MAX)
+    U.smooth = derive && mode == PT_NORMALS_SMOOTH;
+    if (U.smooth && (int64_t)num_triangles * 3 > (int64_t)INT32_MAX)
         return fail(PT_ERR_UNSUPPORTED, "update: PT_NORMALS_SMOOTH numbers corners in 31 bits");
     PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
-    // both workspaces before the first copy: a failed allocation leaves the scene untouched
-    NormalsDev N{};
-    if (smooth) {
+    U.N = NormalsDev{};
+    if (U.smooth) {
         const bool first = !c->normals_dev.ptr;
         if (first) {
             size_t temp = 0;
             PT_HIP(pt::normals_sort_temp_bytes((int64_t)num_triangles * 3, T.num_groups, &temp));
-            N = normals_layout(T, temp, nullptr);
-            if (hipMalloc(&c->normals_dev.ptr, N.bytes) != hipSuccess) {
+            U.N = normals_layout(T, temp, nullptr);
+            if (hipMalloc(&c->normals_dev.ptr, U.N.bytes) != hipSuccess) {
                 c->normals_dev.ptr = nullptr;
                 (void)hipGetLastError();
                 return fail(PT_ERR_OUT_OF_MEMORY, "normals workspace allocation");
             }
-            c->normals_dev.bytes = N.bytes;
+            c->normals_dev.bytes = U.N.bytes;
             c->normals_temp_bytes = temp;
         }
-        N = normals_layout(T, c->normals_temp_bytes, c->normals_dev.ptr);
+        U.N = normals_layout(T, c->normals_temp_bytes, c->normals_dev.ptr);
         if (first)
-            PT_HIP(hipMemcpyAsync(N.group, T.tri_group.data(), T.tri_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            PT_HIP(hipMemcpyAsync(U.N.group, T.tri_group.data(), T.tri_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
-    RefitDev D{};
-    if (const int rc = ensure_refit_dev(c, D)) return rc;
-    if (blas) if (const int rc = blas_refit_prepare(c)) return rc;
-    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
-    const float* src[6] = {v1, v2, v3, n1, n2, n3};
-    for (int k = 0; k < (n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
+    if (const int rc = ensure_refit_dev(c, U.D)) return rc;
+    if (U.blas) if (const int rc = blas_refit_prepare(c)) return rc;
+    *launch = true;
+    return PT_OK;
+}
+
+// The second part, from the arrays staged in U.D.in on the context's stream after Ctx::ev0 was recorded there: the
+// normals when they are derived, the refit of the world triangle BVH, the BLAS path, the root box, the lights, the
+// timing.  normals: U.D.in[3..5] hold normals, given or to be derived (false: the device's are kept).
+int update_run(Ctx* c, const UpdateDev& U, int32_t num_triangles, bool derive, bool normals, const LightVerts& L,
+               double* out_kernel_ms) {
+    const pt::RefitTables& T = c->refit;
+    const RefitDev& D = U.D;
+    const NormalsDev& N = U.N;
     uint32_t* nodes = (uint32_t*)const_cast<float4*>(c->S.tri_nodes);
-    PT_HIP(hipEventRecord(c->ev0, c->stream));
     if (derive)
-        PT_HIP(pt::launch_normals(smooth, num_triangles, D.in[0], D.in[1], D.in[2], D.in[3], D.in[4], D.in[5], N.group, T.num_groups,
+        PT_HIP(pt::launch_normals(U.smooth, num_triangles, D.in[0], D.in[1], D.in[2], D.in[3], D.in[4], D.in[5], N.group, T.num_groups,
                                   N.keys[0], N.keys[1], N.vals[0], N.vals[1], N.temp, N.temp_bytes, c->stream));
-    const bool normals = n1 || derive;
     PT_HIP(pt::launch_refit(T.num_chunks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes, nodes,
                             (uint32_t*)const_cast<float4*>(c->S.tri_chunks), (uint32_t*)const_cast<float4*>(c->S.tri_recs),
                             D.src_of_pos, D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
                             normals ? D.in[5] : nullptr, D.node_box, D.chunk_box, c->stream));
-    if (blas) {
+    if (U.blas) {
         const float* const in[6] = {D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
                                     normals ? D.in[5] : nullptr};
         if (const int rc = blas_refit_launch(c, num_triangles, in)) return rc;
@@ -1425,13 +1453,14 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
     for (size_t i = 0; i < c->h_lights.size() && i < T.light_tri.size(); i++) {
         const int64_t j = T.light_tri[i];
         if (j < 0) continue;
-        pt::tri_light_sphere(v1 + 3 * j, v2 + 3 * j, v3 + 3 * j, c->h_lights[i]);
+        if (L.kept) pt::tri_light_sphere(L.kept + 9 * i, L.kept + 9 * i + 3, L.kept + 9 * i + 6, c->h_lights[i]);
+        else pt::tri_light_sphere(L.v1 + 3 * j, L.v2 + 3 * j, L.v3 + 3 * j, c->h_lights[i]);
         lights_moved = true;
     }
     if (lights_moved)
         PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
                               hipMemcpyHostToDevice, c->stream));
-    if (blas) if (const int rc = blas_refit_finish(c)) return rc;
+    if (U.blas) if (const int rc = blas_refit_finish(c)) return rc;
     PT_HIP(hipStreamSynchronize(c->stream));
     if (T.num_chunks > 0) pt::tri_root_box(root, c->S.tri_box);
     if (out_kernel_ms) {
@@ -1440,6 +1469,27 @@ int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const fl
         *out_kernel_ms = ms;
     }
     return PT_OK;
+}
+
+// pt_update_triangles (mode 0: the normals given, or kept), pt_update_triangles_normals (mode: a pt_normals_mode) and
+// pt_update_meshes: the host arrays checked, staged, and the update run from them
+int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
+                     const float* n2, const float* n3, bool derive, int32_t mode, bool meshes, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!v1 || !v2 || !v3) return fail(PT_ERR_INVALID_ARG, "update: v1, v2 and v3 are required");
+    if ((n1 != nullptr) != (n2 != nullptr) || (n1 != nullptr) != (n3 != nullptr))
+        return fail(PT_ERR_INVALID_ARG, "update: n1/n2/n3 must be all set or all NULL");
+    UpdateDev U{};
+    bool launch = false;
+    if (const int rc = update_prepare(c, num_triangles, derive, mode, meshes, out_kernel_ms, U, &launch)) return rc;
+    if (!launch) return PT_OK;
+    c->pose_staged = false;   // the staged arrays are this update's from here on
+    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
+    const float* src[6] = {v1, v2, v3, n1, n2, n3};
+    for (int k = 0; k < (n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(U.D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    return update_run(c, U, num_triangles, derive, n1 || derive, LightVerts{v1, v2, v3, nullptr}, out_kernel_ms);
 }
 }  // namespace
 
@@ -1470,6 +1520,7 @@ int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3) {
     RefitDev D{};
     if (const int rc = ensure_refit_dev(c, D)) return rc;
     // the staged normal arrays are free between updates: a triangle outside the BVH reads as zeros
+    c->pose_staged = false;
     for (int k = 3; k < 6; k++) PT_HIP(hipMemsetAsync(D.in[k], 0, arr, c->stream));
     PT_HIP(pt::launch_normals_gather((int64_t)T.src_of_pos.size(), (const uint32_t*)c->S.tri_recs, D.src_of_pos, D.in[3], D.in[4],
                                      D.in[5], c->stream));
@@ -1726,6 +1777,121 @@ int pt_update_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms) 
         return fail(PT_ERR_INVALID_ARG, "update meshes: n1/n2/n3 are given and normals_mode derives them");
     return update_triangles(ctx, u->num_triangles, u->v1, u->v2, u->v3, u->n1, u->n2, u->n3, u->normals_mode != 0, u->normals_mode,
                             true, out_kernel_ms);
+}
+
+// ---- posing meshes by matrix on the device
+namespace {
+// The parts of Ctx::pose_dev, each 256-B aligned: [rest v1 v2 v3 n1 n2 n3 | group | matrices | mask]
+struct PoseDev {
+    float* rest[6];
+    int32_t* group;
+    double* matrices;
+    int32_t* mask;
+    size_t bytes;
+};
+PoseDev pose_layout(const pt::RefitTables& T, void* base) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    PoseDev r{};
+    size_t at = 0;
+    char* p = (char*)base;
+    const size_t arr = up((size_t)T.num_triangles * 3 * sizeof(float));
+    for (int k = 0; k < 6; k++) { r.rest[k] = (float*)(p + at); at += arr; }
+    r.group = (int32_t*)(p + at); at += up((size_t)T.num_triangles * sizeof(int32_t));
+    r.matrices = (double*)(p + at); at += up((size_t)T.num_groups * 16 * sizeof(double));
+    r.mask = (int32_t*)(p + at); at += up((size_t)T.num_groups * sizeof(int32_t));
+    r.bytes = at + 256;   // never an empty allocation
+    return r;
+}
+}  // namespace
+
+int pt_set_rest_pose(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
+                     const float* n2, const float* n3) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!v1 || !v2 || !v3 || !n1 || !n2 || !n3) return fail(PT_ERR_INVALID_ARG, "rest pose: v1, v2, v3, n1, n2 and n3 are required");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::RefitTables& T = c->refit;
+    if (num_triangles != T.num_triangles)
+        return fail(PT_ERR_INVALID_ARG, "rest pose: num_triangles is " + std::to_string(num_triangles) + ", the uploaded scene has " +
+                                            std::to_string(T.num_triangles));
+    PT_HIP(hipSetDevice(c->device));
+    const bool first = !c->pose_dev.ptr;
+    if (first) {
+        const PoseDev L = pose_layout(T, nullptr);
+        if (hipMalloc(&c->pose_dev.ptr, L.bytes) != hipSuccess) {
+            c->pose_dev.ptr = nullptr;
+            (void)hipGetLastError();
+            return fail(PT_ERR_OUT_OF_MEMORY, "pose workspace allocation");
+        }
+        c->pose_dev.bytes = L.bytes;
+    }
+    const PoseDev P = pose_layout(T, c->pose_dev.ptr);
+    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
+    const float* src[6] = {v1, v2, v3, n1, n2, n3};
+    if (arr)
+        for (int k = 0; k < 6; k++) PT_HIP(hipMemcpyAsync(P.rest[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
+    if (first && !T.tri_group.empty())
+        PT_HIP(hipMemcpyAsync(P.group, T.tri_group.data(), T.tri_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    // the lights that are loose emissive triangles return to these at every pose
+    c->rest_light_verts.assign(9 * c->h_lights.size(), 0.f);
+    for (size_t i = 0; i < c->h_lights.size() && i < T.light_tri.size(); i++) {
+        const int64_t j = T.light_tri[i];
+        if (j < 0 || j >= num_triangles) continue;
+        for (int k = 0; k < 3; k++) std::memcpy(&c->rest_light_verts[9 * i + 3 * k], src[k] + 3 * j, 3 * sizeof(float));
+    }
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_pose_meshes(void* ctx, const pt_mesh_pose* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!u) return fail(PT_ERR_INVALID_ARG, "pose meshes: u is NULL");
+    if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "pose meshes: reserved must be 0");
+    if (u->normals_mode != 0 && u->normals_mode != PT_NORMALS_FACE && u->normals_mode != PT_NORMALS_SMOOTH)
+        return fail(PT_ERR_INVALID_ARG, "pose meshes: normals_mode " + std::to_string(u->normals_mode) + " is not 0 or a pt_normals_mode");
+    if (!u->matrices) return fail(PT_ERR_INVALID_ARG, "pose meshes: matrices is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::RefitTables& T = c->refit;
+    if (u->num_meshes != T.num_groups)
+        return fail(PT_ERR_INVALID_ARG, "pose meshes: num_meshes is " + std::to_string(u->num_meshes) + ", the uploaded scene has " +
+                                            std::to_string(T.num_groups));
+    if (!c->pose_dev.ptr) return fail(PT_ERR_INVALID_ARG, "pose meshes: no rest pose (pt_set_rest_pose)");
+    const bool derive = u->normals_mode != 0;
+    UpdateDev U{};
+    bool launch = false;
+    if (const int rc = update_prepare(c, T.num_triangles, derive, u->normals_mode, true, out_kernel_ms, U, &launch)) return rc;
+    if (!launch) return PT_OK;
+    const PoseDev P = pose_layout(T, c->pose_dev.ptr);
+    const size_t nm = (size_t)T.num_groups;
+    if (nm) {
+        PT_HIP(hipMemcpyAsync(P.matrices, u->matrices, nm * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (u->mesh_mask) PT_HIP(hipMemcpyAsync(P.mask, u->mesh_mask, nm * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_pose(T.num_triangles, T.num_groups, P.group, u->mesh_mask ? P.mask : nullptr, P.matrices, !derive, P.rest,
+                           U.D.in, c->stream));
+    c->pose_staged = true;
+    return update_run(c, U, T.num_triangles, derive, true, LightVerts{nullptr, nullptr, nullptr, c->rest_light_verts.data()},
+                      out_kernel_ms);
+}
+
+int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n2, float* n3) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->pose_staged || !c->refit_dev.ptr)
+        return fail(PT_ERR_INVALID_ARG, "read pose: the staged arrays hold no pose (none made since the upload, or a later "
+                                        "pt_update_* or pt_read_tri_normals reused them)");
+    const pt::RefitTables& T = c->refit;
+    PT_HIP(hipSetDevice(c->device));
+    const RefitDev D = refit_layout(T, c->refit_dev.ptr);
+    const size_t arr = (size_t)T.num_triangles * 3 * sizeof(float);
+    float* out[6] = {v1, v2, v3, n1, n2, n3};
+    for (int k = 0; k < 6; k++)
+        if (out[k] && arr) PT_HIP(hipMemcpyAsync(out[k], D.in[k], arr, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
 }
 
 int pt_read_blas(void* ctx, int64_t counts[3], int32_t* blas, uint32_t* nodes, uint32_t* recs, uint32_t* shade, float* inner_boxes) {

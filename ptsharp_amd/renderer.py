@@ -154,6 +154,8 @@ class Renderer:
         self._ctx = None
         self._lib = None
         self._uploaded = None
+        self._rest_of = None         # the FlatScene whose rest pose the device holds (SetRestPose)
+        self._mirror_stale = False   # PoseMeshes(mirror=False) left the uploaded FlatScene's triangle arrays behind
         self._pass = 0
         self.iterations = 0
 
@@ -187,6 +189,8 @@ class Renderer:
         if self._uploaded is not flat:
             _abi.check(self._lib.pt_upload_scene(self._ctx, C.byref(flat.desc)), "pt_upload_scene")
             self._uploaded = flat
+            self._rest_of = None
+            self._mirror_stale = False
 
     def _pass_params(self, spp=None, pass_index=None):
         tiles = self.Tiles
@@ -406,6 +410,7 @@ class Renderer:
         back) are then written into the uploaded FlatScene in place, so it describes what the device holds.
         Returns the device time of the kernels in ms."""
         self._ensure_scene()
+        self._refresh_mirror()
         flat = self._uploaded
         n = len(flat.tri_material)
         if (n1 is None) != (n2 is None) or (n1 is None) != (n3 is None):
@@ -437,6 +442,7 @@ class Renderer:
         """The normals the uploaded scene holds on the device now (pt_read_tri_normals): n1, n2, n3, [n, 3]
         float32 each in the order of the compiled scene's tri_n1."""
         self._ensure_scene()
+        self._refresh_mirror()   # pt_read_tri_normals reuses the staged arrays a pose is read from
         n = len(self._uploaded.tri_material)
         out = [np.zeros((n, 3), np.float32) for _ in range(3)]
         _abi.check(self._lib.pt_read_tri_normals(self._ctx, *[a.ctypes.data_as(C.POINTER(C.c_float)) for a in out]),
@@ -536,6 +542,7 @@ class Renderer:
         written into the uploaded FlatScene in place, so it describes what the device holds.  Returns the device time
         of the kernels in ms."""
         self._ensure_scene()
+        self._refresh_mirror()
         flat = self._uploaded
         n = len(flat.tri_material)
         if (n1 is None) != (n2 is None) or (n1 is None) != (n3 is None):
@@ -586,6 +593,81 @@ class Renderer:
                     nn = shade[pos, :9].view(np.float32)
                     out[0][f + t], out[1][f + t], out[2][f + t] = nn[0:3], nn[3:6], nn[6:9]
         return out
+
+    def SetRestPose(self, v1=None, v2=None, v3=None, n1=None, n2=None, n3=None) -> None:
+        """Installs the rest pose PoseMeshes poses from (pt_set_rest_pose): positions and normals of every triangle,
+        [n, 3] float32 in the order of the compiled scene's tri_v1, kept on the device until the next upload.  An
+        array left None is the uploaded FlatScene's current one."""
+        self._ensure_scene()
+        self._refresh_mirror()
+        flat = self._uploaded
+        n = len(flat.tri_material)
+        given = (v1, v2, v3, n1, n2, n3)
+        mine = (flat.tri_v1, flat.tri_v2, flat.tri_v3, flat.tri_n1, flat.tri_n2, flat.tri_n3)
+        arrs = [np.ascontiguousarray(m if a is None else a, np.float32).reshape(-1, 3) for a, m in zip(given, mine)]
+        if any(len(a) != n for a in arrs):
+            raise ValueError(f"the scene has {n} triangles")
+        fp = C.POINTER(C.c_float)
+        _abi.check(self._lib.pt_set_rest_pose(self._ctx, n, *[a.ctypes.data_as(fp) for a in arrs]), "pt_set_rest_pose")
+        self._rest_of = flat
+
+    def PoseMeshes(self, matrices, normals=None, mask=None, mirror=True) -> float:
+        """Mesh.Transform(matrices[j]) of every mesh j of the scene on the device, from the rest pose (pt_pose_meshes):
+        `matrices` is a sequence of Matrix or an [M, 16] (or [M, 4, 4]) float64 array, indexed like the compiled
+        scene's mesh_first; `mask` ([M], optional) is 0 for a mesh that takes its rest values; loose triangles take
+        theirs.  normals=None transforms the rest normals as Mesh.Transform does, "face" or "smooth" derives them from
+        the posed positions.  The BVHs, the instances' boxes and the lights are refitted as UpdateMeshes refits them.
+        The rest pose is installed on first use (SetRestPose()).  With mirror=True the posed arrays are read back into
+        the uploaded FlatScene in place, so it describes what the device holds; with mirror=False that readback (72 B
+        per triangle) is skipped and the FlatScene's triangle arrays are stale until ReadPose(), or the next
+        UpdateTriangles, UpdateMeshes, ReadTriNormals or SetRestPose, refreshes them.  Returns the device time of the
+        kernels in ms."""
+        self._ensure_scene()
+        flat = self._uploaded
+        if normals not in (None, "face", "smooth"):
+            raise ValueError('normals is None, "face" or "smooth"')
+        if self._rest_of is not flat:
+            self.SetRestPose()
+        nm = len(flat.mesh_first)
+        m = np.ascontiguousarray([getattr(k, "m", k) for k in matrices] if nm else np.zeros((0, 16)), np.float64).reshape(-1, 16)
+        if len(m) != nm:
+            raise ValueError(f"the scene has {nm} meshes")
+        u = _abi.pt_mesh_pose()
+        u.num_meshes = nm
+        u.normals_mode = 0 if normals is None else _abi.NORMALS_FACE if normals == "face" else _abi.NORMALS_SMOOTH
+        u.matrices = m.ctypes.data_as(C.POINTER(C.c_double))
+        if mask is not None:
+            on = np.ascontiguousarray(mask, np.int32).reshape(-1)
+            if len(on) != nm:
+                raise ValueError(f"the scene has {nm} meshes")
+            u.mesh_mask = on.ctypes.data_as(C.POINTER(C.c_int32))
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_pose_meshes(self._ctx, C.byref(u), C.byref(ms)), "pt_pose_meshes")
+        # a device time of exactly 0: nothing was launched (no triangle of the scene is in a BVH), nothing to mirror
+        self._mirror_stale = ms.value != 0.0
+        if mirror:
+            self._refresh_mirror()
+        return float(ms.value)
+
+    def ReadPose(self):
+        """The six arrays the last PoseMeshes left on the device (pt_read_pose): v1, v2, v3, n1, n2, n3, [n, 3]
+        float32 each, derived normals included.  Also brings a FlatScene left stale by mirror=False up to date."""
+        self._ensure_scene()
+        n = len(self._uploaded.tri_material)
+        out = [np.zeros((n, 3), np.float32) for _ in range(6)]
+        _abi.check(self._lib.pt_read_pose(self._ctx, *[a.ctypes.data_as(C.POINTER(C.c_float)) for a in out]), "pt_read_pose")
+        if self._mirror_stale:
+            flat = self._uploaded
+            for dst, a in zip((flat.tri_v1, flat.tri_v2, flat.tri_v3, flat.tri_n1, flat.tri_n2, flat.tri_n3), out):
+                dst[...] = a
+            self._mirror_stale = False
+        return tuple(out)
+
+    def _refresh_mirror(self):
+        """The uploaded FlatScene's triangle arrays brought up to date after a PoseMeshes(mirror=False), before a call
+        that reads them or reuses the device's staged arrays."""
+        if self._mirror_stale:
+            self.ReadPose()
 
     def ReadBlas(self):
         """The context's BLASes, the object-space BVHs of instanced meshes, as they stand on the device
