@@ -253,6 +253,10 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_set_rest_pose(IntPtr ctx, int numTriangles, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_pose_meshes(IntPtr ctx, ref pt_mesh_pose u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_pose(IntPtr ctx, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3);
+        // pt_update_meshes that also re-sorts the world triangle BVH on the device (u = IntPtr.Zero: the staged pose), and the tree's cost
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, ref pt_mesh_update u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, IntPtr u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_tri_bvh_cost(IntPtr ctx, double[] out3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr pt_last_error();
@@ -809,6 +813,55 @@ namespace PTSharpCore
             for (int k = 0; k < 6; k++) a[k] = new float[numTriangles * 3];
             PtHip.Check(PtHip.pt_read_pose(ctx, a[0], a[1], a[2], a[3], a[4], a[5]), "pt_read_pose");
             return a;
+        }
+
+        /// <summary>UpdateMeshes that also re-sorts the world triangle BVH on the device into a balanced median tree for
+        /// the new positions (pt_rebuild_meshes), for a mesh deformed far from the pose its tree was built for.  A scene
+        /// with an instanced mesh is refused.  Returns the device time of the kernels in ms.</summary>
+        public double RebuildMeshes(float[] v1, float[] v2, float[] v3, float[] n1 = null, float[] n2 = null, float[] n3 = null,
+                                    int normalsMode = 0)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            IntPtr PinHeld(Array a)
+            {
+                if (a == null) return IntPtr.Zero;
+                var h = GCHandle.Alloc(a, GCHandleType.Pinned);
+                held.Add(h);
+                return h.AddrOfPinnedObject();
+            }
+            try
+            {
+                var u = new PtHip.pt_mesh_update
+                {
+                    num_triangles = v1.Length / 3, normals_mode = normalsMode,
+                    v1 = PinHeld(v1), v2 = PinHeld(v2), v3 = PinHeld(v3), n1 = PinHeld(n1), n2 = PinHeld(n2), n3 = PinHeld(n3),
+                };
+                PtHip.Check(PtHip.pt_rebuild_meshes(ctx, ref u, out double ms), "pt_rebuild_meshes");
+                return ms;
+            }
+            finally
+            {
+                foreach (var h in held) h.Free();
+            }
+        }
+
+        /// <summary>RebuildMeshes from the pose the last PoseMeshes left staged on the device: nothing is copied.</summary>
+        public double RebuildMeshes()
+        {
+            PtHip.Check(PtHip.pt_rebuild_meshes(ctx, IntPtr.Zero, out double ms), "pt_rebuild_meshes");
+            return ms;
+        }
+
+        /// <summary>The surface-area cost of the world triangle BVH as it stands (pt_tri_bvh_cost): inner cost and leaf
+        /// cost relative to the root box's area, and that area.  Its growth since the upload tells when RebuildMeshes
+        /// pays.</summary>
+        public (double inner, double leaf, double rootArea) TriBvhCost()
+        {
+            if (!uploaded) Upload();
+            var o = new double[3];
+            PtHip.Check(PtHip.pt_tri_bvh_cost(ctx, o), "pt_tri_bvh_cost");
+            return (o[0], o[1], o[2]);
         }
 
         /// <summary>The context's BLASes as they stand on the device (pt_read_blas): 4 ints per BLAS, 32 words per

@@ -26,6 +26,10 @@
  *   pt_set_rest_pose   (new) Mesh.Transform(matrix) of every mesh of the      Mesh.cs:254-274 (Mesh.Transform; MoveTo
  *   / pt_pose_meshes   uploaded scene on the device, from a rest pose kept    and FitInside, Mesh.cs:237-252, end in it),
  *   / pt_read_pose     there: one matrix per mesh per call, then the refits   Matrix.cs:134-150
+ *   pt_rebuild_meshes  (new) pt_update_meshes that also re-sorts the world    Tree.NewTree, Tree.cs:22-29 (the reference
+ *   / pt_tri_bvh_cost  triangle BVH into a balanced median tree on the device  builds a new tree for every frame's scene)
+ *                      for the new positions; the SAH cost of the tree as it
+ *                      stands, the host's trigger for "refit or rebuild"
  *   pt_render_pass    one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
@@ -706,6 +710,39 @@ int pt_pose_meshes(void* ctx, const pt_mesh_pose* u, double* out_kernel_ms);
  * pt_scene_desc order; any pointer may be NULL.  They stay until a pt_update_* or pt_read_tri_normals reuses the
  * staged arrays.  A NULL ctx, or no pose staged: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n2, float* n3);
+
+/* Re-sorting the world triangle BVH on the device.  The updates above refit: they keep the topology
+ * of the pose the tree was built for, and a mesh deformed far from it traces an ever worse tree.  pt_rebuild_meshes
+ * takes pt_update_meshes' struct and does everything that call does (positions; normals given, kept or derived), and
+ * in addition replaces the topology of the world triangle BVH (loose triangles and top-level meshes together) by a
+ * balanced object-median tree for these positions: with P triangles in the BVH, chunks of three consecutive positions,
+ * h = the least integer >= 1 with 3 * 8^h >= P levels of nodes that group 8 consecutive chunks, then 8 consecutive nodes,
+ * numbered level by level from the root; the order comes from 3 h rounds of stable sorts of ever halved position
+ * segments by the key min + max of the triangle's vertices on the segment's widest axis (pt_rebuild.h states it
+ * exactly).  The tree's shape depends on P alone, the order is computed on the device, and every box, record and chunk
+ * line then comes from the refit.  With u == NULL the arrays the last pt_pose_meshes left staged are taken: nothing is
+ * copied, the staged normals are used and the pose stays readable.
+ * Afterwards every ray query, feature pass and render pass sees what a fresh pt_upload_scene with these arrays would
+ * see, up to the exact-t tie order of DESIGN.md §5, and every later pt_update_triangles, _normals, pt_update_meshes,
+ * pt_pose_meshes, pt_read_tri_normals and pt_read_tri_bvh works on the new topology (pt_read_tri_bvh's counts follow;
+ * lines past them are left as they are, nothing references them).  The lights that are loose emissive triangles follow.
+ * pt_stats' bvh_nodes, bvh_bytes and traversal_bytes keep describing the upload.  The process-wide build cache is
+ * untouched: other contexts keep their trees.  Runs on the context's stream after every pass issued before it and
+ * synchronises before returning; out_kernel_ms (may be NULL) covers every kernel of the call.  Non-finite positions:
+ * the order is unspecified, still a permutation; no access leaves its array.
+ * Errors (nothing launched, the scene untouched): those of pt_update_meshes (u == NULL without a staged pose:
+ * PT_ERR_INVALID_ARG); a scene with an instanced mesh, whose BLAS is not rebuilt: PT_ERR_UNSUPPORTED; more than 9
+ * levels, or more node and chunk lines together than the upload allocated (nodes and chunks share one run of lines,
+ * so a tree with more nodes than the uploaded one starts its chunks later; short only when the uploaded tree was
+ * within a few lines of perfectly full): PT_ERR_UNSUPPORTED; the workspace (about 130 B per triangle, kept until the
+ * next upload) not allocated: PT_ERR_OUT_OF_MEMORY.  A scene with no triangle in the BVH: PT_OK, nothing launched. */
+int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms);
+/* The surface-area cost of the world triangle BVH from the node words as they stand, valid any time after an upload:
+ * every slot box decoded in fp64 as origin + q 2^(e - 127), A = the area of the union of the root's slot boxes;
+ * out[0] = (A + the area of every inner slot) / A, out[1] = the area of every leaf slot / A, out[2] = A.  Summed on
+ * the device.  No triangle in the BVH (or A == 0): zeros.  Synchronises and changes nothing.  A NULL argument:
+ * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+int pt_tri_bvh_cost(void* ctx, double out[3]);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

@@ -187,6 +187,8 @@ SIGNATURES = {
     "pt_set_rest_pose": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, _f, _f, _f]),
     "pt_pose_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_pose), _d]),
     "pt_read_pose": (C.c_int, [C.c_void_p, _f, _f, _f, _f, _f, _f]),
+    "pt_rebuild_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_update), _d]),
+    "pt_tri_bvh_cost": (C.c_int, [C.c_void_p, _d]),
     "pt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_sampler), C.POINTER(pt_pass_params)]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_reset_buffer": (C.c_int, [C.c_void_p]),

@@ -28,6 +28,7 @@
 #include "pt_device.h"
 #include "pt_math.h"
 #include "pt_pass_plan.h"
+#include "pt_rebuild.h"
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
 #include "pt_shape_refit.h"
@@ -122,6 +123,13 @@ hipError_t launch_normals(bool smooth, int64_t n, const float* v1, const float* 
                           uint32_t* vals_a, uint32_t* vals_b, void* temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_normals_gather(int64_t num_pos, const uint32_t* recs, const int32_t* src_of_pos, float* n1, float* n2,
                                  float* n3, hipStream_t stream);
+// pt_rebuild.hip
+hipError_t rebuild_workspace_bytes(int64_t P, size_t* temp_bytes, size_t* bytes);
+hipError_t launch_rebuild(const RebuildPlan& R, void* ws, size_t temp_bytes, uint32_t* nodes, uint32_t* chunks, uint32_t* recs,
+                          int32_t* src_of_pos, uint32_t* level_nodes, const float* v1, const float* v2, const float* v3,
+                          hipStream_t stream);
+hipError_t bvh_cost_workspace_bytes(int64_t num_nodes, size_t* bytes);
+hipError_t launch_bvh_cost(int64_t num_nodes, const uint32_t* nodes, void* ws, double* sums, hipStream_t stream);
 // pt_pose.hip
 hipError_t launch_pose(int64_t n, int32_t num_meshes, const int32_t* group, const int32_t* mask, const double* matrices,
                        bool normals, const float* const rest[6], float* const out[6], hipStream_t stream);
@@ -273,6 +281,10 @@ struct Ctx {
     DeviceArray pose_dev;
     std::vector<float> rest_light_verts;
     bool pose_staged = false;            // refit_dev's staged arrays hold the last pt_pose_meshes' (pt_read_pose)
+    // pt_rebuild_meshes: the sort's keys, values and temporary, the segments' bounds and the records' scratch copy, one
+    // allocation that comes with the first rebuild and goes with the scene
+    DeviceArray rebuild_dev;
+    size_t rebuild_temp_bytes = 0;
 };
 
 #ifndef PT_VOL_DEFER
@@ -454,6 +466,8 @@ void free_scene(Ctx* c) {
     c->blas_boxes_on_device = false;
     c->blas_refit = pt::BlasRefitTables{};
     c->pose_dev.release();
+    c->rebuild_dev.release();
+    c->rebuild_temp_bytes = 0;
     c->rest_light_verts.clear();
     c->pose_staged = false;
     c->refit = pt::RefitTables{};
@@ -1303,9 +1317,15 @@ RefitDev refit_layout(const pt::RefitTables& T, void* base) {
     const size_t arr = up((size_t)T.num_triangles * 3 * sizeof(float));
     for (int k = 0; k < 6; k++) { r.in[k] = (float*)(p + at); at += arr; }
     r.src_of_pos = (int32_t*)(p + at); at += up(T.src_of_pos.size() * sizeof(int32_t));
-    r.level_nodes = (uint32_t*)(p + at); at += up(T.level_nodes.size() * sizeof(uint32_t));
-    r.node_box = (float*)(p + at); at += up((size_t)T.num_nodes * 6 * sizeof(float));
-    r.chunk_box = (float*)(p + at); at += up((size_t)T.num_chunks * 6 * sizeof(float));
+    // room for the tables pt_rebuild_meshes may put in their place: its balanced tree can have a few more nodes than
+    // the uploaded one (never more chunks), and the layout never grows once allocated
+    pt::RebuildPlan R;
+    const bool planned = pt::rebuild_plan((int64_t)T.src_of_pos.size(), R);
+    const size_t nodes = std::max({T.level_nodes.size(), (size_t)T.num_nodes, planned ? (size_t)R.num_nodes : (size_t)0});
+    const size_t chunks = std::max((size_t)T.num_chunks, planned ? (size_t)R.num_chunks : (size_t)0);
+    r.level_nodes = (uint32_t*)(p + at); at += up(nodes * sizeof(uint32_t));
+    r.node_box = (float*)(p + at); at += up(nodes * 6 * sizeof(float));
+    r.chunk_box = (float*)(p + at); at += up(chunks * 6 * sizeof(float));
     r.bytes = at;
     return r;
 }
@@ -1423,18 +1443,47 @@ int update_prepare(Ctx* c, int32_t num_triangles, bool derive, int32_t mode, boo
     return PT_OK;
 }
 
+// pt_rebuild_meshes' part of update_run: the new topology, and the line its chunks start at (the upload's, or later
+// when the balanced tree has more nodes than the uploaded one had: nodes and chunks share one run of lines)
+struct RebuildRun {
+    pt::RebuildPlan R;
+    uint32_t chunk_line0;
+};
+
 // The second part, from the arrays staged in U.D.in on the context's stream after Ctx::ev0 was recorded there: the
 // normals when they are derived, the refit of the world triangle BVH, the BLAS path, the root box, the lights, the
 // timing.  normals: U.D.in[3..5] hold normals, given or to be derived (false: the device's are kept).
 int update_run(Ctx* c, const UpdateDev& U, int32_t num_triangles, bool derive, bool normals, const LightVerts& L,
-               double* out_kernel_ms) {
-    const pt::RefitTables& T = c->refit;
+               double* out_kernel_ms, const RebuildRun* rebuild = nullptr) {
+    pt::RefitTables& T = c->refit;
     const RefitDev& D = U.D;
     const NormalsDev& N = U.N;
     uint32_t* nodes = (uint32_t*)const_cast<float4*>(c->S.tri_nodes);
     if (derive)
         PT_HIP(pt::launch_normals(U.smooth, num_triangles, D.in[0], D.in[1], D.in[2], D.in[3], D.in[4], D.in[5], N.group, T.num_groups,
                                   N.keys[0], N.keys[1], N.vals[0], N.vals[1], N.temp, N.temp_bytes, c->stream));
+    if (rebuild) {
+        // pt_rebuild_meshes: the re-sort and the new topology before the refit, which then runs over the new tables.
+        // D was laid out for the tables before: the new ones are no larger, so its scratch boxes hold them.
+        const pt::RebuildPlan& R = rebuild->R;
+        if (rebuild->chunk_line0 != c->S.tri_chunk_line0) {   // more nodes than the upload had: the chunks start later
+            c->S.tri_chunk_line0 = rebuild->chunk_line0;
+            c->S.tri_chunks = c->S.lines + 8 * (size_t)rebuild->chunk_line0;
+        }
+        PT_HIP(pt::launch_rebuild(R, c->rebuild_dev.ptr, c->rebuild_temp_bytes, nodes, (uint32_t*)const_cast<float4*>(c->S.tri_chunks),
+                                  (uint32_t*)const_cast<float4*>(c->S.tri_recs), D.src_of_pos, D.level_nodes, D.in[0], D.in[1],
+                                  D.in[2], c->stream));
+        T.num_nodes = R.num_nodes;
+        T.num_chunks = R.num_chunks;
+        T.level_nodes.resize((size_t)R.num_nodes);
+        for (int64_t i = 0; i < R.num_nodes; i++) T.level_nodes[(size_t)i] = (uint32_t)i;
+        T.level_off.assign(R.level_off, R.level_off + R.h + 1);
+        c->S.tri_num_nodes = (int32_t)R.num_nodes;
+        // what the compile derives from the node count follows: the routed split needs a tree of more than 64 nodes
+        // (pt_scene_compile.cpp); the stack key's index bits were sized for the upload's counts, and the balanced
+        // tree has no more chunks, and no more nodes than chunks (pt_stack_key.h)
+        if (c->S.tri_num_nodes <= 64) c->S.route = 0;
+    }
     PT_HIP(pt::launch_refit(T.num_chunks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes, nodes,
                             (uint32_t*)const_cast<float4*>(c->S.tri_chunks), (uint32_t*)const_cast<float4*>(c->S.tri_recs),
                             D.src_of_pos, D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
@@ -1448,6 +1497,8 @@ int update_run(Ctx* c, const UpdateDev& U, int32_t num_triangles, bool derive, b
     // the root box follows (pt_wavefront.hip's refill kernels skip the triangle phase of a ray that misses it)
     uint32_t root[pt::kNode8Words];
     if (T.num_chunks > 0) PT_HIP(hipMemcpyAsync(root, nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
+    if (rebuild)
+        PT_HIP(hipMemcpyAsync(T.src_of_pos.data(), D.src_of_pos, T.src_of_pos.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     // lights that are loose emissive triangles: their sphere from the new vertices
     bool lights_moved = false;
     for (size_t i = 0; i < c->h_lights.size() && i < T.light_tri.size(); i++) {
@@ -1891,6 +1942,110 @@ int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n
     for (int k = 0; k < 6; k++)
         if (out[k] && arr) PT_HIP(hipMemcpyAsync(out[k], D.in[k], arr, hipMemcpyDeviceToHost, c->stream));
     PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// ---- re-sorting the triangle BVH on the device
+int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    bool derive = false;
+    int32_t mode = 0;
+    if (u) {
+        if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "rebuild meshes: reserved must be 0");
+        if (u->normals_mode != 0 && u->normals_mode != PT_NORMALS_FACE && u->normals_mode != PT_NORMALS_SMOOTH)
+            return fail(PT_ERR_INVALID_ARG, "rebuild meshes: normals_mode " + std::to_string(u->normals_mode) + " is not 0 or a pt_normals_mode");
+        if (u->normals_mode != 0 && (u->n1 || u->n2 || u->n3))
+            return fail(PT_ERR_INVALID_ARG, "rebuild meshes: n1/n2/n3 are given and normals_mode derives them");
+        if (!u->v1 || !u->v2 || !u->v3) return fail(PT_ERR_INVALID_ARG, "rebuild meshes: v1, v2 and v3 are required");
+        if ((u->n1 != nullptr) != (u->n2 != nullptr) || (u->n1 != nullptr) != (u->n3 != nullptr))
+            return fail(PT_ERR_INVALID_ARG, "rebuild meshes: n1/n2/n3 must be all set or all NULL");
+        derive = u->normals_mode != 0;
+        mode = u->normals_mode;
+    }
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    if (!u && (!c->pose_staged || !c->refit_dev.ptr))
+        return fail(PT_ERR_INVALID_ARG, "rebuild meshes: u is NULL and the staged arrays hold no pose (pt_pose_meshes)");
+    if (c->has_blas)
+        return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
+                                        "BLASes are not rebuilt");
+    const int32_t num_triangles = u ? u->num_triangles : c->refit.num_triangles;
+    UpdateDev U{};
+    bool launch = false;
+    if (const int rc = update_prepare(c, num_triangles, derive, mode, false, out_kernel_ms, U, &launch)) return rc;
+    if (!launch) return PT_OK;
+    // the new topology, checked against what the upload allocated, and the workspace: before anything is staged
+    RebuildRun run{};
+    pt::RebuildPlan& R = run.R;
+    const int64_t P = (int64_t)c->refit.src_of_pos.size();
+    if (!pt::rebuild_plan(P, R) || pt::rebuild_stack_bound(R) > pt::kStackMax)
+        return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: " + std::to_string(P) + " triangles need more than " +
+                                            std::to_string(pt::kRebuildMaxLevels) + " levels");
+    const int64_t node_cap = (int64_t)c->S.tri_chunk_line0 - (int64_t)c->S.tri_node_line0;
+    const int64_t chunk_cap = (int64_t)c->S.lines_n - (int64_t)c->S.tri_chunk_line0;
+    if (R.num_nodes + R.num_chunks > node_cap + chunk_cap)
+        return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: the balanced tree needs " + std::to_string(R.num_nodes) + " nodes and " +
+                                            std::to_string(R.num_chunks) + " chunks, the upload allocated " +
+                                            std::to_string(node_cap + chunk_cap) + " lines");
+    run.chunk_line0 = R.num_nodes <= node_cap && R.num_chunks <= chunk_cap ? c->S.tri_chunk_line0
+                                                                            : c->S.tri_node_line0 + (uint32_t)R.num_nodes;
+    if (!c->rebuild_dev.ptr) {
+        size_t temp = 0, bytes = 0;
+        PT_HIP(pt::rebuild_workspace_bytes(P, &temp, &bytes));
+        if (hipMalloc(&c->rebuild_dev.ptr, bytes) != hipSuccess) {
+            c->rebuild_dev.ptr = nullptr;
+            (void)hipGetLastError();
+            return fail(PT_ERR_OUT_OF_MEMORY, "rebuild workspace allocation");
+        }
+        c->rebuild_dev.bytes = bytes;
+        c->rebuild_temp_bytes = temp;
+    }
+    if (!u) {   // the pose pt_pose_meshes left staged: nothing copied, its normals used, and it stays readable
+        PT_HIP(hipEventRecord(c->ev0, c->stream));
+        return update_run(c, U, num_triangles, false, true, LightVerts{nullptr, nullptr, nullptr, c->rest_light_verts.data()},
+                          out_kernel_ms, &run);
+    }
+    c->pose_staged = false;
+    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
+    const float* src[6] = {u->v1, u->v2, u->v3, u->n1, u->n2, u->n3};
+    for (int k = 0; k < (u->n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(U.D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    return update_run(c, U, num_triangles, derive, u->n1 || derive, LightVerts{u->v1, u->v2, u->v3, nullptr}, out_kernel_ms, &run);
+}
+
+int pt_tri_bvh_cost(void* ctx, double out[3]) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!out) return fail(PT_ERR_INVALID_ARG, "bvh cost: out is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    out[0] = out[1] = out[2] = 0.0;
+    const int64_t nn = c->refit.num_nodes;
+    if (nn <= 0 || c->refit.src_of_pos.empty()) return PT_OK;
+    PT_HIP(hipSetDevice(c->device));
+    size_t bytes = 0;
+    PT_HIP(pt::bvh_cost_workspace_bytes(nn, &bytes));
+    DeviceArray ws;
+    if (hipMalloc(&ws.ptr, bytes + 2 * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, "bvh cost workspace allocation");
+    }
+    double* d_sums = (double*)((char*)ws.ptr + bytes);
+    double sums[2] = {0.0, 0.0};
+    uint32_t root[pt::kNode8Words];
+    hipError_t e = hipStreamSynchronize(c->side);   // after every pass issued before
+    if (e == hipSuccess) e = pt::launch_bvh_cost(nn, (const uint32_t*)c->S.tri_nodes, ws.ptr, d_sums, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(root, c->S.tri_nodes, sizeof root, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    ws.release();
+    PT_HIP(e);
+    double ri = 0.0, rl = 0.0, area = 0.0;
+    pt::rebuild_node_cost(root, &ri, &rl, &area);
+    out[2] = area;
+    if (area > 0.0) {
+        out[0] = (area + sums[0]) / area;
+        out[1] = sums[1] / area;
+    }
     return PT_OK;
 }
 

@@ -570,6 +570,56 @@ class Renderer:
             dst[...] = a
         return float(ms.value)
 
+    def RebuildMeshes(self, v1=None, v2=None, v3=None, n1=None, n2=None, n3=None, normals=None) -> float:
+        """UpdateMeshes that also re-sorts the world triangle BVH on the device (pt_rebuild_meshes): the topology is
+        replaced by a balanced object-median tree for the new positions, for a mesh deformed far from the pose its tree
+        was built for (TriBvhCost tells when).  RebuildMeshes() with no arrays takes the pose the last PoseMeshes left
+        staged on the device; nothing is copied.  A scene with an instanced mesh is refused.  The uploaded FlatScene
+        is kept as UpdateMeshes keeps it.  Returns the device time of the kernels in ms."""
+        self._ensure_scene()
+        ms = C.c_double(0.0)
+        if v1 is None:
+            if any(a is not None for a in (v2, v3, n1, n2, n3)) or normals is not None:
+                raise ValueError("RebuildMeshes() takes the staged pose: no other argument goes with it")
+            _abi.check(self._lib.pt_rebuild_meshes(self._ctx, None, C.byref(ms)), "pt_rebuild_meshes")
+            self._refresh_mirror()
+            return float(ms.value)
+        self._refresh_mirror()
+        flat = self._uploaded
+        n = len(flat.tri_material)
+        if (n1 is None) != (n2 is None) or (n1 is None) != (n3 is None):
+            raise ValueError("n1, n2 and n3 must be all given or all None")
+        if normals is not None and n1 is not None:
+            raise ValueError("normals= derives the normals: n1, n2 and n3 cannot be given with it")
+        if normals not in (None, "face", "smooth"):
+            raise ValueError('normals is None, "face" or "smooth"')
+        arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (v1, v2, v3)]
+        if n1 is not None:
+            arrs += [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (n1, n2, n3)]
+        if any(len(a) != n for a in arrs):
+            raise ValueError(f"the scene has {n} triangles")
+        fp = C.POINTER(C.c_float)
+        u = _abi.pt_mesh_update()
+        u.num_triangles = n
+        u.normals_mode = 0 if normals is None else _abi.NORMALS_FACE if normals == "face" else _abi.NORMALS_SMOOTH
+        for name, a in zip(("v1", "v2", "v3", "n1", "n2", "n3"), arrs):
+            setattr(u, name, a.ctypes.data_as(fp))
+        _abi.check(self._lib.pt_rebuild_meshes(self._ctx, C.byref(u), C.byref(ms)), "pt_rebuild_meshes")
+        if normals is not None:
+            arrs += [a.copy() for a in self.ReadTriNormals()]
+        for dst, a in zip((flat.tri_v1, flat.tri_v2, flat.tri_v3, flat.tri_n1, flat.tri_n2, flat.tri_n3), arrs):
+            dst[...] = a
+        return float(ms.value)
+
+    def TriBvhCost(self):
+        """The surface-area cost of the world triangle BVH as it stands on the device (pt_tri_bvh_cost): (inner,
+        leaf, root_area), the first two relative to the root box's area.  A refit keeps the topology, so the cost
+        grows as a mesh deforms; its growth since the upload is the trigger for RebuildMeshes."""
+        self._ensure_scene()
+        out = (C.c_double * 3)()
+        _abi.check(self._lib.pt_tri_bvh_cost(self._ctx, out), "pt_tri_bvh_cost")
+        return float(out[0]), float(out[1]), float(out[2])
+
     def _derived_normals(self, verts):
         """The normals the device derived, in the scene's order: pt_read_tri_normals', and for the triangles of
         instanced meshes (zeros there unless the mesh is a top-level shape too) the BLAS shade rows, matched to their
