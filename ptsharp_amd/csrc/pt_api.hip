@@ -32,6 +32,7 @@
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
 #include "pt_shape_refit.h"
+#include "pt_update_layout.h"
 #include "pt_wavefront.h"
 
 #pragma clang fp contract(off)
@@ -191,6 +192,48 @@ struct EventTimer : pt::LaunchTimer {
     void destroy() { for (auto e : pool) (void)hipEventDestroy(e); pool.clear(); }
 };
 
+// A per-scene device workspace of the moving-geometry entry points: one allocation that comes with the first call
+// that needs it (ensure_workspace), its carved parts (pt_update_layout.h) kept beside it, and goes with the scene
+template <class L>
+struct Workspace {
+    DeviceArray mem;
+    L at{};
+    void release() { mem.release(); at = L{}; }
+};
+// pt_rebuild_meshes' workspace (the sort's keys, values and temporary, the segments' bounds and the records' scratch
+// copy) is carved by pt_rebuild.hip: what its launch takes
+struct RebuildDev {
+    size_t temp_bytes, bytes;
+};
+// Everything the moving-geometry entry points keep per scene.  free_scene replaces it by a fresh value, so a field
+// added here is reset with the rest; a device allocation added here goes into release_device.
+struct SceneDyn {
+    // the host tables of the last upload (pt_scene_compile.h); shape_refit with the parameters the device holds now
+    pt::RefitTables refit;
+    pt::ShapeRefitTables shape_refit;
+    pt::BlasRefitTables blas_refit;
+    std::vector<pt::DevLight> h_lights;   // the uploaded lights; the ones that follow geometry are moved by the updates
+    bool has_blas = false;                // an instanced mesh: pt_update_triangles and pt_rebuild_meshes refuse
+    Workspace<pt::RefitDev> refit_ws;       // first update, or pt_read_tri_normals
+    Workspace<pt::NormalsDev> normals_ws;   // first PT_NORMALS_SMOOTH
+    Workspace<pt::ShapesDev> shapes_ws;     // first pt_update_shapes, or pt_update_meshes on instanced meshes
+    Workspace<pt::BlasDev> blas_ws;         // first pt_update_meshes on instanced meshes
+    Workspace<pt::PoseDev> pose_ws;         // pt_set_rest_pose
+    Workspace<RebuildDev> rebuild_ws;       // first pt_rebuild_meshes
+    // pt_set_rest_pose: the rest vertices of the lights that are loose triangles, 9 floats per h_lights entry
+    std::vector<float> rest_light_verts;
+    bool pose_staged = false;            // refit_ws' staged arrays hold the last pt_pose_meshes' (pt_read_pose)
+    bool blas_boxes_on_device = false;   // blas_ws holds the meshes' boxes (after the first pt_update_meshes)
+    void release_device() {
+        refit_ws.release();
+        normals_ws.release();
+        shapes_ws.release();
+        blas_ws.release();
+        pose_ws.release();
+        rebuild_ws.release();
+    }
+};
+
 struct Ctx {
     int device = 0;
     int width = 0, height = 0;
@@ -253,39 +296,54 @@ struct Ctx {
     double tri_build_ms = 0;       // last upload: host time to build (or wait for, or find) the triangle BVH
     std::shared_ptr<const pt::TriBvhBuild> tri_build;   // that build, shared with the other contexts of its geometry
                                                     // (released at the next upload and at pt_destroy)
-    // pt_update_triangles: the host tables of the last upload; the device side (one allocation: the six staged
-    // input arrays, src_of_pos, level_nodes, an exact box per node and per chunk) comes with the first update
-    pt::RefitTables refit;
-    std::vector<pt::DevLight> h_lights;   // the uploaded lights (loose emissive triangles' spheres follow an update)
-    bool has_blas = false;                // an instanced mesh: no refit
-    DeviceArray refit_dev;
-    // pt_update_triangles_normals, PT_NORMALS_SMOOTH: the triangles' groups, two key and two corner arrays and the
-    // sort's temporary, one allocation that comes with the first such call and goes with the scene
-    DeviceArray normals_dev;
-    size_t normals_temp_bytes = 0;
-    // pt_update_shapes: the host tables of the last upload with the parameters the device holds now; the device side
-    // (one allocation: the staged parameters, a box per transformed shape, record and node, the level list and the
-    // static tables) comes with the first update
-    pt::ShapeRefitTables shape_refit;
-    DeviceArray shapes_dev;
-    // pt_update_meshes on a scene with instanced meshes: the host tables of the last upload; the device side (one
-    // allocation: the tables, a box per BLAS triangle and node, the bounds' block partials, a box per BLAS) comes with
-    // the first update
-    pt::BlasRefitTables blas_refit;
-    DeviceArray blas_dev;
-    size_t blas_num_blocks = 0;          // blocks of the bounds kernel (blas_dev's block tables)
-    bool blas_boxes_on_device = false;   // blas_dev holds the meshes' boxes (after the first pt_update_meshes)
-    // pt_pose_meshes: the rest pose (six arrays), the triangles' groups and a call's matrices and mask, one allocation
-    // that comes with pt_set_rest_pose and goes with the scene; the rest vertices of the lights that are loose
-    // triangles (9 floats per h_lights entry) stay on the host
-    DeviceArray pose_dev;
-    std::vector<float> rest_light_verts;
-    bool pose_staged = false;            // refit_dev's staged arrays hold the last pt_pose_meshes' (pt_read_pose)
-    // pt_rebuild_meshes: the sort's keys, values and temporary, the segments' bounds and the records' scratch copy, one
-    // allocation that comes with the first rebuild and goes with the scene
-    DeviceArray rebuild_dev;
-    size_t rebuild_temp_bytes = 0;
+    SceneDyn dyn;                  // moving geometry: born after an upload, gone with the scene (free_scene)
 };
+
+// The device time between Ctx::ev0 and Ctx::ev1, after the stream that recorded them was synchronised
+int kernel_ms(Ctx* c, double* out_kernel_ms) {
+    if (!out_kernel_ms) return PT_OK;
+    float ms = 0.f;
+    PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *out_kernel_ms = ms;
+    return PT_OK;
+}
+
+int check_hip(hipError_t e, const char* what) {
+    return e == hipSuccess ? PT_OK : fail(PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+// Host arrays to the device on one stream; after an error the rest are skipped
+struct Uploader {
+    hipStream_t stream;
+    hipError_t err = hipSuccess;
+    void copy(void* dst, const void* src, size_t bytes) {
+        if (err == hipSuccess && bytes) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
+    }
+    template <class T>
+    void operator()(T* dst, const std::vector<T>& v) { copy(dst, v.data(), v.size() * sizeof(T)); }
+};
+
+// A workspace allocated once per scene, else reused; *first tells which.  layout(base) carves it (called with NULL
+// for the size, then with the allocation); upload(parts, Uploader&) copies what the first use puts there, on the
+// context's stream.  "Allocated" means "tables uploaded": when an upload fails the workspace is released, so the
+// next call starts over.
+template <class L, class Layout, class Upload>
+int ensure_workspace(Ctx* c, Workspace<L>& W, const char* name, Layout&& layout, Upload&& upload, bool* first = nullptr) {
+    if (first) *first = !W.mem.ptr;
+    if (W.mem.ptr) return PT_OK;
+    const size_t bytes = layout(nullptr).bytes;
+    if (hipMalloc(&W.mem.ptr, bytes) != hipSuccess) {
+        W.mem.ptr = nullptr;
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, std::string(name) + " workspace allocation");
+    }
+    W.mem.bytes = bytes;
+    W.at = layout(W.mem.ptr);
+    Uploader up{c->stream};
+    upload(W.at, up);
+    const int rc = check_hip(up.err, (std::string(name) + " workspace tables").c_str());
+    if (rc != PT_OK) W.release();
+    return rc;
+}
 
 #ifndef PT_VOL_DEFER
 #define PT_VOL_DEFER 1   // split traversal: Volumes deferred to k_wf_vol_hits / k_wf_vol_shadow (0: marched in place)
@@ -456,23 +514,8 @@ int upload(Ctx* c, const std::vector<T>& host, const T** out) {
 void free_scene(Ctx* c) {
     for (auto& a : c->scene_arrays) a.release();
     c->scene_arrays.clear();
-    c->refit_dev.release();
-    c->normals_dev.release();
-    c->normals_temp_bytes = 0;
-    c->shapes_dev.release();
-    c->shape_refit = pt::ShapeRefitTables{};
-    c->blas_dev.release();
-    c->blas_num_blocks = 0;
-    c->blas_boxes_on_device = false;
-    c->blas_refit = pt::BlasRefitTables{};
-    c->pose_dev.release();
-    c->rebuild_dev.release();
-    c->rebuild_temp_bytes = 0;
-    c->rest_light_verts.clear();
-    c->pose_staged = false;
-    c->refit = pt::RefitTables{};
-    c->h_lights.clear();
-    c->has_blas = false;
+    c->dyn.release_device();
+    c->dyn = SceneDyn{};
     c->S = pt::DevScene{};
     c->has_scene = false;
 }
@@ -634,11 +677,11 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     PT_HIP(hipStreamSynchronize(c->stream));
     c->S = S;
     c->has_scene = true;
-    c->refit = std::move(H.refit);
-    c->shape_refit = std::move(H.shape_refit);
-    c->blas_refit = std::move(H.blas_refit);
-    c->h_lights = std::move(H.lights);
-    c->has_blas = !H.blas.empty();
+    c->dyn.refit = std::move(H.refit);
+    c->dyn.shape_refit = std::move(H.shape_refit);
+    c->dyn.blas_refit = std::move(H.blas_refit);
+    c->dyn.h_lights = std::move(H.lights);
+    c->dyn.has_blas = !H.blas.empty();
     c->stats.bvh_nodes = H.bvh_nodes;
     c->stats.traversal_bytes = H.traversal_bytes;
     c->stats.bvh_bytes = H.bvh_bytes;
@@ -1056,12 +1099,7 @@ int pt_denoise(void* ctx, const pt_denoise_params* params, double* out_kernel_ms
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     PT_HIP(hipStreamSynchronize(c->stream));
     c->denoise_pair = pair;
-    if (out_kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *out_kernel_ms = ms;
-    }
-    return PT_OK;
+    return kernel_ms(c, out_kernel_ms);
 }
 
 int pt_read_denoised(void* ctx, int32_t format, void* out) {
@@ -1125,12 +1163,7 @@ int pt_render_features(void* ctx, const pt_camera* camera, double* out_kernel_ms
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     PT_HIP(hipStreamSynchronize(c->stream));
     c->have_features = true;
-    if (out_kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *out_kernel_ms = ms;
-    }
-    return PT_OK;
+    return kernel_ms(c, out_kernel_ms);
 }
 
 int pt_read_features(void* ctx, int32_t feature, void* out) {
@@ -1198,12 +1231,7 @@ int pt_denoise_guided(void* ctx, const pt_denoise_guided_params* params, double*
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     PT_HIP(hipStreamSynchronize(c->stream));
     c->denoise_pair = pair;
-    if (out_kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *out_kernel_ms = ms;
-    }
-    return PT_OK;
+    return kernel_ms(c, out_kernel_ms);
 }
 
 static int tile_workspace(Ctx* c);
@@ -1298,179 +1326,235 @@ int pt_occluded(void* ctx, int64_t n, const float* origins, const float* dirs, c
     return ray_queries(ctx, n, origins, dirs, t_max, flags, nullptr, out_blocked);
 }
 
-// ---- moving triangles
+}  // extern "C"
+
+// ---- moving geometry: what the entry points of DESIGN.md §4c-§4g share
 namespace {
-// The parts of Ctx::refit_dev, each 256-B aligned: [v1 v2 v3 n1 n2 n3 | src_of_pos | level_nodes | node_box | chunk_box]
-struct RefitDev {
-    float* in[6];
-    int32_t* src_of_pos;
-    uint32_t* level_nodes;
-    float* node_box;
-    float* chunk_box;
-    size_t bytes;
-};
-RefitDev refit_layout(const pt::RefitTables& T, void* base) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    RefitDev r{};
-    size_t at = 0;
-    char* p = (char*)base;
-    const size_t arr = up((size_t)T.num_triangles * 3 * sizeof(float));
-    for (int k = 0; k < 6; k++) { r.in[k] = (float*)(p + at); at += arr; }
-    r.src_of_pos = (int32_t*)(p + at); at += up(T.src_of_pos.size() * sizeof(int32_t));
-    // room for the tables pt_rebuild_meshes may put in their place: its balanced tree can have a few more nodes than
-    // the uploaded one (never more chunks), and the layout never grows once allocated
-    pt::RebuildPlan R;
-    const bool planned = pt::rebuild_plan((int64_t)T.src_of_pos.size(), R);
-    const size_t nodes = std::max({T.level_nodes.size(), (size_t)T.num_nodes, planned ? (size_t)R.num_nodes : (size_t)0});
-    const size_t chunks = std::max((size_t)T.num_chunks, planned ? (size_t)R.num_chunks : (size_t)0);
-    r.level_nodes = (uint32_t*)(p + at); at += up(nodes * sizeof(uint32_t));
-    r.node_box = (float*)(p + at); at += up(nodes * 6 * sizeof(float));
-    r.chunk_box = (float*)(p + at); at += up(chunks * 6 * sizeof(float));
-    r.bytes = at;
-    return r;
-}
-// Ctx::refit_dev, allocated and its tables uploaded (on the context's stream) at the first use after an upload
-int ensure_refit_dev(Ctx* c, RefitDev& D) {
-    const pt::RefitTables& T = c->refit;
-    D = refit_layout(T, nullptr);
-    const bool first = !c->refit_dev.ptr;
-    if (first) {
-        if (hipMalloc(&c->refit_dev.ptr, D.bytes) != hipSuccess) {
-            c->refit_dev.ptr = nullptr;
-            (void)hipGetLastError();
-            return fail(PT_ERR_OUT_OF_MEMORY, "refit workspace allocation");
-        }
-        c->refit_dev.bytes = D.bytes;
-    }
-    D = refit_layout(T, c->refit_dev.ptr);
-    if (first && !T.src_of_pos.empty()) {
-        PT_HIP(hipMemcpyAsync(D.src_of_pos, T.src_of_pos.data(), T.src_of_pos.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        PT_HIP(hipMemcpyAsync(D.level_nodes, T.level_nodes.data(), T.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    }
+int upload_lights(Ctx* c) {
+    const std::vector<pt::DevLight>& L = c->dyn.h_lights;
+    PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), L.data(), L.size() * sizeof(pt::DevLight), hipMemcpyHostToDevice, c->stream));
     return PT_OK;
 }
 
-// The parts of Ctx::normals_dev (PT_NORMALS_SMOOTH), each 256-B aligned: [group | keys a b | corners a b | the sort's temporary]
-struct NormalsDev {
-    int32_t* group;
-    uint32_t* keys[2];
-    uint32_t* vals[2];
-    void* temp;
-    size_t temp_bytes, bytes;
-};
-NormalsDev normals_layout(const pt::RefitTables& T, size_t temp_bytes, void* base) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    NormalsDev r{};
-    size_t at = 0;
-    char* p = (char*)base;
-    r.group = (int32_t*)(p + at); at += up((size_t)T.num_triangles * sizeof(int32_t));
-    const size_t arr = up((size_t)T.num_triangles * 3 * sizeof(uint32_t));
-    for (int k = 0; k < 2; k++) { r.keys[k] = (uint32_t*)(p + at); at += arr; }
-    for (int k = 0; k < 2; k++) { r.vals[k] = (uint32_t*)(p + at); at += arr; }
-    r.temp = p + at; at += up(temp_bytes);
-    r.temp_bytes = temp_bytes;
-    r.bytes = at;
-    return r;
+// Three arrays of [num_triangles][3] floats, or six when src[3] is set, to the device
+void stage_arrays(Uploader& up, float* const dst[6], const float* const src[6], int32_t num_triangles) {
+    for (int k = 0; k < (src[3] ? 6 : 3); k++) up.copy(dst[k], src[k], (size_t)num_triangles * 3 * sizeof(float));
 }
 
-// pt_update_meshes' part for instanced meshes (below, with the shape refit it ends in): both workspaces, before the
-// first copy; the kernels on the context's stream, after the arrays were staged in `in` (in[3..5] NULL: normals kept);
-// the meshes' boxes back into the host tables and the lights, which ends in a synchronise.
-int blas_refit_prepare(Ctx* c);
-int blas_refit_launch(Ctx* c, int32_t num_triangles, const float* const in[6]);
-int blas_refit_finish(Ctx* c);
+// A read-back the caller may not want (dst NULL) or that may be empty
+hipError_t read_back(Ctx* c, void* dst, const void* src, size_t bytes) {
+    if (!dst || !bytes) return hipSuccess;
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
+}
 
-// What an update runs from, made by update_prepare before anything is staged
-struct UpdateDev {
-    RefitDev D;
-    NormalsDev N;
-    bool blas, smooth;
-};
-// The vertices of the lights that are loose emissive triangles: the caller's arrays (in pt_scene_desc order), or with
-// `kept` the rest vertices pt_set_rest_pose kept, 9 floats per light
-struct LightVerts {
-    const float *v1, *v2, *v3;
-    const float* kept;
-};
+// The argument checks of the mesh entry points; `who` starts the message
+int check_arrays(const std::string& who, const float* const a[6]) {
+    if (!a[0] || !a[1] || !a[2]) return fail(PT_ERR_INVALID_ARG, who + ": v1, v2 and v3 are required");
+    if ((a[3] != nullptr) != (a[4] != nullptr) || (a[3] != nullptr) != (a[5] != nullptr))
+        return fail(PT_ERR_INVALID_ARG, who + ": n1/n2/n3 must be all set or all NULL");
+    return PT_OK;
+}
+int check_normals_mode(const std::string& who, int32_t mode) {
+    if (mode == 0 || mode == PT_NORMALS_FACE || mode == PT_NORMALS_SMOOTH) return PT_OK;
+    return fail(PT_ERR_INVALID_ARG, who + ": normals_mode " + std::to_string(mode) + " is not 0 or a pt_normals_mode");
+}
+int check_mesh_update(const std::string& who, const pt_mesh_update* u) {
+    if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, who + ": reserved must be 0");
+    if (const int rc = check_normals_mode(who, u->normals_mode)) return rc;
+    if (u->normals_mode != 0 && (u->n1 || u->n2 || u->n3))
+        return fail(PT_ERR_INVALID_ARG, who + ": n1/n2/n3 are given and normals_mode derives them");
+    const float* const a[6] = {u->v1, u->v2, u->v3, u->n1, u->n2, u->n3};
+    return check_arrays(who, a);
+}
 
-// The first part of pt_update_triangles, pt_update_triangles_normals, pt_update_meshes (meshes: instanced meshes are
-// refitted too, not refused) and pt_pose_meshes, after their own argument checks: the checks against the scene, then
-// every workspace, before the first copy (a failed allocation leaves the scene untouched).  *launch is false when
-// the scene holds no triangle in any BVH: PT_OK, nothing to run.
-int update_prepare(Ctx* c, int32_t num_triangles, bool derive, int32_t mode, bool meshes, double* out_kernel_ms, UpdateDev& U,
-                   bool* launch) {
-    *launch = false;
-    if (derive && mode != PT_NORMALS_FACE && mode != PT_NORMALS_SMOOTH)
-        return fail(PT_ERR_INVALID_ARG, "update: mode " + std::to_string(mode) + " is not a pt_normals_mode");
-    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    const pt::RefitTables& T = c->refit;
-    if (num_triangles != T.num_triangles)
-        return fail(PT_ERR_INVALID_ARG, "update: num_triangles is " + std::to_string(num_triangles) + ", the uploaded scene has " +
-                                            std::to_string(T.num_triangles));
-    if (c->has_blas && !meshes)
-        return fail(PT_ERR_UNSUPPORTED, "update: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
-                                        "its BLAS is not refitted");
-    if (out_kernel_ms) *out_kernel_ms = 0.0;
-    U.blas = c->has_blas && num_triangles > 0;
-    if (T.num_chunks == 0 && !U.blas) return PT_OK;   // no triangle in a BVH (num_triangles == 0, or none of them in Scene.Shapes)
-    PT_HIP(hipSetDevice(c->device));
-    U.smooth = derive && mode == PT_NORMALS_SMOOTH;
-    if (U.smooth && (int64_t)num_triangles * 3 > (int64_t)INT32_MAX)
-        return fail(PT_ERR_UNSUPPORTED, "update: PT_NORMALS_SMOOTH numbers corners in 31 bits");
-    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
-    U.N = NormalsDev{};
-    if (U.smooth) {
-        const bool first = !c->normals_dev.ptr;
-        if (first) {
-            size_t temp = 0;
-            PT_HIP(pt::normals_sort_temp_bytes((int64_t)num_triangles * 3, T.num_groups, &temp));
-            U.N = normals_layout(T, temp, nullptr);
-            if (hipMalloc(&c->normals_dev.ptr, U.N.bytes) != hipSuccess) {
-                c->normals_dev.ptr = nullptr;
-                (void)hipGetLastError();
-                return fail(PT_ERR_OUT_OF_MEMORY, "normals workspace allocation");
-            }
-            c->normals_dev.bytes = U.N.bytes;
-            c->normals_temp_bytes = temp;
-        }
-        U.N = normals_layout(T, c->normals_temp_bytes, c->normals_dev.ptr);
-        if (first)
-            PT_HIP(hipMemcpyAsync(U.N.group, T.tri_group.data(), T.tri_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
-    if (const int rc = ensure_refit_dev(c, U.D)) return rc;
-    if (U.blas) if (const int rc = blas_refit_prepare(c)) return rc;
-    *launch = true;
+// ---- the shape refit's device side (pt_update_shapes, and pt_update_meshes on instanced meshes ends in it)
+int ensure_shapes_ws(Ctx* c) {
+    const pt::ShapeRefitTables& T = c->dyn.shape_refit;
+    return ensure_workspace(c, c->dyn.shapes_ws, "shape refit", [&](void* base) { return pt::shapes_layout(T, base); },
+                            [&](const pt::ShapesDev& D, Uploader& up) {
+                                up(D.level_nodes, T.level_nodes);
+                                up(D.xf_kind, T.xf_kind);
+                                up(D.xf_index, T.xf_index);
+                                up(D.xf_inner_box, T.xf_inner_box);
+                                up(D.rec_box, T.rec_box);   // top-level SDF and Volume records keep these
+                            });
+}
+// The current parameters (ShapeRefitTables) into their staged copies, on the context's stream
+int stage_shape_params(Ctx* c) {
+    const pt::ShapeRefitTables& T = c->dyn.shape_refit;
+    const pt::ShapesDev& D = c->dyn.shapes_ws.at;
+    Uploader up{c->stream};
+    up(D.sphere_center, T.sphere_center);
+    up(D.sphere_radius, T.sphere_radius);
+    up(D.cube_min, T.cube_min);
+    up(D.cube_max, T.cube_max);
+    up(D.xf_matrix, T.xf_matrix);
+    up(D.xf_inverse, T.xf_inverse);
+    return check_hip(up.err, "staging the shape parameters");
+}
+// The shape refit from the staged parameters
+int launch_shapes(Ctx* c) {
+    const pt::ShapeRefitTables& T = c->dyn.shape_refit;
+    const pt::ShapesDev& D = c->dyn.shapes_ws.at;
+    const pt::ShapeParams P{T.num_spheres, T.num_cubes, T.num_transformed, D.sphere_center, D.sphere_radius,
+                            D.cube_min, D.cube_max, D.xf_matrix, D.xf_inverse};
+    PT_HIP(pt::launch_shape_refit(P, T.num_nodes, T.num_recs, T.num_heavy, (int64_t)T.level_off.size() - 1, T.level_off.data(),
+                                  D.level_nodes, (uint32_t*)const_cast<float4*>(c->S.ana_nodes),
+                                  (uint32_t*)const_cast<float4*>(c->S.ana_recs), (uint32_t*)const_cast<float4*>(c->S.ext_recs),
+                                  const_cast<pt::DevXform*>(c->S.xforms), (uint32_t*)const_cast<float4*>(c->S.heavy), D.xf_kind,
+                                  D.xf_index, D.xf_inner_box, D.xbox, D.rec_box, D.node_box, c->stream));
     return PT_OK;
 }
 
-// pt_rebuild_meshes' part of update_run: the new topology, and the line its chunks start at (the upload's, or later
+// ---- pt_update_meshes' part for instanced meshes
+// Both workspaces, before the first copy, then the parameters the shape refit at the end runs from
+int blas_refit_prepare(Ctx* c) {
+    if (const int rc = ensure_shapes_ws(c)) return rc;
+    const pt::BlasRefitTables& T = c->dyn.blas_refit;
+    pt::BlasBlocks B;
+    if (!c->dyn.blas_ws.mem.ptr) pt::blas_blocks(T, pt::blas_bounds_span(), B);
+    bool first = false;
+    if (const int rc = ensure_workspace(c, c->dyn.blas_ws, "BLAS refit", [&](void* base) { return pt::blas_layout(T, B.blas.size(), base); },
+                                        [&](const pt::BlasDev& D, Uploader& up) {
+                                            up(D.desc, T.desc);
+                                            up(D.src_of_pos, T.src_of_pos);
+                                            up(D.level_nodes, T.level_nodes);
+                                            up(D.level_blas, T.level_blas);
+                                            up(D.block_blas, B.blas);
+                                            up(D.block_first, B.first);
+                                            up(D.blas_block_off, B.off);
+                                            up(D.xf_blas, T.xf_blas);
+                                        },
+                                        &first))
+        return rc;   // (a failed upload released the workspace: hipFree waits for the copies issued from B)
+    if (first) {     // B goes out of scope
+        const int rc = check_hip(hipStreamSynchronize(c->stream), "BLAS refit workspace tables");
+        if (rc != PT_OK) { c->dyn.blas_ws.release(); return rc; }
+    }
+    return stage_shape_params(c);
+}
+// The kernels on the context's stream, after the arrays were staged in `in` (in[3..5] NULL: normals kept)
+int blas_refit_launch(Ctx* c, int32_t num_triangles, const float* const in[6]) {
+    const pt::BlasRefitTables& T = c->dyn.blas_refit;
+    const pt::BlasDev& D = c->dyn.blas_ws.at;
+    PT_HIP(pt::launch_blas_refit((int64_t)T.num_blas(), T.num_tris, T.num_nodes, num_triangles, (int64_t)T.xf_blas.size(),
+                                 (int64_t)D.num_blocks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes,
+                                 D.level_blas, D.desc, D.src_of_pos, D.block_blas, D.block_first, D.blas_block_off, D.xf_blas,
+                                 (uint32_t*)const_cast<float4*>(c->S.blas_nodes), (uint32_t*)const_cast<float4*>(c->S.blas_recs),
+                                 (uint32_t*)const_cast<float4*>(c->S.blas_shade), in[0], in[1], in[2], in[3], in[4], in[5],
+                                 D.tri_box, D.node_box, D.block_part, D.blas_box, c->dyn.shapes_ws.at.xf_inner_box, c->stream));
+    c->dyn.blas_boxes_on_device = true;
+    return launch_shapes(c);
+}
+// The meshes' boxes back into the host tables and the lights; synchronises the context's stream
+int blas_refit_finish(Ctx* c) {
+    const pt::BlasRefitTables& T = c->dyn.blas_refit;
+    pt::ShapeRefitTables& ST = c->dyn.shape_refit;
+    std::vector<float> boxes(T.num_blas() * 6);
+    PT_HIP(hipMemcpyAsync(boxes.data(), c->dyn.blas_ws.at.blas_box, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));   // the lights below need the boxes
+    for (size_t t = 0; t < T.xf_blas.size() && 6 * t + 6 <= ST.xf_inner_box.size(); t++) {
+        const int64_t b = T.xf_blas[t];
+        if (b < 0 || (size_t)b >= T.num_blas()) continue;
+        std::memcpy(&ST.xf_inner_box[6 * t], &boxes[6 * (size_t)b], 6 * sizeof(float));
+    }
+    // lights that are transformed shapes over a mesh follow its box
+    if (pt::shape_refit_lights(ST, c->dyn.h_lights)) return upload_lights(c);
+    return PT_OK;
+}
+
+// ---- moving triangles: the path every triangle update takes
+int ensure_refit_ws(Ctx* c) {
+    const pt::RefitTables& T = c->dyn.refit;
+    return ensure_workspace(c, c->dyn.refit_ws, "refit", [&](void* base) { return pt::refit_layout(T, base); },
+                            [&](const pt::RefitDev& D, Uploader& up) {
+                                if (T.src_of_pos.empty()) return;
+                                up(D.src_of_pos, T.src_of_pos);
+                                up(D.level_nodes, T.level_nodes);
+                            });
+}
+
+enum class Normals { Kept, Given, Face, Smooth };   // the device's stay; staged in in[3..5]; derived there from the vertices
+Normals normals_of(int32_t mode, bool given) {
+    return mode == PT_NORMALS_FACE ? Normals::Face : mode == PT_NORMALS_SMOOTH ? Normals::Smooth : given ? Normals::Given : Normals::Kept;
+}
+// pt_rebuild_meshes' part of an update: the new topology, and the line its chunks start at (the upload's, or later
 // when the balanced tree has more nodes than the uploaded one had: nodes and chunks share one run of lines)
 struct RebuildRun {
     pt::RebuildPlan R;
     uint32_t chunk_line0;
 };
+// One update: update_prepare checks it and makes its workspaces, the caller stages its arrays in the refit
+// workspace's `in` after recording Ctx::ev0, update_run runs it
+struct UpdateCall {
+    int32_t num_triangles;
+    Normals normals;
+    const float* light_verts[3];   // the vertices of the lights that are loose emissive triangles: the caller's v1, v2, v3
+                                   // (pt_scene_desc order), or NULL: the rest vertices pt_set_rest_pose kept
+    const RebuildRun* rebuild;     // pt_rebuild_meshes: re-sorted before the refit (NULL: the topology stays)
+};
+// Whether the scene's instanced meshes take part in an update (update_prepare refused it for an entry point that
+// does not refit them)
+bool refits_blas(const Ctx* c, const UpdateCall& U) { return c->dyn.has_blas && U.num_triangles > 0; }
 
-// The second part, from the arrays staged in U.D.in on the context's stream after Ctx::ev0 was recorded there: the
-// normals when they are derived, the refit of the world triangle BVH, the BLAS path, the root box, the lights, the
-// timing.  normals: U.D.in[3..5] hold normals, given or to be derived (false: the device's are kept).
-int update_run(Ctx* c, const UpdateDev& U, int32_t num_triangles, bool derive, bool normals, const LightVerts& L,
-               double* out_kernel_ms, const RebuildRun* rebuild = nullptr) {
-    pt::RefitTables& T = c->refit;
-    const RefitDev& D = U.D;
-    const NormalsDev& N = U.N;
+// The checks against the scene (meshes: the entry point refits instanced meshes too, it does not refuse them), then
+// every workspace, before the first copy (a failed allocation leaves the scene untouched).  *launch is false when
+// the scene holds no triangle in any BVH: PT_OK, nothing to run.
+int update_prepare(Ctx* c, const UpdateCall& U, bool meshes, double* out_kernel_ms, bool* launch) {
+    *launch = false;
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const pt::RefitTables& T = Y.refit;
+    if (U.num_triangles != T.num_triangles)
+        return fail(PT_ERR_INVALID_ARG, "update: num_triangles is " + std::to_string(U.num_triangles) + ", the uploaded scene has " +
+                                            std::to_string(T.num_triangles));
+    if (Y.has_blas && !meshes)
+        return fail(PT_ERR_UNSUPPORTED, "update: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
+                                        "its BLAS is not refitted");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    const bool blas = refits_blas(c, U);
+    if (T.num_chunks == 0 && !blas) return PT_OK;   // no triangle in a BVH (num_triangles == 0, or none of them in Scene.Shapes)
+    PT_HIP(hipSetDevice(c->device));
+    const bool smooth = U.normals == Normals::Smooth;
+    if (smooth && (int64_t)U.num_triangles * 3 > (int64_t)INT32_MAX)
+        return fail(PT_ERR_UNSUPPORTED, "update: PT_NORMALS_SMOOTH numbers corners in 31 bits");
+    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
+    if (smooth) {
+        size_t temp = 0;
+        if (!Y.normals_ws.mem.ptr) PT_HIP(pt::normals_sort_temp_bytes((int64_t)U.num_triangles * 3, T.num_groups, &temp));
+        if (const int rc = ensure_workspace(c, Y.normals_ws, "normals", [&](void* base) { return pt::normals_layout(T, temp, base); },
+                                            [&](const pt::NormalsDev& N, Uploader& up) { up(N.group, T.tri_group); }))
+            return rc;
+    }
+    if (const int rc = ensure_refit_ws(c)) return rc;
+    if (blas) if (const int rc = blas_refit_prepare(c)) return rc;
+    *launch = true;
+    return PT_OK;
+}
+
+// From the arrays staged in the refit workspace on the context's stream after Ctx::ev0 was recorded there: the
+// normals when they are derived, the re-sort of a rebuild, the refit of the world triangle BVH, the BLAS path, the
+// root box, the lights, the timing.
+int update_run(Ctx* c, const UpdateCall& U, double* out_kernel_ms) {
+    SceneDyn& Y = c->dyn;
+    pt::RefitTables& T = Y.refit;
+    const pt::RefitDev& D = Y.refit_ws.at;
     uint32_t* nodes = (uint32_t*)const_cast<float4*>(c->S.tri_nodes);
-    if (derive)
-        PT_HIP(pt::launch_normals(U.smooth, num_triangles, D.in[0], D.in[1], D.in[2], D.in[3], D.in[4], D.in[5], N.group, T.num_groups,
+    if (U.normals == Normals::Face || U.normals == Normals::Smooth) {
+        const bool smooth = U.normals == Normals::Smooth;
+        const pt::NormalsDev N = smooth ? Y.normals_ws.at : pt::NormalsDev{};
+        PT_HIP(pt::launch_normals(smooth, U.num_triangles, D.in[0], D.in[1], D.in[2], D.in[3], D.in[4], D.in[5], N.group, T.num_groups,
                                   N.keys[0], N.keys[1], N.vals[0], N.vals[1], N.temp, N.temp_bytes, c->stream));
-    if (rebuild) {
-        // pt_rebuild_meshes: the re-sort and the new topology before the refit, which then runs over the new tables.
-        // D was laid out for the tables before: the new ones are no larger, so its scratch boxes hold them.
-        const pt::RebuildPlan& R = rebuild->R;
-        if (rebuild->chunk_line0 != c->S.tri_chunk_line0) {   // more nodes than the upload had: the chunks start later
-            c->S.tri_chunk_line0 = rebuild->chunk_line0;
-            c->S.tri_chunks = c->S.lines + 8 * (size_t)rebuild->chunk_line0;
+    }
+    if (U.rebuild) {
+        // the re-sort and the new topology before the refit, which then runs over the new tables: D reserved room for
+        // them when it was laid out (pt_update_layout.h refit_layout)
+        const pt::RebuildPlan& R = U.rebuild->R;
+        if (U.rebuild->chunk_line0 != c->S.tri_chunk_line0) {   // more nodes than the upload had: the chunks start later
+            c->S.tri_chunk_line0 = U.rebuild->chunk_line0;
+            c->S.tri_chunks = c->S.lines + 8 * (size_t)U.rebuild->chunk_line0;
         }
-        PT_HIP(pt::launch_rebuild(R, c->rebuild_dev.ptr, c->rebuild_temp_bytes, nodes, (uint32_t*)const_cast<float4*>(c->S.tri_chunks),
+        PT_HIP(pt::launch_rebuild(R, Y.rebuild_ws.mem.ptr, Y.rebuild_ws.at.temp_bytes, nodes, (uint32_t*)const_cast<float4*>(c->S.tri_chunks),
                                   (uint32_t*)const_cast<float4*>(c->S.tri_recs), D.src_of_pos, D.level_nodes, D.in[0], D.in[1],
                                   D.in[2], c->stream));
         T.num_nodes = R.num_nodes;
@@ -1484,74 +1568,83 @@ int update_run(Ctx* c, const UpdateDev& U, int32_t num_triangles, bool derive, b
         // tree has no more chunks, and no more nodes than chunks (pt_stack_key.h)
         if (c->S.tri_num_nodes <= 64) c->S.route = 0;
     }
+    const bool normals = U.normals != Normals::Kept;
+    const float* const in[6] = {D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
+                                normals ? D.in[5] : nullptr};
     PT_HIP(pt::launch_refit(T.num_chunks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes, nodes,
                             (uint32_t*)const_cast<float4*>(c->S.tri_chunks), (uint32_t*)const_cast<float4*>(c->S.tri_recs),
-                            D.src_of_pos, D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
-                            normals ? D.in[5] : nullptr, D.node_box, D.chunk_box, c->stream));
-    if (U.blas) {
-        const float* const in[6] = {D.in[0], D.in[1], D.in[2], normals ? D.in[3] : nullptr, normals ? D.in[4] : nullptr,
-                                    normals ? D.in[5] : nullptr};
-        if (const int rc = blas_refit_launch(c, num_triangles, in)) return rc;
-    }
+                            D.src_of_pos, in[0], in[1], in[2], in[3], in[4], in[5], D.node_box, D.chunk_box, c->stream));
+    if (refits_blas(c, U)) if (const int rc = blas_refit_launch(c, U.num_triangles, in)) return rc;
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     // the root box follows (pt_wavefront.hip's refill kernels skip the triangle phase of a ray that misses it)
     uint32_t root[pt::kNode8Words];
     if (T.num_chunks > 0) PT_HIP(hipMemcpyAsync(root, nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
-    if (rebuild)
+    if (U.rebuild)
         PT_HIP(hipMemcpyAsync(T.src_of_pos.data(), D.src_of_pos, T.src_of_pos.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     // lights that are loose emissive triangles: their sphere from the new vertices
     bool lights_moved = false;
-    for (size_t i = 0; i < c->h_lights.size() && i < T.light_tri.size(); i++) {
+    for (size_t i = 0; i < Y.h_lights.size() && i < T.light_tri.size(); i++) {
         const int64_t j = T.light_tri[i];
         if (j < 0) continue;
-        if (L.kept) pt::tri_light_sphere(L.kept + 9 * i, L.kept + 9 * i + 3, L.kept + 9 * i + 6, c->h_lights[i]);
-        else pt::tri_light_sphere(L.v1 + 3 * j, L.v2 + 3 * j, L.v3 + 3 * j, c->h_lights[i]);
+        const float* const* v = U.light_verts;
+        const float* kept = v[0] ? nullptr : &Y.rest_light_verts[9 * i];
+        if (v[0]) pt::tri_light_sphere(v[0] + 3 * j, v[1] + 3 * j, v[2] + 3 * j, Y.h_lights[i]);
+        else pt::tri_light_sphere(kept, kept + 3, kept + 6, Y.h_lights[i]);
         lights_moved = true;
     }
-    if (lights_moved)
-        PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
-                              hipMemcpyHostToDevice, c->stream));
-    if (U.blas) if (const int rc = blas_refit_finish(c)) return rc;
+    if (lights_moved) if (const int rc = upload_lights(c)) return rc;
+    if (refits_blas(c, U)) if (const int rc = blas_refit_finish(c)) return rc;
     PT_HIP(hipStreamSynchronize(c->stream));
     if (T.num_chunks > 0) pt::tri_root_box(root, c->S.tri_box);
-    if (out_kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *out_kernel_ms = ms;
-    }
-    return PT_OK;
+    return kernel_ms(c, out_kernel_ms);
 }
 
-// pt_update_triangles (mode 0: the normals given, or kept), pt_update_triangles_normals (mode: a pt_normals_mode) and
-// pt_update_meshes: the host arrays checked, staged, and the update run from them
-int update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
-                     const float* n2, const float* n3, bool derive, int32_t mode, bool meshes, double* out_kernel_ms) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
-    if (!v1 || !v2 || !v3) return fail(PT_ERR_INVALID_ARG, "update: v1, v2 and v3 are required");
-    if ((n1 != nullptr) != (n2 != nullptr) || (n1 != nullptr) != (n3 != nullptr))
-        return fail(PT_ERR_INVALID_ARG, "update: n1/n2/n3 must be all set or all NULL");
-    UpdateDev U{};
-    bool launch = false;
-    if (const int rc = update_prepare(c, num_triangles, derive, mode, meshes, out_kernel_ms, U, &launch)) return rc;
-    if (!launch) return PT_OK;
-    c->pose_staged = false;   // the staged arrays are this update's from here on
-    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
-    const float* src[6] = {v1, v2, v3, n1, n2, n3};
-    for (int k = 0; k < (n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(U.D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
+// An update from host arrays: src staged (NULL: the pose pt_pose_meshes left staged is used and stays readable), then run
+int update_stage_and_run(Ctx* c, const UpdateCall& U, const float* const src[6], double* out_kernel_ms) {
+    if (src) {
+        c->dyn.pose_staged = false;   // the staged arrays are this update's from here on
+        Uploader up{c->stream};
+        stage_arrays(up, c->dyn.refit_ws.at.in, src, U.num_triangles);
+        if (const int rc = check_hip(up.err, "staging the triangle arrays")) return rc;
+    }
     PT_HIP(hipEventRecord(c->ev0, c->stream));
-    return update_run(c, U, num_triangles, derive, n1 || derive, LightVerts{v1, v2, v3, nullptr}, out_kernel_ms);
+    return update_run(c, U, out_kernel_ms);
+}
+// pt_update_triangles, pt_update_triangles_normals and pt_update_meshes after their argument checks
+int update_triangles(Ctx* c, int32_t num_triangles, const float* const src[6], int32_t mode, bool meshes, double* out_kernel_ms) {
+    const UpdateCall U{num_triangles, normals_of(mode, src[3]), {src[0], src[1], src[2]}, nullptr};
+    bool launch = false;
+    if (const int rc = update_prepare(c, U, meshes, out_kernel_ms, &launch)) return rc;
+    return launch ? update_stage_and_run(c, U, src, out_kernel_ms) : PT_OK;
 }
 }  // namespace
 
+extern "C" {
+
 int pt_update_triangles(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
                         const float* n2, const float* n3, double* out_kernel_ms) {
-    return update_triangles(ctx, num_triangles, v1, v2, v3, n1, n2, n3, false, 0, false, out_kernel_ms);
+    if (!ctx) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    const float* const src[6] = {v1, v2, v3, n1, n2, n3};
+    if (const int rc = check_arrays("update", src)) return rc;
+    return update_triangles((Ctx*)ctx, num_triangles, src, 0, false, out_kernel_ms);
 }
 
 int pt_update_triangles_normals(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, int32_t mode,
                                 double* out_kernel_ms) {
-    return update_triangles(ctx, num_triangles, v1, v2, v3, nullptr, nullptr, nullptr, true, mode, false, out_kernel_ms);
+    if (!ctx) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    const float* const src[6] = {v1, v2, v3, nullptr, nullptr, nullptr};
+    if (const int rc = check_arrays("update", src)) return rc;
+    if (mode != PT_NORMALS_FACE && mode != PT_NORMALS_SMOOTH)
+        return fail(PT_ERR_INVALID_ARG, "update: mode " + std::to_string(mode) + " is not a pt_normals_mode");
+    return update_triangles((Ctx*)ctx, num_triangles, src, mode, false, out_kernel_ms);
+}
+
+int pt_update_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms) {
+    if (!ctx) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!u) return fail(PT_ERR_INVALID_ARG, "update meshes: u is NULL");
+    if (const int rc = check_mesh_update("update meshes", u)) return rc;
+    const float* const src[6] = {u->v1, u->v2, u->v3, u->n1, u->n2, u->n3};
+    return update_triangles((Ctx*)ctx, u->num_triangles, src, u->normals_mode, true, out_kernel_ms);
 }
 
 int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3) {
@@ -1559,7 +1652,7 @@ int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3) {
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!n1 || !n2 || !n3) return fail(PT_ERR_INVALID_ARG, "read normals: n1, n2 and n3 are required");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    const pt::RefitTables& T = c->refit;
+    const pt::RefitTables& T = c->dyn.refit;
     if (T.num_triangles <= 0) return PT_OK;
     const size_t arr = (size_t)T.num_triangles * 3 * sizeof(float);
     float* out[3] = {n1, n2, n3};
@@ -1568,10 +1661,10 @@ int pt_read_tri_normals(void* ctx, float* n1, float* n2, float* n3) {
         return PT_OK;
     }
     PT_HIP(hipSetDevice(c->device));
-    RefitDev D{};
-    if (const int rc = ensure_refit_dev(c, D)) return rc;
+    if (const int rc = ensure_refit_ws(c)) return rc;
+    const pt::RefitDev& D = c->dyn.refit_ws.at;
     // the staged normal arrays are free between updates: a triangle outside the BVH reads as zeros
-    c->pose_staged = false;
+    c->dyn.pose_staged = false;
     for (int k = 3; k < 6; k++) PT_HIP(hipMemsetAsync(D.in[k], 0, arr, c->stream));
     PT_HIP(pt::launch_normals_gather((int64_t)T.src_of_pos.size(), (const uint32_t*)c->S.tri_recs, D.src_of_pos, D.in[3], D.in[4],
                                      D.in[5], c->stream));
@@ -1584,311 +1677,52 @@ int pt_read_tri_bvh(void* ctx, int64_t counts[3], uint32_t* nodes, uint32_t* chu
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    const pt::RefitTables& T = c->refit;
+    const pt::RefitTables& T = c->dyn.refit;
     if (counts) { counts[0] = T.num_nodes; counts[1] = T.num_chunks; counts[2] = (int64_t)T.src_of_pos.size(); }
     if (out_box) std::memcpy(out_box, c->S.tri_box, sizeof c->S.tri_box);
     PT_HIP(hipSetDevice(c->device));
     const size_t line = pt::kNode8Words * sizeof(uint32_t);
-    if (nodes && T.num_nodes) PT_HIP(hipMemcpyAsync(nodes, c->S.tri_nodes, (size_t)T.num_nodes * line, hipMemcpyDeviceToHost, c->stream));
-    if (chunks && T.num_chunks) PT_HIP(hipMemcpyAsync(chunks, c->S.tri_chunks, (size_t)T.num_chunks * line, hipMemcpyDeviceToHost, c->stream));
-    if (records && !T.src_of_pos.empty())
-        PT_HIP(hipMemcpyAsync(records, c->S.tri_recs, T.src_of_pos.size() * line, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(read_back(c, nodes, c->S.tri_nodes, (size_t)T.num_nodes * line));
+    PT_HIP(read_back(c, chunks, c->S.tri_chunks, (size_t)T.num_chunks * line));
+    PT_HIP(read_back(c, records, c->S.tri_recs, T.src_of_pos.size() * line));
     PT_HIP(hipStreamSynchronize(c->stream));
     return PT_OK;
 }
 
-// ---- moving spheres, cubes and transformed shapes
-namespace {
-// The parts of Ctx::shapes_dev, each 256-B aligned: [the staged parameters | xbox | rec_box | node_box | level_nodes |
-// the transformed shapes' inner kind, index and box]
-struct ShapesDev {
-    float* sphere_center;
-    double* sphere_radius;
-    float* cube_min;
-    float* cube_max;
-    double* xf_matrix;
-    double* xf_inverse;
-    float* xbox;
-    float* rec_box;
-    float* node_box;
-    uint32_t* level_nodes;
-    int32_t* xf_kind;
-    int32_t* xf_index;
-    float* xf_inner_box;
-    size_t bytes;
-};
-ShapesDev shapes_layout(const pt::ShapeRefitTables& T, void* base) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    ShapesDev r{};
-    size_t at = 0;
-    char* p = (char*)base;
-    const size_t ns = (size_t)T.num_spheres, nc = (size_t)T.num_cubes, nx = (size_t)T.num_transformed;
-    r.sphere_center = (float*)(p + at); at += up(ns * 3 * sizeof(float));
-    r.sphere_radius = (double*)(p + at); at += up(ns * sizeof(double));
-    r.cube_min = (float*)(p + at); at += up(nc * 3 * sizeof(float));
-    r.cube_max = (float*)(p + at); at += up(nc * 3 * sizeof(float));
-    r.xf_matrix = (double*)(p + at); at += up(nx * 16 * sizeof(double));
-    r.xf_inverse = (double*)(p + at); at += up(nx * 16 * sizeof(double));
-    r.xbox = (float*)(p + at); at += up(nx * 6 * sizeof(float));
-    r.rec_box = (float*)(p + at); at += up((size_t)T.num_recs * 6 * sizeof(float));
-    r.node_box = (float*)(p + at); at += up((size_t)T.num_nodes * 6 * sizeof(float));
-    r.level_nodes = (uint32_t*)(p + at); at += up(T.level_nodes.size() * sizeof(uint32_t));
-    r.xf_kind = (int32_t*)(p + at); at += up(nx * sizeof(int32_t));
-    r.xf_index = (int32_t*)(p + at); at += up(nx * sizeof(int32_t));
-    r.xf_inner_box = (float*)(p + at); at += up(nx * 6 * sizeof(float));
-    r.bytes = at + 256;   // never an empty allocation
-    return r;
-}
-hipError_t shapes_copy_bytes(void* dst, const void* src, size_t bytes, hipStream_t s) {
-    if (!bytes) return hipSuccess;
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-}
-#define shapes_copy(dst, vec, s) shapes_copy_bytes((dst), (vec).data(), (vec).size() * sizeof((vec)[0]), (s))
-// Ctx::shapes_dev, allocated and its tables uploaded (on the context's stream) at the first use after an upload
-int ensure_shapes_dev(Ctx* c, ShapesDev& D) {
-    const pt::ShapeRefitTables& T = c->shape_refit;
-    D = shapes_layout(T, nullptr);
-    const bool first = !c->shapes_dev.ptr;
-    if (first) {
-        if (hipMalloc(&c->shapes_dev.ptr, D.bytes) != hipSuccess) {
-            c->shapes_dev.ptr = nullptr;
-            (void)hipGetLastError();
-            return fail(PT_ERR_OUT_OF_MEMORY, "shape refit workspace allocation");
-        }
-        c->shapes_dev.bytes = D.bytes;
-    }
-    D = shapes_layout(T, c->shapes_dev.ptr);
-    if (first) {
-        PT_HIP(shapes_copy(D.level_nodes, T.level_nodes, c->stream));
-        PT_HIP(shapes_copy(D.xf_kind, T.xf_kind, c->stream));
-        PT_HIP(shapes_copy(D.xf_index, T.xf_index, c->stream));
-        PT_HIP(shapes_copy(D.xf_inner_box, T.xf_inner_box, c->stream));
-        PT_HIP(shapes_copy(D.rec_box, T.rec_box, c->stream));   // top-level SDF and Volume records keep these
-    }
-    return PT_OK;
-}
-// The current parameters (ShapeRefitTables) into their staged copies, on the context's stream
-int stage_shape_params(Ctx* c, const ShapesDev& D) {
-    const pt::ShapeRefitTables& T = c->shape_refit;
-    PT_HIP(shapes_copy(D.sphere_center, T.sphere_center, c->stream));
-    PT_HIP(shapes_copy(D.sphere_radius, T.sphere_radius, c->stream));
-    PT_HIP(shapes_copy(D.cube_min, T.cube_min, c->stream));
-    PT_HIP(shapes_copy(D.cube_max, T.cube_max, c->stream));
-    PT_HIP(shapes_copy(D.xf_matrix, T.xf_matrix, c->stream));
-    PT_HIP(shapes_copy(D.xf_inverse, T.xf_inverse, c->stream));
-    return PT_OK;
-}
-// The shape refit from the staged parameters
-int launch_shapes(Ctx* c, const ShapesDev& D) {
-    const pt::ShapeRefitTables& T = c->shape_refit;
-    const pt::ShapeParams P{T.num_spheres, T.num_cubes, T.num_transformed, D.sphere_center, D.sphere_radius,
-                            D.cube_min, D.cube_max, D.xf_matrix, D.xf_inverse};
-    PT_HIP(pt::launch_shape_refit(P, T.num_nodes, T.num_recs, T.num_heavy, (int64_t)T.level_off.size() - 1, T.level_off.data(),
-                                  D.level_nodes, (uint32_t*)const_cast<float4*>(c->S.ana_nodes),
-                                  (uint32_t*)const_cast<float4*>(c->S.ana_recs), (uint32_t*)const_cast<float4*>(c->S.ext_recs),
-                                  const_cast<pt::DevXform*>(c->S.xforms), (uint32_t*)const_cast<float4*>(c->S.heavy), D.xf_kind,
-                                  D.xf_index, D.xf_inner_box, D.xbox, D.rec_box, D.node_box, c->stream));
-    return PT_OK;
-}
-
-// The parts of Ctx::blas_dev, each 256-B aligned: [the tables | tri_box | node_box | block_part | blas_box]
-struct BlasDev {
-    int32_t* desc;
-    int32_t* src_of_pos;
-    uint32_t* level_nodes;
-    int32_t* level_blas;
-    int32_t* block_blas;
-    int32_t* block_first;
-    int32_t* blas_block_off;
-    int32_t* xf_blas;
-    float* tri_box;
-    float* node_box;
-    float* block_part;
-    float* blas_box;
-    size_t bytes;
-};
-// k_blas_bounds' blocks: each folds up to pt::blas_bounds_span() positions of one BLAS
-struct BlasBlocks {
-    std::vector<int32_t> blas, first, off;   // per block its BLAS and first position; per BLAS its first block (and the end)
-};
-void blas_blocks(const pt::BlasRefitTables& T, BlasBlocks& B) {
-    const int64_t span = pt::blas_bounds_span();
-    for (size_t b = 0; b < T.num_blas(); b++) {
-        B.off.push_back((int32_t)B.blas.size());
-        const int64_t r0 = T.desc[4 * b + 2], n = T.desc[4 * b + 3];
-        for (int64_t at = 0; at < n; at += span) {
-            B.blas.push_back((int32_t)b);
-            B.first.push_back((int32_t)(r0 + at));
-        }
-    }
-    B.off.push_back((int32_t)B.blas.size());
-}
-BlasDev blas_layout(const pt::BlasRefitTables& T, size_t num_blocks, void* base) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    BlasDev r{};
-    size_t at = 0;
-    char* p = (char*)base;
-    const size_t i4 = sizeof(int32_t), nb = T.num_blas();
-    r.desc = (int32_t*)(p + at); at += up(T.desc.size() * i4);
-    r.src_of_pos = (int32_t*)(p + at); at += up(T.src_of_pos.size() * i4);
-    r.level_nodes = (uint32_t*)(p + at); at += up(T.level_nodes.size() * i4);
-    r.level_blas = (int32_t*)(p + at); at += up(T.level_blas.size() * i4);
-    r.block_blas = (int32_t*)(p + at); at += up(num_blocks * i4);
-    r.block_first = (int32_t*)(p + at); at += up(num_blocks * i4);
-    r.blas_block_off = (int32_t*)(p + at); at += up((nb + 1) * i4);
-    r.xf_blas = (int32_t*)(p + at); at += up(T.xf_blas.size() * i4);
-    r.tri_box = (float*)(p + at); at += up((size_t)T.num_tris * 6 * sizeof(float));
-    r.node_box = (float*)(p + at); at += up((size_t)T.num_nodes * 6 * sizeof(float));
-    r.block_part = (float*)(p + at); at += up(num_blocks * 6 * sizeof(float));
-    r.blas_box = (float*)(p + at); at += up(nb * 6 * sizeof(float));
-    r.bytes = at + 256;   // never an empty allocation
-    return r;
-}
-// Ctx::blas_dev, allocated and its tables uploaded (on the context's stream) at the first use after an upload
-int ensure_blas_dev(Ctx* c, BlasDev& D) {
-    const pt::BlasRefitTables& T = c->blas_refit;
-    if (!c->blas_dev.ptr) {
-        BlasBlocks B;
-        blas_blocks(T, B);
-        D = blas_layout(T, B.blas.size(), nullptr);
-        if (hipMalloc(&c->blas_dev.ptr, D.bytes) != hipSuccess) {
-            c->blas_dev.ptr = nullptr;
-            (void)hipGetLastError();
-            return fail(PT_ERR_OUT_OF_MEMORY, "BLAS refit workspace allocation");
-        }
-        c->blas_dev.bytes = D.bytes;
-        c->blas_num_blocks = B.blas.size();
-        D = blas_layout(T, c->blas_num_blocks, c->blas_dev.ptr);
-        PT_HIP(shapes_copy(D.desc, T.desc, c->stream));
-        PT_HIP(shapes_copy(D.src_of_pos, T.src_of_pos, c->stream));
-        PT_HIP(shapes_copy(D.level_nodes, T.level_nodes, c->stream));
-        PT_HIP(shapes_copy(D.level_blas, T.level_blas, c->stream));
-        PT_HIP(shapes_copy(D.block_blas, B.blas, c->stream));
-        PT_HIP(shapes_copy(D.block_first, B.first, c->stream));
-        PT_HIP(shapes_copy(D.blas_block_off, B.off, c->stream));
-        PT_HIP(shapes_copy(D.xf_blas, T.xf_blas, c->stream));
-        PT_HIP(hipStreamSynchronize(c->stream));   // B's arrays go out of scope
-    }
-    D = blas_layout(T, c->blas_num_blocks, c->blas_dev.ptr);
-    return PT_OK;
-}
-
-int blas_refit_prepare(Ctx* c) {
-    ShapesDev S{};
-    if (const int rc = ensure_shapes_dev(c, S)) return rc;
-    BlasDev D{};
-    if (const int rc = ensure_blas_dev(c, D)) return rc;
-    return stage_shape_params(c, S);   // the shape refit the BLAS refit ends in runs from the current parameters
-}
-
-int blas_refit_launch(Ctx* c, int32_t num_triangles, const float* const in[6]) {
-    const pt::BlasRefitTables& T = c->blas_refit;
-    ShapesDev S{};
-    if (const int rc = ensure_shapes_dev(c, S)) return rc;
-    BlasDev D{};
-    if (const int rc = ensure_blas_dev(c, D)) return rc;
-    PT_HIP(pt::launch_blas_refit((int64_t)T.num_blas(), T.num_tris, T.num_nodes, num_triangles, (int64_t)T.xf_blas.size(),
-                                 (int64_t)c->blas_num_blocks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes,
-                                 D.level_blas, D.desc, D.src_of_pos, D.block_blas, D.block_first, D.blas_block_off, D.xf_blas,
-                                 (uint32_t*)const_cast<float4*>(c->S.blas_nodes), (uint32_t*)const_cast<float4*>(c->S.blas_recs),
-                                 (uint32_t*)const_cast<float4*>(c->S.blas_shade), in[0], in[1], in[2], in[3], in[4], in[5],
-                                 D.tri_box, D.node_box, D.block_part, D.blas_box, S.xf_inner_box, c->stream));
-    c->blas_boxes_on_device = true;
-    return launch_shapes(c, S);
-}
-
-int blas_refit_finish(Ctx* c) {
-    const pt::BlasRefitTables& T = c->blas_refit;
-    pt::ShapeRefitTables& ST = c->shape_refit;
-    BlasDev D{};
-    if (const int rc = ensure_blas_dev(c, D)) return rc;
-    std::vector<float> boxes(T.num_blas() * 6);
-    PT_HIP(hipMemcpyAsync(boxes.data(), D.blas_box, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    PT_HIP(hipStreamSynchronize(c->stream));   // the lights below need the boxes
-    for (size_t t = 0; t < T.xf_blas.size() && 6 * t + 6 <= ST.xf_inner_box.size(); t++) {
-        const int64_t b = T.xf_blas[t];
-        if (b < 0 || (size_t)b >= T.num_blas()) continue;
-        std::memcpy(&ST.xf_inner_box[6 * t], &boxes[6 * (size_t)b], 6 * sizeof(float));
-    }
-    // lights that are transformed shapes over a mesh follow its box
-    if (pt::shape_refit_lights(ST, c->h_lights))
-        PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
-                              hipMemcpyHostToDevice, c->stream));
-    return PT_OK;
-}
-}  // namespace
-
-int pt_update_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms) {
-    if (!ctx) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
-    if (!u) return fail(PT_ERR_INVALID_ARG, "update meshes: u is NULL");
-    if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "update meshes: reserved must be 0");
-    if (u->normals_mode != 0 && u->normals_mode != PT_NORMALS_FACE && u->normals_mode != PT_NORMALS_SMOOTH)
-        return fail(PT_ERR_INVALID_ARG, "update meshes: normals_mode " + std::to_string(u->normals_mode) + " is not 0 or a pt_normals_mode");
-    if (u->normals_mode != 0 && (u->n1 || u->n2 || u->n3))
-        return fail(PT_ERR_INVALID_ARG, "update meshes: n1/n2/n3 are given and normals_mode derives them");
-    return update_triangles(ctx, u->num_triangles, u->v1, u->v2, u->v3, u->n1, u->n2, u->n3, u->normals_mode != 0, u->normals_mode,
-                            true, out_kernel_ms);
-}
-
 // ---- posing meshes by matrix on the device
-namespace {
-// The parts of Ctx::pose_dev, each 256-B aligned: [rest v1 v2 v3 n1 n2 n3 | group | matrices | mask]
-struct PoseDev {
-    float* rest[6];
-    int32_t* group;
-    double* matrices;
-    int32_t* mask;
-    size_t bytes;
-};
-PoseDev pose_layout(const pt::RefitTables& T, void* base) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    PoseDev r{};
-    size_t at = 0;
-    char* p = (char*)base;
-    const size_t arr = up((size_t)T.num_triangles * 3 * sizeof(float));
-    for (int k = 0; k < 6; k++) { r.rest[k] = (float*)(p + at); at += arr; }
-    r.group = (int32_t*)(p + at); at += up((size_t)T.num_triangles * sizeof(int32_t));
-    r.matrices = (double*)(p + at); at += up((size_t)T.num_groups * 16 * sizeof(double));
-    r.mask = (int32_t*)(p + at); at += up((size_t)T.num_groups * sizeof(int32_t));
-    r.bytes = at + 256;   // never an empty allocation
-    return r;
-}
-}  // namespace
-
 int pt_set_rest_pose(void* ctx, int32_t num_triangles, const float* v1, const float* v2, const float* v3, const float* n1,
                      const float* n2, const float* n3) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!v1 || !v2 || !v3 || !n1 || !n2 || !n3) return fail(PT_ERR_INVALID_ARG, "rest pose: v1, v2, v3, n1, n2 and n3 are required");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    const pt::RefitTables& T = c->refit;
+    SceneDyn& Y = c->dyn;
+    const pt::RefitTables& T = Y.refit;
     if (num_triangles != T.num_triangles)
         return fail(PT_ERR_INVALID_ARG, "rest pose: num_triangles is " + std::to_string(num_triangles) + ", the uploaded scene has " +
                                             std::to_string(T.num_triangles));
     PT_HIP(hipSetDevice(c->device));
-    const bool first = !c->pose_dev.ptr;
-    if (first) {
-        const PoseDev L = pose_layout(T, nullptr);
-        if (hipMalloc(&c->pose_dev.ptr, L.bytes) != hipSuccess) {
-            c->pose_dev.ptr = nullptr;
-            (void)hipGetLastError();
-            return fail(PT_ERR_OUT_OF_MEMORY, "pose workspace allocation");
-        }
-        c->pose_dev.bytes = L.bytes;
+    const float* const src[6] = {v1, v2, v3, n1, n2, n3};
+    // the first rest pose goes in with the workspace, the triangles' groups behind it
+    bool first = false;
+    if (const int rc = ensure_workspace(c, Y.pose_ws, "pose", [&](void* base) { return pt::pose_layout(T, base); },
+                                        [&](const pt::PoseDev& P, Uploader& up) {
+                                            stage_arrays(up, P.rest, src, num_triangles);
+                                            up(P.group, T.tri_group);
+                                        },
+                                        &first))
+        return rc;
+    if (!first) {
+        Uploader up{c->stream};
+        stage_arrays(up, Y.pose_ws.at.rest, src, num_triangles);
+        if (const int rc = check_hip(up.err, "staging the rest pose")) return rc;
     }
-    const PoseDev P = pose_layout(T, c->pose_dev.ptr);
-    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
-    const float* src[6] = {v1, v2, v3, n1, n2, n3};
-    if (arr)
-        for (int k = 0; k < 6; k++) PT_HIP(hipMemcpyAsync(P.rest[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
-    if (first && !T.tri_group.empty())
-        PT_HIP(hipMemcpyAsync(P.group, T.tri_group.data(), T.tri_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     // the lights that are loose emissive triangles return to these at every pose
-    c->rest_light_verts.assign(9 * c->h_lights.size(), 0.f);
-    for (size_t i = 0; i < c->h_lights.size() && i < T.light_tri.size(); i++) {
+    Y.rest_light_verts.assign(9 * Y.h_lights.size(), 0.f);
+    for (size_t i = 0; i < Y.h_lights.size() && i < T.light_tri.size(); i++) {
         const int64_t j = T.light_tri[i];
         if (j < 0 || j >= num_triangles) continue;
-        for (int k = 0; k < 3; k++) std::memcpy(&c->rest_light_verts[9 * i + 3 * k], src[k] + 3 * j, 3 * sizeof(float));
+        for (int k = 0; k < 3; k++) std::memcpy(&Y.rest_light_verts[9 * i + 3 * k], src[k] + 3 * j, 3 * sizeof(float));
     }
     PT_HIP(hipStreamSynchronize(c->stream));
     return PT_OK;
@@ -1899,48 +1733,43 @@ int pt_pose_meshes(void* ctx, const pt_mesh_pose* u, double* out_kernel_ms) {
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!u) return fail(PT_ERR_INVALID_ARG, "pose meshes: u is NULL");
     if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "pose meshes: reserved must be 0");
-    if (u->normals_mode != 0 && u->normals_mode != PT_NORMALS_FACE && u->normals_mode != PT_NORMALS_SMOOTH)
-        return fail(PT_ERR_INVALID_ARG, "pose meshes: normals_mode " + std::to_string(u->normals_mode) + " is not 0 or a pt_normals_mode");
+    if (const int rc = check_normals_mode("pose meshes", u->normals_mode)) return rc;
     if (!u->matrices) return fail(PT_ERR_INVALID_ARG, "pose meshes: matrices is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    const pt::RefitTables& T = c->refit;
+    const pt::RefitTables& T = c->dyn.refit;
     if (u->num_meshes != T.num_groups)
         return fail(PT_ERR_INVALID_ARG, "pose meshes: num_meshes is " + std::to_string(u->num_meshes) + ", the uploaded scene has " +
                                             std::to_string(T.num_groups));
-    if (!c->pose_dev.ptr) return fail(PT_ERR_INVALID_ARG, "pose meshes: no rest pose (pt_set_rest_pose)");
-    const bool derive = u->normals_mode != 0;
-    UpdateDev U{};
+    if (!c->dyn.pose_ws.mem.ptr) return fail(PT_ERR_INVALID_ARG, "pose meshes: no rest pose (pt_set_rest_pose)");
+    // the posed normals are staged unless a mode derives them; the lights return to their rest vertices
+    const UpdateCall U{T.num_triangles, normals_of(u->normals_mode, true), {nullptr, nullptr, nullptr}, nullptr};
     bool launch = false;
-    if (const int rc = update_prepare(c, T.num_triangles, derive, u->normals_mode, true, out_kernel_ms, U, &launch)) return rc;
+    if (const int rc = update_prepare(c, U, true, out_kernel_ms, &launch)) return rc;
     if (!launch) return PT_OK;
-    const PoseDev P = pose_layout(T, c->pose_dev.ptr);
+    const pt::PoseDev& P = c->dyn.pose_ws.at;
     const size_t nm = (size_t)T.num_groups;
     if (nm) {
         PT_HIP(hipMemcpyAsync(P.matrices, u->matrices, nm * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
         if (u->mesh_mask) PT_HIP(hipMemcpyAsync(P.mask, u->mesh_mask, nm * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
     PT_HIP(hipEventRecord(c->ev0, c->stream));
-    PT_HIP(pt::launch_pose(T.num_triangles, T.num_groups, P.group, u->mesh_mask ? P.mask : nullptr, P.matrices, !derive, P.rest,
-                           U.D.in, c->stream));
-    c->pose_staged = true;
-    return update_run(c, U, T.num_triangles, derive, true, LightVerts{nullptr, nullptr, nullptr, c->rest_light_verts.data()},
-                      out_kernel_ms);
+    PT_HIP(pt::launch_pose(T.num_triangles, T.num_groups, P.group, u->mesh_mask ? P.mask : nullptr, P.matrices, U.normals == Normals::Given,
+                           P.rest, c->dyn.refit_ws.at.in, c->stream));
+    c->dyn.pose_staged = true;
+    return update_run(c, U, out_kernel_ms);
 }
 
 int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n2, float* n3) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    if (!c->pose_staged || !c->refit_dev.ptr)
+    if (!c->dyn.pose_staged || !c->dyn.refit_ws.mem.ptr)
         return fail(PT_ERR_INVALID_ARG, "read pose: the staged arrays hold no pose (none made since the upload, or a later "
                                         "pt_update_* or pt_read_tri_normals reused them)");
-    const pt::RefitTables& T = c->refit;
     PT_HIP(hipSetDevice(c->device));
-    const RefitDev D = refit_layout(T, c->refit_dev.ptr);
-    const size_t arr = (size_t)T.num_triangles * 3 * sizeof(float);
+    const size_t arr = (size_t)c->dyn.refit.num_triangles * 3 * sizeof(float);
     float* out[6] = {v1, v2, v3, n1, n2, n3};
-    for (int k = 0; k < 6; k++)
-        if (out[k] && arr) PT_HIP(hipMemcpyAsync(out[k], D.in[k], arr, hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < 6; k++) PT_HIP(read_back(c, out[k], c->dyn.refit_ws.at.in[k], arr));
     PT_HIP(hipStreamSynchronize(c->stream));
     return PT_OK;
 }
@@ -1949,35 +1778,24 @@ int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n
 int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
-    bool derive = false;
-    int32_t mode = 0;
-    if (u) {
-        if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "rebuild meshes: reserved must be 0");
-        if (u->normals_mode != 0 && u->normals_mode != PT_NORMALS_FACE && u->normals_mode != PT_NORMALS_SMOOTH)
-            return fail(PT_ERR_INVALID_ARG, "rebuild meshes: normals_mode " + std::to_string(u->normals_mode) + " is not 0 or a pt_normals_mode");
-        if (u->normals_mode != 0 && (u->n1 || u->n2 || u->n3))
-            return fail(PT_ERR_INVALID_ARG, "rebuild meshes: n1/n2/n3 are given and normals_mode derives them");
-        if (!u->v1 || !u->v2 || !u->v3) return fail(PT_ERR_INVALID_ARG, "rebuild meshes: v1, v2 and v3 are required");
-        if ((u->n1 != nullptr) != (u->n2 != nullptr) || (u->n1 != nullptr) != (u->n3 != nullptr))
-            return fail(PT_ERR_INVALID_ARG, "rebuild meshes: n1/n2/n3 must be all set or all NULL");
-        derive = u->normals_mode != 0;
-        mode = u->normals_mode;
-    }
+    if (u) if (const int rc = check_mesh_update("rebuild meshes", u)) return rc;
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    if (!u && (!c->pose_staged || !c->refit_dev.ptr))
+    SceneDyn& Y = c->dyn;
+    if (!u && (!Y.pose_staged || !Y.refit_ws.mem.ptr))
         return fail(PT_ERR_INVALID_ARG, "rebuild meshes: u is NULL and the staged arrays hold no pose (pt_pose_meshes)");
-    if (c->has_blas)
+    if (Y.has_blas)
         return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
                                         "BLASes are not rebuilt");
-    const int32_t num_triangles = u ? u->num_triangles : c->refit.num_triangles;
-    UpdateDev U{};
+    // u NULL: the staged pose with its normals, the lights at their rest vertices
+    RebuildRun run{};
+    UpdateCall U{Y.refit.num_triangles, Normals::Given, {nullptr, nullptr, nullptr}, &run};
+    if (u) U = UpdateCall{u->num_triangles, normals_of(u->normals_mode, u->n1), {u->v1, u->v2, u->v3}, &run};
     bool launch = false;
-    if (const int rc = update_prepare(c, num_triangles, derive, mode, false, out_kernel_ms, U, &launch)) return rc;
+    if (const int rc = update_prepare(c, U, false, out_kernel_ms, &launch)) return rc;
     if (!launch) return PT_OK;
     // the new topology, checked against what the upload allocated, and the workspace: before anything is staged
-    RebuildRun run{};
     pt::RebuildPlan& R = run.R;
-    const int64_t P = (int64_t)c->refit.src_of_pos.size();
+    const int64_t P = (int64_t)Y.refit.src_of_pos.size();
     if (!pt::rebuild_plan(P, R) || pt::rebuild_stack_bound(R) > pt::kStackMax)
         return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: " + std::to_string(P) + " triangles need more than " +
                                             std::to_string(pt::kRebuildMaxLevels) + " levels");
@@ -1989,28 +1807,13 @@ int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms)
                                             std::to_string(node_cap + chunk_cap) + " lines");
     run.chunk_line0 = R.num_nodes <= node_cap && R.num_chunks <= chunk_cap ? c->S.tri_chunk_line0
                                                                             : c->S.tri_node_line0 + (uint32_t)R.num_nodes;
-    if (!c->rebuild_dev.ptr) {
-        size_t temp = 0, bytes = 0;
-        PT_HIP(pt::rebuild_workspace_bytes(P, &temp, &bytes));
-        if (hipMalloc(&c->rebuild_dev.ptr, bytes) != hipSuccess) {
-            c->rebuild_dev.ptr = nullptr;
-            (void)hipGetLastError();
-            return fail(PT_ERR_OUT_OF_MEMORY, "rebuild workspace allocation");
-        }
-        c->rebuild_dev.bytes = bytes;
-        c->rebuild_temp_bytes = temp;
-    }
-    if (!u) {   // the pose pt_pose_meshes left staged: nothing copied, its normals used, and it stays readable
-        PT_HIP(hipEventRecord(c->ev0, c->stream));
-        return update_run(c, U, num_triangles, false, true, LightVerts{nullptr, nullptr, nullptr, c->rest_light_verts.data()},
-                          out_kernel_ms, &run);
-    }
-    c->pose_staged = false;
-    const size_t arr = (size_t)num_triangles * 3 * sizeof(float);
-    const float* src[6] = {u->v1, u->v2, u->v3, u->n1, u->n2, u->n3};
-    for (int k = 0; k < (u->n1 ? 6 : 3); k++) PT_HIP(hipMemcpyAsync(U.D.in[k], src[k], arr, hipMemcpyHostToDevice, c->stream));
-    PT_HIP(hipEventRecord(c->ev0, c->stream));
-    return update_run(c, U, num_triangles, derive, u->n1 || derive, LightVerts{u->v1, u->v2, u->v3, nullptr}, out_kernel_ms, &run);
+    RebuildDev sized{};   // pt_rebuild.hip sizes and carves this one: nothing to lay out or upload here
+    if (!Y.rebuild_ws.mem.ptr) PT_HIP(pt::rebuild_workspace_bytes(P, &sized.temp_bytes, &sized.bytes));
+    if (const int rc = ensure_workspace(c, Y.rebuild_ws, "rebuild", [&](void*) { return sized; }, [](const RebuildDev&, Uploader&) {}))
+        return rc;
+    const float* const src[6] = {u ? u->v1 : nullptr, u ? u->v2 : nullptr, u ? u->v3 : nullptr, u ? u->n1 : nullptr,
+                                 u ? u->n2 : nullptr, u ? u->n3 : nullptr};
+    return update_stage_and_run(c, U, u ? src : nullptr, out_kernel_ms);
 }
 
 int pt_tri_bvh_cost(void* ctx, double out[3]) {
@@ -2019,8 +1822,8 @@ int pt_tri_bvh_cost(void* ctx, double out[3]) {
     if (!out) return fail(PT_ERR_INVALID_ARG, "bvh cost: out is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
     out[0] = out[1] = out[2] = 0.0;
-    const int64_t nn = c->refit.num_nodes;
-    if (nn <= 0 || c->refit.src_of_pos.empty()) return PT_OK;
+    const int64_t nn = c->dyn.refit.num_nodes;
+    if (nn <= 0 || c->dyn.refit.src_of_pos.empty()) return PT_OK;
     PT_HIP(hipSetDevice(c->device));
     size_t bytes = 0;
     PT_HIP(pt::bvh_cost_workspace_bytes(nn, &bytes));
@@ -2049,32 +1852,28 @@ int pt_tri_bvh_cost(void* ctx, double out[3]) {
     return PT_OK;
 }
 
+// ---- instanced meshes and moving shapes read back and moved
 int pt_read_blas(void* ctx, int64_t counts[3], int32_t* blas, uint32_t* nodes, uint32_t* recs, uint32_t* shade, float* inner_boxes) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    const pt::BlasRefitTables& T = c->blas_refit;
+    const pt::BlasRefitTables& T = c->dyn.blas_refit;
     const size_t nb = T.num_blas();
     if (counts) { counts[0] = (int64_t)nb; counts[1] = T.num_nodes; counts[2] = T.num_tris; }
     PT_HIP(hipSetDevice(c->device));
     const size_t word = sizeof(uint32_t);
-    if (blas && nb) PT_HIP(hipMemcpyAsync(blas, c->S.blas, nb * sizeof(pt::DevBlas), hipMemcpyDeviceToHost, c->stream));
-    if (nodes && T.num_nodes)
-        PT_HIP(hipMemcpyAsync(nodes, c->S.blas_nodes, (size_t)T.num_nodes * pt::kShapeNodeWords * word, hipMemcpyDeviceToHost, c->stream));
-    if (recs && T.num_tris)
-        PT_HIP(hipMemcpyAsync(recs, c->S.blas_recs, (size_t)T.num_tris * pt::kBlasRecWords * word, hipMemcpyDeviceToHost, c->stream));
-    if (shade && T.num_tris)
-        PT_HIP(hipMemcpyAsync(shade, c->S.blas_shade, (size_t)T.num_tris * pt::kBlasRecWords * word, hipMemcpyDeviceToHost, c->stream));
-    if (inner_boxes && nb) {
-        if (c->blas_boxes_on_device && c->blas_dev.ptr) {
-            const BlasDev D = blas_layout(T, c->blas_num_blocks, c->blas_dev.ptr);
-            PT_HIP(hipMemcpyAsync(inner_boxes, D.blas_box, nb * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        } else {   // no update yet: the upload's, from the host table
-            std::memset(inner_boxes, 0, nb * 6 * sizeof(float));
-            for (size_t t = 0; t < T.xf_blas.size() && 6 * t + 6 <= c->shape_refit.xf_inner_box.size(); t++) {
-                const int64_t b = T.xf_blas[t];
-                if (b >= 0 && (size_t)b < nb) std::memcpy(inner_boxes + 6 * b, &c->shape_refit.xf_inner_box[6 * t], 6 * sizeof(float));
-            }
+    PT_HIP(read_back(c, blas, c->S.blas, nb * sizeof(pt::DevBlas)));
+    PT_HIP(read_back(c, nodes, c->S.blas_nodes, (size_t)T.num_nodes * pt::kShapeNodeWords * word));
+    PT_HIP(read_back(c, recs, c->S.blas_recs, (size_t)T.num_tris * pt::kBlasRecWords * word));
+    PT_HIP(read_back(c, shade, c->S.blas_shade, (size_t)T.num_tris * pt::kBlasRecWords * word));
+    if (c->dyn.blas_boxes_on_device && c->dyn.blas_ws.mem.ptr) {
+        PT_HIP(read_back(c, inner_boxes, c->dyn.blas_ws.at.blas_box, nb * 6 * sizeof(float)));
+    } else if (inner_boxes && nb) {   // no update yet: the upload's, from the host table
+        const std::vector<float>& host = c->dyn.shape_refit.xf_inner_box;
+        std::memset(inner_boxes, 0, nb * 6 * sizeof(float));
+        for (size_t t = 0; t < T.xf_blas.size() && 6 * t + 6 <= host.size(); t++) {
+            const int64_t b = T.xf_blas[t];
+            if (b >= 0 && (size_t)b < nb) std::memcpy(inner_boxes + 6 * b, &host[6 * t], 6 * sizeof(float));
         }
     }
     PT_HIP(hipStreamSynchronize(c->stream));
@@ -2093,7 +1892,7 @@ int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms)
         return fail(PT_ERR_INVALID_ARG, "update shapes: sphere_radius needs sphere_center");
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    pt::ShapeRefitTables& T = c->shape_refit;
+    pt::ShapeRefitTables& T = c->dyn.shape_refit;
     auto count_is = [&](const char* what, int32_t given, int32_t have) -> int {
         if (given == have) return PT_OK;
         return fail(PT_ERR_INVALID_ARG, std::string("update shapes: ") + what + " is " + std::to_string(given) +
@@ -2107,8 +1906,7 @@ int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms)
     if ((!u->sphere_center && !u->cube_min && !u->xform_matrix) || T.num_recs == 0) return PT_OK;
     PT_HIP(hipSetDevice(c->device));
     PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
-    ShapesDev D{};
-    if (const int rc = ensure_shapes_dev(c, D)) return rc;   // before the first change: a failed allocation leaves the scene untouched
+    if (const int rc = ensure_shapes_ws(c)) return rc;   // before the first change: a failed allocation leaves the scene untouched
     // the given groups into the current parameters
     if (u->sphere_center) T.sphere_center.assign(u->sphere_center, u->sphere_center + 3 * (size_t)T.num_spheres);
     if (u->sphere_radius) T.sphere_radius.assign(u->sphere_radius, u->sphere_radius + (size_t)T.num_spheres);
@@ -2120,40 +1918,30 @@ int pt_update_shapes(void* ctx, const pt_shape_update* u, double* out_kernel_ms)
         T.xf_matrix.assign(u->xform_matrix, u->xform_matrix + 16 * (size_t)T.num_transformed);
         T.xf_inverse.assign(u->xform_inverse, u->xform_inverse + 16 * (size_t)T.num_transformed);
     }
-    if (const int rc = stage_shape_params(c, D)) return rc;
+    if (const int rc = stage_shape_params(c)) return rc;
     PT_HIP(hipEventRecord(c->ev0, c->stream));
-    if (const int rc = launch_shapes(c, D)) return rc;
+    if (const int rc = launch_shapes(c)) return rc;
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     // lights that are spheres, cubes or transformed shapes: their sphere from the new parameters
-    if (pt::shape_refit_lights(T, c->h_lights))
-        PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(c->S.lights), c->h_lights.data(), c->h_lights.size() * sizeof(pt::DevLight),
-                              hipMemcpyHostToDevice, c->stream));
+    if (pt::shape_refit_lights(T, c->dyn.h_lights)) if (const int rc = upload_lights(c)) return rc;
     PT_HIP(hipStreamSynchronize(c->stream));
-    if (out_kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *out_kernel_ms = ms;
-    }
-    return PT_OK;
+    return kernel_ms(c, out_kernel_ms);
 }
 
 int pt_read_shape_bvh(void* ctx, int64_t counts[4], uint32_t* nodes, uint32_t* recs, uint32_t* heavy, double* lights) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    const pt::ShapeRefitTables& T = c->shape_refit;
-    const size_t nl = c->h_lights.size();
+    const pt::ShapeRefitTables& T = c->dyn.shape_refit;
+    const size_t nl = c->dyn.h_lights.size();
     if (counts) { counts[0] = T.num_nodes; counts[1] = T.num_recs; counts[2] = T.num_heavy; counts[3] = (int64_t)nl; }
     PT_HIP(hipSetDevice(c->device));
     const size_t word = sizeof(uint32_t);
-    if (nodes && T.num_nodes)
-        PT_HIP(hipMemcpyAsync(nodes, c->S.ana_nodes, (size_t)T.num_nodes * pt::kShapeNodeWords * word, hipMemcpyDeviceToHost, c->stream));
-    if (recs && T.num_recs)
-        PT_HIP(hipMemcpyAsync(recs, c->S.ana_recs, (size_t)T.num_recs * pt::kShapeRecWords * word, hipMemcpyDeviceToHost, c->stream));
-    if (heavy && T.num_heavy)
-        PT_HIP(hipMemcpyAsync(heavy, c->S.heavy, (size_t)T.num_heavy * pt::kShapeHeavyWords * word, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(read_back(c, nodes, c->S.ana_nodes, (size_t)T.num_nodes * pt::kShapeNodeWords * word));
+    PT_HIP(read_back(c, recs, c->S.ana_recs, (size_t)T.num_recs * pt::kShapeRecWords * word));
+    PT_HIP(read_back(c, heavy, c->S.heavy, (size_t)T.num_heavy * pt::kShapeHeavyWords * word));
     std::vector<pt::DevLight> dl(lights ? nl : 0);   // what the device holds, not the host's copy
-    if (!dl.empty()) PT_HIP(hipMemcpyAsync(dl.data(), c->S.lights, nl * sizeof(pt::DevLight), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(read_back(c, dl.data(), c->S.lights, dl.size() * sizeof(pt::DevLight)));
     PT_HIP(hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < dl.size(); i++) {
         for (int k = 0; k < 3; k++) lights[4 * i + k] = (double)dl[i].center[k];

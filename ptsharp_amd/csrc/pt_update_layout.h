@@ -1,0 +1,188 @@
+// pt_update_layout.h — how the moving-geometry entry points (pt_api.hip) carve their per-scene
+// device workspaces: one allocation each, its parts 256-B aligned and in the order listed.  Host code only: no HIP
+// call, compiles with g++ (tests/native/rebuild_check.cpp, blas_check.cpp and shapes_check.cpp check the layouts
+// against what the kernels index).  With a null base the pointers are the parts' offsets.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "pt_rebuild.h"
+#include "pt_scene_compile.h"
+
+namespace pt {
+
+// Parts taken one after another from `base`, each rounded up to 256 B
+struct Carver {
+    uintptr_t base;
+    size_t at = 0;
+    explicit Carver(void* b) : base((uintptr_t)b) {}
+    template <class T>
+    T* take(size_t n) {
+        T* p = (T*)(base + at);
+        at += (n * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+    size_t bytes() const { return at ? at : 256; }   // never an empty allocation
+};
+
+// pt_update_triangles: [v1 v2 v3 n1 n2 n3 staged | src_of_pos | level_nodes | an exact box per node | per chunk]
+struct RefitDev {
+    float* in[6];
+    int32_t* src_of_pos;
+    uint32_t* level_nodes;
+    float* node_box;
+    float* chunk_box;
+    size_t bytes;
+};
+inline RefitDev refit_layout(const RefitTables& T, void* base) {
+    Carver c(base);
+    RefitDev r{};
+    for (float*& a : r.in) a = c.take<float>((size_t)T.num_triangles * 3);
+    r.src_of_pos = c.take<int32_t>(T.src_of_pos.size());
+    // room for the tables pt_rebuild_meshes may put in their place: its balanced tree can have a few more nodes than
+    // the uploaded one (never more chunks), and the layout is made once per scene, from the uploaded tables
+    RebuildPlan R;
+    const bool planned = rebuild_plan((int64_t)T.src_of_pos.size(), R);
+    const size_t nodes = std::max({T.level_nodes.size(), (size_t)T.num_nodes, planned ? (size_t)R.num_nodes : (size_t)0});
+    const size_t chunks = std::max((size_t)T.num_chunks, planned ? (size_t)R.num_chunks : (size_t)0);
+    r.level_nodes = c.take<uint32_t>(nodes);
+    r.node_box = c.take<float>(nodes * 6);
+    r.chunk_box = c.take<float>(chunks * 6);
+    r.bytes = c.bytes();
+    return r;
+}
+
+// PT_NORMALS_SMOOTH: [group | keys a b | corners a b | the sort's temporary]
+struct NormalsDev {
+    int32_t* group;
+    uint32_t* keys[2];
+    uint32_t* vals[2];
+    void* temp;
+    size_t temp_bytes, bytes;
+};
+inline NormalsDev normals_layout(const RefitTables& T, size_t temp_bytes, void* base) {
+    Carver c(base);
+    NormalsDev r{};
+    r.group = c.take<int32_t>((size_t)T.num_triangles);
+    for (uint32_t*& a : r.keys) a = c.take<uint32_t>((size_t)T.num_triangles * 3);
+    for (uint32_t*& a : r.vals) a = c.take<uint32_t>((size_t)T.num_triangles * 3);
+    r.temp = c.take<char>(temp_bytes);
+    r.temp_bytes = temp_bytes;
+    r.bytes = c.bytes();
+    return r;
+}
+
+// pt_update_shapes: [the staged parameters | xbox | rec_box | node_box | level_nodes | the transformed shapes' inner
+// kind, index and box]
+struct ShapesDev {
+    float* sphere_center;
+    double* sphere_radius;
+    float* cube_min;
+    float* cube_max;
+    double* xf_matrix;
+    double* xf_inverse;
+    float* xbox;
+    float* rec_box;
+    float* node_box;
+    uint32_t* level_nodes;
+    int32_t* xf_kind;
+    int32_t* xf_index;
+    float* xf_inner_box;
+    size_t bytes;
+};
+inline ShapesDev shapes_layout(const ShapeRefitTables& T, void* base) {
+    Carver c(base);
+    ShapesDev r{};
+    const size_t ns = (size_t)T.num_spheres, nc = (size_t)T.num_cubes, nx = (size_t)T.num_transformed;
+    r.sphere_center = c.take<float>(ns * 3);
+    r.sphere_radius = c.take<double>(ns);
+    r.cube_min = c.take<float>(nc * 3);
+    r.cube_max = c.take<float>(nc * 3);
+    r.xf_matrix = c.take<double>(nx * 16);
+    r.xf_inverse = c.take<double>(nx * 16);
+    r.xbox = c.take<float>(nx * 6);
+    r.rec_box = c.take<float>((size_t)T.num_recs * 6);
+    r.node_box = c.take<float>((size_t)T.num_nodes * 6);
+    r.level_nodes = c.take<uint32_t>(T.level_nodes.size());
+    r.xf_kind = c.take<int32_t>(nx);
+    r.xf_index = c.take<int32_t>(nx);
+    r.xf_inner_box = c.take<float>(nx * 6);
+    r.bytes = c.bytes();
+    return r;
+}
+
+// k_blas_bounds' blocks: each folds up to `span` positions (pt::blas_bounds_span()) of one BLAS
+struct BlasBlocks {
+    std::vector<int32_t> blas, first, off;   // per block its BLAS and first position; per BLAS its first block (and the end)
+};
+inline void blas_blocks(const BlasRefitTables& T, int64_t span, BlasBlocks& B) {
+    for (size_t b = 0; b < T.num_blas(); b++) {
+        B.off.push_back((int32_t)B.blas.size());
+        const int64_t r0 = T.desc[4 * b + 2], n = T.desc[4 * b + 3];
+        for (int64_t at = 0; at < n; at += span) {
+            B.blas.push_back((int32_t)b);
+            B.first.push_back((int32_t)(r0 + at));
+        }
+    }
+    B.off.push_back((int32_t)B.blas.size());
+}
+// pt_update_meshes on instanced meshes: [the tables | tri_box | node_box | block_part | blas_box]
+struct BlasDev {
+    int32_t* desc;
+    int32_t* src_of_pos;
+    uint32_t* level_nodes;
+    int32_t* level_blas;
+    int32_t* block_blas;
+    int32_t* block_first;
+    int32_t* blas_block_off;
+    int32_t* xf_blas;
+    float* tri_box;
+    float* node_box;
+    float* block_part;
+    float* blas_box;
+    size_t num_blocks, bytes;
+};
+inline BlasDev blas_layout(const BlasRefitTables& T, size_t num_blocks, void* base) {
+    Carver c(base);
+    BlasDev r{};
+    const size_t nb = T.num_blas();
+    r.desc = c.take<int32_t>(T.desc.size());
+    r.src_of_pos = c.take<int32_t>(T.src_of_pos.size());
+    r.level_nodes = c.take<uint32_t>(T.level_nodes.size());
+    r.level_blas = c.take<int32_t>(T.level_blas.size());
+    r.block_blas = c.take<int32_t>(num_blocks);
+    r.block_first = c.take<int32_t>(num_blocks);
+    r.blas_block_off = c.take<int32_t>(nb + 1);
+    r.xf_blas = c.take<int32_t>(T.xf_blas.size());
+    r.tri_box = c.take<float>((size_t)T.num_tris * 6);
+    r.node_box = c.take<float>((size_t)T.num_nodes * 6);
+    r.block_part = c.take<float>(num_blocks * 6);
+    r.blas_box = c.take<float>(nb * 6);
+    r.num_blocks = num_blocks;
+    r.bytes = c.bytes();
+    return r;
+}
+
+// pt_pose_meshes: [rest v1 v2 v3 n1 n2 n3 | group | matrices | mask]
+struct PoseDev {
+    float* rest[6];
+    int32_t* group;
+    double* matrices;
+    int32_t* mask;
+    size_t bytes;
+};
+inline PoseDev pose_layout(const RefitTables& T, void* base) {
+    Carver c(base);
+    PoseDev r{};
+    for (float*& a : r.rest) a = c.take<float>((size_t)T.num_triangles * 3);
+    r.group = c.take<int32_t>((size_t)T.num_triangles);
+    r.matrices = c.take<double>((size_t)T.num_groups * 16);
+    r.mask = c.take<int32_t>((size_t)T.num_groups);
+    r.bytes = c.bytes();
+    return r;
+}
+
+}  // namespace pt

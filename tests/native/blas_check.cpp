@@ -13,6 +13,9 @@
 //                 padded world boxes, heavy boxes and transforms equal it bit for bit, the lights as values;
 //   sequence      pose A then pose B gives the words of pose B alone;
 //   tables        the level table lists every BLAS node once, parents on lower levels than their children;
+//   layout        the BLAS workspace (pt_update_layout.h) of each scene: the bounds kernel's blocks cover every position
+//                 once and never span two BLASes; parts 256-B aligned, disjoint, in the documented order, inside
+//                 `bytes` and as large as what the kernels index;
 //   non-finite    NaN and infinite vertices run through the refit (under ASan: no access leaves its array).
 // `--dump DIR` writes the sine pose of the `two` scene with given normals, inputs and outputs, as raw arrays into DIR
 // (tests/blas_refit_ref.py is checked against them).
@@ -28,6 +31,8 @@
 #include "../../ptsharp_amd/csrc/pt_bvh.h"
 #include "../../ptsharp_amd/csrc/pt_scene_compile.h"
 #include "../../ptsharp_amd/csrc/pt_shape_refit.h"
+#include "../../ptsharp_amd/csrc/pt_update_layout.h"
+#include "layout_parts.h"
 #include "scene_fixture.h"
 
 static int failures = 0;
@@ -310,6 +315,35 @@ static size_t check_levels(const Twin& W) {
         }
     return B.level_off.size() - 1;
 }
+// The BLAS workspace (pt_update_layout.h) from a null base, for k_blas_bounds blocks of `span` positions (the kernels'
+// is 2048, pt_blas_refit.hip kBlasSpan; a small one gives the fixtures' meshes several blocks): every position of every
+// BLAS in exactly one block of its own BLAS, and every part as large as what the kernels index
+// nb, nn, nt, nx: the BLASes, their nodes and triangle positions as the compiled arrays count them, and the scene's
+// transformed shapes
+static void check_layout(const pt::BlasRefitTables& T, size_t nb, size_t nn, size_t nt, size_t nx, int64_t span) {
+    pt::BlasBlocks B;
+    pt::blas_blocks(T, span, B);
+    CHECK(T.num_blas() == nb && (size_t)T.num_nodes == nn && (size_t)T.num_tris == nt);
+    size_t blocks = 0;
+    CHECK(B.off.size() == nb + 1 && B.blas.size() == B.first.size());
+    for (size_t b = 0; b < nb; b++) {
+        const int64_t r0 = T.desc[4 * b + 2], n = T.desc[4 * b + 3];
+        CHECK((size_t)B.off[b] == blocks);
+        for (int64_t at = 0; at < n; at += span, blocks++) {
+            if (blocks >= B.blas.size()) break;
+            CHECK(B.blas[blocks] == (int32_t)b && B.first[blocks] == r0 + at);
+        }
+    }
+    CHECK(blocks == B.blas.size() && (size_t)B.off[nb] == blocks);
+    const pt::BlasDev D = pt::blas_layout(T, blocks, nullptr);
+    const size_t i4 = sizeof(int32_t), box = 6 * sizeof(float);
+    CHECK(D.num_blocks == blocks);
+    CHECK(layout_violations({{D.desc, nb * 4 * i4}, {D.src_of_pos, nt * i4}, {D.level_nodes, nn * i4},
+                             {D.level_blas, nn * i4}, {D.block_blas, blocks * i4}, {D.block_first, blocks * i4},
+                             {D.blas_block_off, (nb + 1) * i4}, {D.xf_blas, nx * i4}, {D.tri_box, nt * box},
+                             {D.node_box, nn * box}, {D.block_part, blocks * box}, {D.blas_box, nb * box}},
+                            D.bytes) == 0);
+}
 static void check_identity(const char* name, void (*build)(FixScene&)) {
     FixScene s;
     build(s);
@@ -319,6 +353,8 @@ static void check_identity(const char* name, void (*build)(FixScene&)) {
     CHECK(rc == PT_OK);
     if (rc != PT_OK) { std::fprintf(stderr, "%s: %s\n", name, err.c_str()); return; }
     const int before = failures;
+    for (const int64_t span : {2048, 100, 1})   // float4 rows: 8 per BLAS node, kBlasRecWords / 4 per triangle position
+        check_layout(H.blas_refit, H.blas.size(), H.blas_nodes.size() / 8, H.blas_recs.size() / (pt::kBlasRecWords / 4), s.xf.size(), span);
     for (const bool normals : {false, true}) {
         Twin W;
         twin_of(H, W);

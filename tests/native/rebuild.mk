@@ -7,7 +7,7 @@ OUT := _build
 CSRC := ../../ptsharp_amd/csrc
 ROCM ?= /opt/rocm
 HIPINC := -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Wno-unknown-pragmas -Wno-attributes
-DEPS := rebuild_check.cpp scene_fixture.h $(CSRC)/pt_rebuild.h $(CSRC)/pt_refit.h $(CSRC)/pt_scene_compile.cpp $(CSRC)/pt_scene_compile.h \
+DEPS := rebuild_check.cpp scene_fixture.h layout_parts.h $(CSRC)/pt_update_layout.h $(CSRC)/pt_rebuild.h $(CSRC)/pt_refit.h $(CSRC)/pt_scene_compile.cpp $(CSRC)/pt_scene_compile.h \
         $(CSRC)/pt_scene.h $(CSRC)/pt_ext.h $(CSRC)/pt_math.h $(CSRC)/pt_bvh.cpp $(CSRC)/pt_bvh.h ../../include/ptsharp_hip.h rebuild.mk
 SRC := rebuild_check.cpp $(CSRC)/pt_scene_compile.cpp $(CSRC)/pt_bvh.cpp
 FLAGS := -std=c++17 -O2 -ffp-contract=off -fno-fast-math -pthread -Wall $(HIPINC)

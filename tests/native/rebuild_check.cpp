@@ -14,23 +14,33 @@
 //                triangle; the emissive loose triangle's light equals the fresh compile's;
 //   fixed point  a rebuild applied twice to the same arrays leaves src_of_pos (and every word) as the first left them;
 //   cost         on the 6,400-triangle sphere, Σ area(slot box) / area(root box): after the offset pose
-//                cost(rebuilt) <= cost(refit) / 3, after the twist cost(rebuilt) <= 0.8 cost(refit).
+//                cost(rebuilt) <= cost(refit) / 3, after the twist cost(rebuilt) <= 0.8 cost(refit);
+//   layouts      for every P in 1..6400 (the sanitized build: 1..400, every 61st P after that and the sizes above; a
+//                compile each), the refit and pose workspaces (pt_update_layout.h) laid out from the compiled scene's
+//                tables: parts 256-B aligned, disjoint, in the documented order and inside `bytes`; level_nodes,
+//                node_box and chunk_box hold the uploaded tree and rebuild_plan(P)'s; a layout from the tables a
+//                rebuild leaves is never larger.
 // `--dump DIR P POSE` writes that case's inputs and outputs as raw arrays (tests/rebuild_ref.py is checked against them).
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../ptsharp_amd/csrc/pt_bvh.h"
 #include "../../ptsharp_amd/csrc/pt_rebuild.h"
 #include "../../ptsharp_amd/csrc/pt_refit.h"
 #include "../../ptsharp_amd/csrc/pt_scene_compile.h"
+#include "../../ptsharp_amd/csrc/pt_update_layout.h"
+#include "layout_parts.h"
 #include "scene_fixture.h"
 
-static int failures = 0;
+static std::atomic<int> failures{0};   // the layout sweep counts from several threads
+constexpr size_t kSweepThreads = 8;
 #define CHECK(c)                                                                  \
     do {                                                                          \
         if (!(c)) {                                                               \
@@ -436,6 +446,47 @@ static void check_cost() {
     }
 }
 
+// ---- the refit and pose workspaces of a P-triangle scene as pt_api.hip lays them out once per scene, from the
+// uploaded tables: the refit's scratch parts hold the uploaded tree and the balanced one a rebuild puts in its place
+static void check_layouts(int P) {
+    FixScene s;
+    sphere_scene(s, P);
+    pt::HostScene H;
+    if (compile(s, H) != PT_OK) { failures++; return; }
+    const pt::RefitTables& T = H.refit;
+    pt::RebuildPlan R;
+    CHECK(pt::rebuild_plan(P, R));
+    const size_t nt = s.tm.size(), up_nodes = (size_t)T.num_nodes, up_chunks = (size_t)T.num_chunks;
+    CHECK((size_t)T.num_triangles == nt && T.src_of_pos.size() == (size_t)P && T.level_nodes.size() == up_nodes);
+    const size_t nodes = std::max(up_nodes, (size_t)R.num_nodes), chunks = std::max(up_chunks, (size_t)R.num_chunks);
+    const pt::RefitDev D = pt::refit_layout(T, nullptr);
+    std::vector<LayoutPart> parts;
+    for (const float* a : D.in) parts.push_back({a, nt * 3 * sizeof(float)});
+    parts.push_back({D.src_of_pos, (size_t)P * sizeof(int32_t)});
+    parts.push_back({D.level_nodes, nodes * sizeof(uint32_t)});
+    parts.push_back({D.node_box, nodes * 6 * sizeof(float)});
+    parts.push_back({D.chunk_box, chunks * 6 * sizeof(float)});
+    CHECK(layout_violations(parts, D.bytes) == 0);
+    // the tables overwritten as pt_rebuild_meshes leaves them: a layout from these is never larger, part by part
+    pt::RefitTables T1 = T;
+    T1.num_nodes = R.num_nodes;
+    T1.num_chunks = R.num_chunks;
+    T1.level_nodes.resize((size_t)R.num_nodes);
+    T1.level_off.assign(R.level_off, R.level_off + R.h + 1);
+    const pt::RefitDev D1 = pt::refit_layout(T1, nullptr);
+    CHECK(D1.bytes <= D.bytes && D1.level_nodes == D.level_nodes && D1.node_box <= D.node_box && D1.chunk_box <= D.chunk_box);
+
+    const size_t ng = (size_t)T.num_groups;
+    const pt::PoseDev Q = pt::pose_layout(T, nullptr);
+    parts.clear();
+    for (const float* a : Q.rest) parts.push_back({a, nt * 3 * sizeof(float)});
+    parts.push_back({Q.group, nt * sizeof(int32_t)});
+    parts.push_back({Q.matrices, ng * 16 * sizeof(double)});
+    parts.push_back({Q.mask, ng * sizeof(int32_t)});
+    CHECK(layout_violations(parts, Q.bytes) == 0);
+    pt::tri_bvh_release(H.tri_build);   // the sweep keeps no build cached
+}
+
 template <class T>
 static void dump(const std::string& dir, const char* name, const T* p, size_t n) {
     const std::string path = dir + "/" + name;
@@ -488,6 +539,24 @@ int main(int argc, char** argv) {
     for (int P : {1, 2, 3, 4, 24, 25, 192, 193, 1537, 6400})
         for (int pose = 0; pose < POSE_COUNT; pose++) check_case(P, pose);
     check_cost();
-    std::printf("rebuild_check: %d failures\n", failures);
+    {   // every P up to the largest case, a compile each, on a few threads (the compile is made for that: contexts
+        // upload at once).  Under the sanitizers all 6,400 take minutes: that build keeps every P up to 400, every
+        // 61st after that and the cases above.
+#if defined(__SANITIZE_ADDRESS__)
+        const bool all = false;
+#else
+        const bool all = true;
+#endif
+        const int before = failures;
+        std::vector<int> sweep;
+        for (int P = 1; P <= 6400; P++)
+            if (all || P <= 400 || P % 61 == 0 || P == 1537 || P == 6400) sweep.push_back(P);
+        std::vector<std::thread> pool;
+        for (size_t t = 0; t < kSweepThreads; t++)
+            pool.emplace_back([&sweep, t] { for (size_t i = t; i < sweep.size(); i += kSweepThreads) check_layouts(sweep[i]); });
+        for (std::thread& th : pool) th.join();
+        std::printf("layouts %zu of P 1..6400 %s\n", sweep.size(), failures == before ? "ok" : "FAILED");
+    }
+    std::printf("rebuild_check: %d failures\n", failures.load());
     return failures ? 1 : 0;
 }

@@ -23,6 +23,8 @@
 #include "../../ptsharp_amd/csrc/pt_bvh.h"
 #include "../../ptsharp_amd/csrc/pt_scene_compile.h"
 #include "../../ptsharp_amd/csrc/pt_shape_refit.h"
+#include "../../ptsharp_amd/csrc/pt_update_layout.h"
+#include "layout_parts.h"
 #include "scene_fixture.h"
 
 static int failures = 0;
@@ -300,6 +302,17 @@ static void check_identity(const char* name, void (*build)(FixScene&)) {
             if (ref != pt::kEmpty4 && !(ref & 0x80000000u)) CHECK(level[ref] == level[(size_t)n] + 1);
         }
     }
+    // the shape workspace (pt_update_layout.h) from a null base: parts 256-B aligned, disjoint, in the documented order,
+    // inside `bytes`, each as large as what the refit indexes, counted from the scene and the compiled arrays
+    const size_t ns = s.sr.size(), nc = s.cm.size(), nx = s.xf.size(), nn = W.nodes.size() / 32, nr = W.rec_box.size() / 6;
+    const size_t f4 = sizeof(float), f8 = sizeof(double), i4 = sizeof(int32_t);
+    const pt::ShapesDev D = pt::shapes_layout(H.shape_refit, nullptr);
+    CHECK((size_t)H.shape_refit.num_nodes == nn && (size_t)H.shape_refit.num_recs == nr);
+    CHECK(layout_violations({{D.sphere_center, ns * 3 * f4}, {D.sphere_radius, ns * f8}, {D.cube_min, nc * 3 * f4}, {D.cube_max, nc * 3 * f4},
+                             {D.xf_matrix, nx * 16 * f8}, {D.xf_inverse, nx * 16 * f8}, {D.xbox, nx * 6 * f4}, {D.rec_box, nr * 6 * f4},
+                             {D.node_box, nn * 6 * f4}, {D.level_nodes, nn * i4}, {D.xf_kind, nx * i4}, {D.xf_index, nx * i4},
+                             {D.xf_inner_box, nx * 6 * f4}},
+                            D.bytes) == 0);
     std::printf("identity %s nodes %lld recs %lld heavy %lld levels %zu lights %zu: %s\n", name, (long long)W.T.num_nodes,
                 (long long)W.T.num_recs, (long long)W.T.num_heavy, W.T.level_off.size() - 1, W.lights.size(),
                 failures == before ? "ok" : "FAILED");

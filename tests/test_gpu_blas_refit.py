@@ -595,6 +595,31 @@ def test_update_upload_update(gpu):
         r.close()
 
 
+def test_every_entry_point_then_an_upload_of_another_size(gpu):
+    """One context through the entry points that move an instanced scene (so the shape, BLAS, refit and pose workspaces
+    exist and their kept layouts were used), then an upload of a scene with other counts on the same context: an
+    update of that scene leaves the device bit for bit as it leaves a fresh context."""
+    from ptsharp_amd import scenes
+    st, st2, st3 = scenes.instances(copies=2, mesh_tris=200), scenes.instances(copies=3, mesh_tris=120), scenes.instances(copies=3, mesh_tris=120)
+    r, fresh = renderer(st), renderer(st3)
+    try:
+        flat = st[0].Compile()
+        v, kw = pose("grow", flat)
+        r.UpdateMeshes(*v, **kw)
+        r.UpdateShapes(**spun(flat))
+        r.SetRestPose()
+        r.PoseMeshes([Matrix.TranslateM(Vector(0.5, -0.25, 1)).Mul(Matrix.RotateM(Vector(1, 2, 3), 1.1))], mirror=False)
+        r.Scene = st2[0]   # uploaded by the next call
+        v2, kw2 = pose("twist_smooth", st3[0].Compile())
+        r.UpdateMeshes(*v2, **kw2)
+        fresh.UpdateMeshes(*v2, **kw2)
+        assert len(r.ReadBlas()[0]) == 1
+        same_state(state(r), state(fresh), "after the second upload", boxes_as_values=False)
+    finally:
+        r.close()
+        fresh.close()
+
+
 # ------------------------------------------------------------------ 8. errors and the refusal
 def test_errors_leave_the_scene_untouched(gpu):
     st = scene_t()

@@ -299,6 +299,37 @@ def test_rebuild_from_the_staged_pose(gpu):
         r2.close()
 
 
+@pytest.mark.parametrize("first,second", [(1537, 193), (193, 1537)])
+def test_every_entry_point_then_an_upload_of_another_size(gpu, first, second):
+    """One context through every moving-triangle entry point (so every per-scene workspace exists and its kept layout
+    was used), then an upload of a scene of another size on the same context: a rebuild and an update of that scene
+    leave the device bit for bit as they leave a fresh context.  At 1537 triangles the balanced tree and the uploaded
+    one differ in node count."""
+    arrs, arrs2 = sphere_arrays(first), sphere_arrays(second)
+    a, b = pose("offset", arrs2), pose("sine", arrs2)
+    r, fresh = renderer(make_scene(arrs)), renderer(make_scene(arrs2))
+    try:
+        r.UpdateTriangles(*pose("sine", arrs)[:3], normals="smooth")
+        m = Matrix.TranslateM(Vector(0.5, -0.25, 1)).Mul(Matrix.RotateM(Vector(1, 2, 3), 1.1)).Mul(Matrix.ScaleM(Vector(1.5, 0.5, 1)))
+        r.SetRestPose()
+        r.PoseMeshes([m], mirror=False)
+        assert r.RebuildMeshes() > 0
+        r.UpdateTriangles(*pose("twist", arrs)[:3])
+        r.ReadTriNormals()
+        r.Scene = make_scene(arrs2)[0]   # uploaded by the next call
+        for q in (r, fresh):
+            q.RebuildMeshes(*a)
+            q.UpdateTriangles(*b[:3])
+        same_bvh(r.ReadTriBvh(), fresh.ReadTriBvh(), f"{first} then {second}")
+        assert len(r.ReadTriBvh()[2]) == second
+        for got, want, what in zip(r.ReadTriNormals(), fresh.ReadTriNormals(), ("n1", "n2", "n3")):
+            normals_ref.same_bits(got, want, what)
+        assert r.TriBvhCost() == fresh.TriBvhCost()
+    finally:
+        r.close()
+        fresh.close()
+
+
 def test_smooth_normals_after_a_rebuild(gpu):
     P = 1537
     arrs = sphere_arrays(P)

@@ -35,6 +35,8 @@ def test_rebuild_check(built):
     for p in SIZES:
         for pose in POSES:
             assert ["P", str(p), "pose", pose, "ok"] in lines, out
+    # the refit and pose workspaces' layouts: every P from 1 to 6400, SIZES among them
+    assert "layouts 6400 of P 1..6400 ok".split() in lines, out
     # the cost gates on the 6,400-triangle sphere: the program asserts them; the figures are printed
     cost = {m.group(1): (float(m.group(2)), float(m.group(3)))
             for m in re.finditer(r"cost (\w+) +refit ([\d.]+) rebuilt ([\d.]+)", out)}
@@ -49,6 +51,9 @@ def test_rebuild_check_sanitized():
     r = subprocess.run([EXE_ASAN], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert r.stdout.strip().endswith("rebuild_check: 0 failures")
+    # this build samples the layout sweep (every P up to 400, every 61st after that, 1537 and 6400): all 6400
+    # compiles take minutes under the sanitizers; test_rebuild_check sweeps every P
+    assert "layouts 500 of P 1..6400 ok" in r.stdout, r.stdout[-2000:]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 
