@@ -204,6 +204,24 @@ namespace PTSharpCore
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_hit_arrays
+        {
+            // every pointer may be IntPtr.Zero: that output is not wanted
+            public fixed int reserved[2];  // 0
+            public IntPtr t;               // [n] double: Hit.T, 1e9 on a miss
+            public IntPtr kind;            // [n] int: the pt_shape_kind hit, or -1
+            public IntPtr index;           // [n] int: index into that kind's arrays; the source triangle for a triangle
+            public IntPtr prim;            // [n] int: the source triangle whose surface was hit, or -1
+            public IntPtr shape;           // [n] int: the slot in Scene.Shapes order
+            public IntPtr position;        // [n][3] float: Hit.Info's Position
+            public IntPtr normal;          // [n][3] float: Hit.Info's Normal after the flip
+            public IntPtr inside;          // [n] int: Hit.Info's Inside
+            public IntPtr material;        // [n] int: the material id
+            public IntPtr albedo;          // [n][3] double: the MaterialAt colour; on a miss the environment
+            public IntPtr gloss;           // [n] double: the MaterialAt gloss
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         public unsafe struct pt_mesh_pose
         {
             public int num_meshes;         // must equal the uploaded scene's num_meshes
@@ -259,6 +277,9 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_tri_bvh_cost(IntPtr ctx, double[] out3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
+        // what a host's rays hit and where: identity in the host's numbering and Hit.Info (DESIGN.md §4h)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect_hits(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, ref pt_hit_arrays arrays);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_query_kernel_ms(IntPtr ctx, out double ms);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr pt_last_error();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void pt_destroy(IntPtr ctx);
         // multi-GPU (include/ptsharp_hip.h "Multi-GPU"): one process per GPU (unique id + init per rank) or
@@ -851,6 +872,52 @@ namespace PTSharpCore
         {
             PtHip.Check(PtHip.pt_rebuild_meshes(ctx, IntPtr.Zero, out double ms), "pt_rebuild_meshes");
             return ms;
+        }
+
+        /// <summary>The hits of n rays with their identity and Hit.Info (pt_intersect_hits).</summary>
+        public sealed class Hits
+        {
+            public double[] T, Albedo, Gloss;
+            public int[] Kind, Index, Prim, Shape, Inside, Material;
+            public float[] Position, Normal;
+        }
+
+        /// <summary>Scene.Intersect of n rays ([n][3] origins and directions) with what was hit and where: the kind,
+        /// the index in the scene's own arrays, the source triangle, the Scene.Shapes slot and, with info, Hit.Info's
+        /// position, normal, side, material and MaterialAt colour and gloss (without it the kernel skips Hit.Info and
+        /// those arrays stay null).</summary>
+        public Hits IntersectHits(float[] origins, float[] dirs, bool info = true, int flags = 0)
+        {
+            if (!uploaded) Upload();
+            int n = origins.Length / 3;
+            var h = new Hits { T = new double[n], Kind = new int[n], Index = new int[n], Prim = new int[n], Shape = new int[n] };
+            if (info)
+            {
+                h.Position = new float[3 * n]; h.Normal = new float[3 * n]; h.Inside = new int[n]; h.Material = new int[n];
+                h.Albedo = new double[3 * n]; h.Gloss = new double[n];
+            }
+            var pins = new List<GCHandle>();
+            IntPtr Pin(Array a)
+            {
+                if (a == null) return IntPtr.Zero;
+                pins.Add(GCHandle.Alloc(a, GCHandleType.Pinned));
+                return pins[pins.Count - 1].AddrOfPinnedObject();
+            }
+            try
+            {
+                var a = new PtHip.pt_hit_arrays
+                {
+                    t = Pin(h.T), kind = Pin(h.Kind), index = Pin(h.Index), prim = Pin(h.Prim), shape = Pin(h.Shape),
+                    position = Pin(h.Position), normal = Pin(h.Normal), inside = Pin(h.Inside), material = Pin(h.Material),
+                    albedo = Pin(h.Albedo), gloss = Pin(h.Gloss),
+                };
+                PtHip.Check(PtHip.pt_intersect_hits(ctx, n, origins, dirs, flags, ref a), "pt_intersect_hits");
+            }
+            finally
+            {
+                foreach (var p in pins) p.Free();
+            }
+            return h;
         }
 
         /// <summary>The surface-area cost of the world triangle BVH as it stands (pt_tri_bvh_cost): inner cost and leaf

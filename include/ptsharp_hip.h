@@ -50,6 +50,9 @@
  *   pt_write_tiles     display of a rank's tiles, host-side gathers
  *   pt_intersect /     Scene.Intersect of a host's rays; the shadow query   Scene.cs:75-79, Sampler.cs:261-265
  *   pt_occluded
+ *   pt_intersect_hits  Scene.Intersect of a host's rays with the Hit and its   Hit.cs:6-55, Scene.cs:75-79
+ *                      Hit.Info: which shape, which triangle, where, the
+ *                      normal, the side, the material and its colour
  *   pt_stats           Scene.rays (Interlocked counter, never printed)     Scene.cs:70-79
  *                      + the "time elapsed" stopwatch                      Renderer.cs:212-213,470
  *   pt_last_error      oidnGetDeviceError(device, out msg)                 OIDN.cs:85-86
@@ -536,6 +539,51 @@ int pt_intersect(void* ctx, int64_t n, const float* origins, const float* dirs, 
                  int32_t* out_kind);
 int pt_occluded(void* ctx, int64_t n, const float* origins, const float* dirs, const double* t_max, int32_t flags,
                 int32_t* out_blocked);
+
+/* Ray queries that say what was hit and where: pt_intersect's query with the identity of the hit in the
+ * host's own numbering and, when wanted, Hit.Info (Hit.cs:26-55) there.  Rays and flags as for pt_intersect; n in
+ * [0, 2^30].  Every pointer of pt_hit_arrays may be NULL: that output is not wanted.  Asking for none of position ..
+ * gloss runs a kernel that does not evaluate Hit.Info: pt_intersect's trace plus a few table lookups per ray.
+ * A miss: t = 1e9; kind, index, prim, shape and material -1; position and normal (0,0,0); inside and gloss 0; albedo
+ * the environment (sampleEnvironment(direction), as pt_render_features writes it).
+ * shape: for an analytic shape or a plane the slot whose (shape_kind, shape_index) names it; for a triangle of the world
+ * BVH the slot of the PT_SHAPE_TRIANGLE that names it, else of the mesh it belongs to (the last mesh_first / mesh_count
+ * range that contains it, as for PT_NORMALS_SMOOTH and pt_pose_meshes; should that mesh be in no slot, the first slot of
+ * a mesh that contains it); a hit through an instance reports the PT_SHAPE_TRANSFORMED slot.  Where several slots name
+ * one shape, the first.
+ * index, prim and shape name the scene as uploaded and stay what they were after pt_update_*, pt_pose_meshes and
+ * pt_rebuild_meshes (the source numbering never changes); t, position and normal follow the moved geometry.  Where two
+ * primitives are hit at exactly the same t, the one reported is the traversal's: any of them.
+ * Rays and answers are staged in chunks of at most 2^22 rays (the environment's PT_QUERY_CHUNK, read at each call and
+ * clamped to [64, 2^22], lowers it; the answers do not depend on it).  Runs on the context's stream after every pass
+ * issued before it and synchronises before returning; changes neither the Buffer, the pass state, the counters nor the
+ * feature buffers.  The identity tables (a few bytes per triangle and shape) are uploaded by the scene's first query and
+ * kept until the next upload.
+ * Errors (nothing launched, no output written): a NULL ctx or out, NULL origins or dirs with n > 0, reserved != 0, n
+ * out of range, bad flags: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; the staging or the tables not allocated:
+ * PT_ERR_OUT_OF_MEMORY.  n = 0, or every pointer NULL: PT_OK, nothing launched.
+ * pt_query_kernel_ms: the device time of the last pt_intersect_hits' kernels on the context (hipEvents around each
+ * chunk's launch, summed); 0 when that call launched nothing. */
+typedef struct pt_hit_arrays {      /* every pointer may be NULL: that output is not wanted */
+    int32_t reserved[2];            /* 0 */
+    double*  t;         /* [n]     Hit.T; 1e9 (Hit.INF) on a miss: pt_intersect's, bit for bit */
+    int32_t* kind;      /* [n]     pt_shape_kind as pt_intersect reports it, or -1 */
+    int32_t* index;     /* [n]     index into that kind's pt_scene_desc arrays: sphere, cube, plane, sdf_shapes, volumes,
+                                   transformed; for PT_SHAPE_TRIANGLE the source triangle (tri_v1 row); -1 on a miss */
+    int32_t* prim;      /* [n]     the source triangle whose surface was hit: == index for PT_SHAPE_TRIANGLE, the mesh's
+                                   triangle for a pt_transformed_shape over PT_SHAPE_MESH, else -1 */
+    int32_t* shape;     /* [n]     slot in Scene.Shapes order (pt_scene_desc.shape_kind / shape_index) of the top-level
+                                   shape hit; -1 on a miss */
+    float*   position;  /* [n][3]  Hit.Info's Position (ray.Position(T)) */
+    float*   normal;    /* [n][3]  Hit.Info's Normal after the flip, normal and bump maps applied */
+    int32_t* inside;    /* [n]     Hit.Info's Inside */
+    int32_t* material;  /* [n]     material id, as pt_read_features' PT_FEATURE_MATERIAL_I32 */
+    double*  albedo;    /* [n][3]  Material.MaterialAt colour; on a miss sampleEnvironment(direction) */
+    double*  gloss;     /* [n]     MaterialAt gloss (gloss texture applied) */
+} pt_hit_arrays;
+int pt_intersect_hits(void* ctx, int64_t n, const float* origins, const float* dirs, int32_t flags,
+                      const pt_hit_arrays* out);
+int pt_query_kernel_ms(void* ctx, double* out_ms);
 
 /* The triangle BVH is built once per process for identical geometry: N contexts that upload the same
  * scene (one process driving N GPUs) share one host build (Scene.Compile once, Scene.cs:48-68) and upload

@@ -152,6 +152,17 @@ class pt_mesh_pose(C.Structure):
                 ("matrices", _d), ("mesh_mask", _i)]
 
 
+# pt_hit_arrays' outputs in the header's order: name -> (numpy dtype, components per ray)
+HIT_ARRAYS = {"t": ("f8", 1), "kind": ("i4", 1), "index": ("i4", 1), "prim": ("i4", 1), "shape": ("i4", 1),
+              "position": ("f4", 3), "normal": ("f4", 3), "inside": ("i4", 1), "material": ("i4", 1),
+              "albedo": ("f8", 3), "gloss": ("f8", 1)}
+
+
+class pt_hit_arrays(C.Structure):
+    _fields_ = [("reserved", C.c_int32 * 2), ("t", _d), ("kind", _i), ("index", _i), ("prim", _i), ("shape", _i),
+                ("position", _f), ("normal", _f), ("inside", _i), ("material", _i), ("albedo", _d), ("gloss", _d)]
+
+
 class pt_trace_counters(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
                 ("shading_fetches", C.c_uint64), ("shadow_rays", C.c_uint64), ("shadow_nodes", C.c_uint64),
@@ -220,6 +231,8 @@ SIGNATURES = {
     "pt_scene_bvh_digest": (C.c_int, [C.POINTER(pt_scene_desc), C.POINTER(C.c_uint64)]),
     "pt_intersect": (C.c_int, [C.c_void_p, C.c_int64, _f, _f, C.c_int32, _d, _i]),
     "pt_occluded": (C.c_int, [C.c_void_p, C.c_int64, _f, _f, _d, C.c_int32, _i]),
+    "pt_intersect_hits": (C.c_int, [C.c_void_p, C.c_int64, _f, _f, C.c_int32, C.POINTER(pt_hit_arrays)]),
+    "pt_query_kernel_ms": (C.c_int, [C.c_void_p, _d]),
     "pt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(pt_mesh_data)]),
     "pt_mesh_free": (None, [C.POINTER(pt_mesh_data)]),
     "pt_obj_last_error": (C.c_char_p, []),

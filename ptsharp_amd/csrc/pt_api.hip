@@ -28,6 +28,7 @@
 #include "pt_device.h"
 #include "pt_math.h"
 #include "pt_pass_plan.h"
+#include "pt_query.h"
 #include "pt_rebuild.h"
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
@@ -212,6 +213,7 @@ struct SceneDyn {
     pt::RefitTables refit;
     pt::ShapeRefitTables shape_refit;
     pt::BlasRefitTables blas_refit;
+    pt::QueryTables query;                // the slot tables pt_intersect_hits uploads at its first call
     std::vector<pt::DevLight> h_lights;   // the uploaded lights; the ones that follow geometry are moved by the updates
     bool has_blas = false;                // an instanced mesh: pt_update_triangles and pt_rebuild_meshes refuse
     Workspace<pt::RefitDev> refit_ws;       // first update, or pt_read_tri_normals
@@ -220,6 +222,8 @@ struct SceneDyn {
     Workspace<pt::BlasDev> blas_ws;         // first pt_update_meshes on instanced meshes
     Workspace<pt::PoseDev> pose_ws;         // pt_set_rest_pose
     Workspace<RebuildDev> rebuild_ws;       // first pt_rebuild_meshes
+    Workspace<pt::QueryDev> query_ws;       // first pt_intersect_hits: its own copies of the identity tables
+    bool query_src_stale = false;           // a pt_rebuild_meshes permuted refit.src_of_pos after query_ws took its copy
     // pt_set_rest_pose: the rest vertices of the lights that are loose triangles, 9 floats per h_lights entry
     std::vector<float> rest_light_verts;
     bool pose_staged = false;            // refit_ws' staged arrays hold the last pt_pose_meshes' (pt_read_pose)
@@ -231,6 +235,7 @@ struct SceneDyn {
         blas_ws.release();
         pose_ws.release();
         rebuild_ws.release();
+        query_ws.release();
     }
 };
 
@@ -252,6 +257,7 @@ struct Ctx {
     int denoise_pair = -1;                      // the pair that holds the last pt_denoise's or pt_denoise_guided's result (-1: none yet)
     void* d_features = nullptr;                 // first-hit features and their guide records (pt_features.hip; first use)
     bool have_features = false;                 // pt_render_features or pt_write_features filled d_features
+    double query_kernel_ms = 0;                 // the last pt_intersect_hits' kernels (pt_query_kernel_ms)
     int32_t* d_tiles = nullptr;
     int32_t tiles_cap = 0;
     std::vector<int32_t> h_tiles;               // the tile list in d_tiles (uploaded when it changes)
@@ -680,6 +686,7 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     c->dyn.refit = std::move(H.refit);
     c->dyn.shape_refit = std::move(H.shape_refit);
     c->dyn.blas_refit = std::move(H.blas_refit);
+    c->dyn.query = std::move(H.query);
     c->dyn.h_lights = std::move(H.lights);
     c->dyn.has_blas = !H.blas.empty();
     c->stats.bvh_nodes = H.bvh_nodes;
@@ -1579,8 +1586,10 @@ int update_run(Ctx* c, const UpdateCall& U, double* out_kernel_ms) {
     // the root box follows (pt_wavefront.hip's refill kernels skip the triangle phase of a ray that misses it)
     uint32_t root[pt::kNode8Words];
     if (T.num_chunks > 0) PT_HIP(hipMemcpyAsync(root, nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
-    if (U.rebuild)
+    if (U.rebuild) {
         PT_HIP(hipMemcpyAsync(T.src_of_pos.data(), D.src_of_pos, T.src_of_pos.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        Y.query_src_stale = true;   // pt_intersect_hits' copy follows at its next call
+    }
     // lights that are loose emissive triangles: their sphere from the new vertices
     bool lights_moved = false;
     for (size_t i = 0; i < Y.h_lights.size() && i < T.light_tri.size(); i++) {
@@ -1947,6 +1956,138 @@ int pt_read_shape_bvh(void* ctx, int64_t counts[4], uint32_t* nodes, uint32_t* r
         for (int k = 0; k < 3; k++) lights[4 * i + k] = (double)dl[i].center[k];
         lights[4 * i + 3] = dl[i].radius;
     }
+    return PT_OK;
+}
+
+}  // extern "C"
+
+// ---- pt_intersect_hits
+namespace {
+// The identity tables on the device: uploaded by the scene's first query, gone with the scene.  The query keeps its own
+// copy of position -> source triangle (the refit workspace's exists only after an update), and takes
+// RefitTables::src_of_pos again after a pt_rebuild_meshes permuted it.
+int ensure_query_ws(Ctx* c) {
+    SceneDyn& Y = c->dyn;
+    bool first = false;
+    if (const int rc = ensure_workspace(c, Y.query_ws, "query", [&](void* base) { return pt::query_layout(Y.refit, Y.blas_refit, Y.query, base); },
+                                        [&](const pt::QueryDev& D, Uploader& up) {
+                                            up(D.tri_src, Y.refit.src_of_pos);
+                                            up(D.blas_src, Y.blas_refit.src_of_pos);
+                                            up(D.tri_slot, Y.query.tri_slot);
+                                            up(D.ana_slot, Y.query.ana_slot);
+                                            up(D.plane_slot, Y.query.plane_slot);
+                                        },
+                                        &first))
+        return rc;
+    if (!first && Y.query_src_stale) {
+        Uploader up{c->stream};
+        up(Y.query_ws.at.tri_src, Y.refit.src_of_pos);
+        if (const int rc = check_hip(up.err, "query: the rebuilt triangle order")) return rc;
+    }
+    Y.query_src_stale = false;
+    return PT_OK;
+}
+
+// PT_QUERY_CHUNK, read at each call (tests set it): rays staged at a time
+int64_t query_chunk() {
+    const char* e = std::getenv("PT_QUERY_CHUNK");
+    if (!e || !*e) return pt::kQueryChunkMax;
+    return std::min(std::max((int64_t)std::atoll(e), pt::kQueryChunkMin), pt::kQueryChunkMax);
+}
+
+// One output of pt_hit_arrays: the host's array (NULL: not wanted), its staged chunk on the device, bytes per ray
+struct QueryPart {
+    void* host;
+    void** dev;
+    size_t stride;
+};
+}  // namespace
+
+extern "C" {
+
+int pt_intersect_hits(void* ctx, int64_t n, const float* origins, const float* dirs, int32_t flags, const pt_hit_arrays* out) {
+    Ctx* c = (Ctx*)ctx;
+    const std::string who = "pt_intersect_hits";
+    if (!c || !out) return fail(PT_ERR_INVALID_ARG, who + ": ctx or out is NULL");
+    if (out->reserved[0] != 0 || out->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, who + ": reserved must be 0");
+    if (n < 0 || n > (int64_t)1 << 30) return fail(PT_ERR_INVALID_ARG, who + ": n out of range [0, 2^30]");
+    if (n > 0 && (!origins || !dirs)) return fail(PT_ERR_INVALID_ARG, who + ": origins or dirs is NULL");
+    if (flags & ~(PT_MARCH_LANE | PT_MARCH_WAVE) || (flags & PT_MARCH_LANE && flags & PT_MARCH_WAVE))
+        return fail(PT_ERR_INVALID_ARG, who + ": flags: PT_MARCH_LANE or PT_MARCH_WAVE, not both");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    pt::QueryOut O{};
+    const QueryPart parts[] = {
+        {out->t, (void**)&O.t, sizeof(double)},           {out->kind, (void**)&O.kind, sizeof(int32_t)},
+        {out->index, (void**)&O.index, sizeof(int32_t)},  {out->prim, (void**)&O.prim, sizeof(int32_t)},
+        {out->shape, (void**)&O.shape, sizeof(int32_t)},  {out->position, (void**)&O.position, 3 * sizeof(float)},
+        {out->normal, (void**)&O.normal, 3 * sizeof(float)}, {out->inside, (void**)&O.inside, sizeof(int32_t)},
+        {out->material, (void**)&O.material, sizeof(int32_t)}, {out->albedo, (void**)&O.albedo, 3 * sizeof(double)},
+        {out->gloss, (void**)&O.gloss, sizeof(double)}};
+    bool wanted = false;
+    for (const QueryPart& p : parts) wanted = wanted || p.host;
+    c->query_kernel_ms = 0.0;
+    if (n == 0 || !wanted) return PT_OK;
+    PT_HIP(hipSetDevice(c->device));
+    if (const int rc = ensure_query_ws(c)) return rc;
+    // the staging of one chunk: [origins | dirs | every wanted output], parts 256-B aligned
+    const int64_t chunk = std::min(query_chunk(), n);
+    float *d_o = nullptr, *d_d = nullptr;
+    auto carve = [&](void* base) {
+        pt::Carver cv(base);
+        d_o = cv.take<float>((size_t)chunk * 3);
+        d_d = cv.take<float>((size_t)chunk * 3);
+        for (const QueryPart& p : parts) if (p.host) *p.dev = cv.take<char>((size_t)chunk * p.stride);
+        return cv.bytes();
+    };
+    void* staging = nullptr;
+    if (hipMalloc(&staging, carve(nullptr)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, who + ": staging allocation");
+    }
+    carve(staging);
+    const SceneDyn& Y = c->dyn;
+    const pt::QueryDev& D = Y.query_ws.at;
+    pt::QueryDevTables T{};
+    T.tri_src = D.tri_src; T.tri_src_n = (int64_t)Y.refit.src_of_pos.size();
+    T.blas_src = D.blas_src; T.blas_src_n = (int64_t)Y.blas_refit.src_of_pos.size();
+    T.tri_slot = D.tri_slot; T.tri_slot_n = (int64_t)Y.query.tri_slot.size();
+    T.ana_slot = D.ana_slot; T.ana_slot_n = (int64_t)Y.query.ana_slot.size();
+    T.plane_slot = D.plane_slot; T.plane_slot_n = (int64_t)Y.query.plane_slot.size();
+    std::memcpy(T.ana_off, Y.query.ana_off, sizeof T.ana_off);
+    std::memcpy(T.ana_cnt, Y.query.ana_cnt, sizeof T.ana_cnt);
+    T.num_blas = (int32_t)Y.blas_refit.num_blas();
+    pt::DevScene S = c->S;
+    S.march = nullptr;
+    if (flags & PT_MARCH_LANE) S.coop_min_lanes = 65;   // as pt_intersect sets them
+    if (flags & PT_MARCH_WAVE) S.coop_min_lanes = 1;
+    int rc = PT_OK;
+    auto step = [&](hipError_t err, const char* what) {
+        if (rc == PT_OK && err != hipSuccess) rc = fail(PT_ERR_HIP, who + ": " + what + ": " + hipGetErrorString(err));
+    };
+    for (int64_t at = 0; at < n && rc == PT_OK; at += chunk) {
+        const size_t m = (size_t)std::min(chunk, n - at);
+        step(hipMemcpyAsync(d_o, origins + 3 * at, m * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream), "origins");
+        step(hipMemcpyAsync(d_d, dirs + 3 * at, m * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream), "dirs");
+        step(hipEventRecord(c->ev0, c->stream), "hipEventRecord");
+        if (rc == PT_OK) step(pt::launch_intersect_hits(S, T, (int64_t)m, d_o, d_d, O, c->stream), "k_intersect_hits");
+        step(hipEventRecord(c->ev1, c->stream), "hipEventRecord");
+        for (const QueryPart& p : parts)
+            if (p.host && rc == PT_OK)
+                step(hipMemcpyAsync((char*)p.host + (size_t)at * p.stride, *p.dev, m * p.stride, hipMemcpyDeviceToHost, c->stream), "answers");
+        step(hipStreamSynchronize(c->stream), "hipStreamSynchronize");   // the next chunk reuses the staging
+        float ms = 0.f;
+        if (rc == PT_OK) step(hipEventElapsedTime(&ms, c->ev0, c->ev1), "hipEventElapsedTime");
+        c->query_kernel_ms += ms;
+    }
+    if (rc != PT_OK) (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(staging);
+    return rc;
+}
+
+int pt_query_kernel_ms(void* ctx, double* out_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out_ms) return fail(PT_ERR_INVALID_ARG, "NULL argument");
+    *out_ms = c->query_kernel_ms;
     return PT_OK;
 }
 

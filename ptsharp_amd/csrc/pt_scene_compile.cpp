@@ -885,6 +885,7 @@ int Compiler::run() {
     lights();
     if ((rc = lines())) return rc;
     flags();
+    query_tables(d, H.refit.tri_group, H.query);
     return PT_OK;
 }
 
@@ -1024,6 +1025,46 @@ void refit_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t
     level_nodes.resize((size_t)num_nodes);
     std::vector<uint32_t> at(level_off.begin(), level_off.end() - 1);
     for (int64_t i = 0; i < num_nodes; i++) level_nodes[at[depth[(size_t)i]]++] = (uint32_t)i;
+}
+
+// The slot tables of pt_intersect_hits (pt_scene_compile.h QueryTables): one pass over Scene.Shapes for the first slot
+// of every shape, then the triangles from the loose slots and the meshes' slots
+void query_tables(const pt_scene_desc* d, const std::vector<int32_t>& tri_group, QueryTables& Q) {
+    const int32_t counts[8] = {d->num_spheres, d->num_cubes, 0, 0, 0, d->num_sdf_shapes, d->num_volumes, d->num_transformed};
+    int32_t at = 0;
+    for (int k = 0; k < 8; k++) {
+        Q.ana_off[k] = at;
+        Q.ana_cnt[k] = std::max(counts[k], 0);
+        at += Q.ana_cnt[k];
+    }
+    Q.ana_slot.assign((size_t)at, -1);
+    Q.plane_slot.assign((size_t)std::max(d->num_planes, 0), -1);
+    const size_t nt = (size_t)std::max(d->num_triangles, 0), nm = (size_t)std::max(d->num_meshes, 0);
+    std::vector<int32_t> loose_slot(nt, -1), mesh_slot(nm, -1);
+    for (int i = 0; i < d->num_shapes; i++) {
+        const int k = d->shape_kind[i], j = d->shape_index[i];
+        int32_t* first = nullptr;
+        if (j < 0 || k < 0 || k > 7) continue;
+        if (k == PT_SHAPE_PLANE) { if ((size_t)j < Q.plane_slot.size()) first = &Q.plane_slot[(size_t)j]; }
+        else if (k == PT_SHAPE_TRIANGLE) { if ((size_t)j < nt) first = &loose_slot[(size_t)j]; }
+        else if (k == PT_SHAPE_MESH) { if ((size_t)j < nm) first = &mesh_slot[(size_t)j]; }
+        else if (j < Q.ana_cnt[k]) first = &Q.ana_slot[(size_t)(Q.ana_off[k] + j)];
+        if (first && *first < 0) *first = i;
+    }
+    Q.tri_slot = loose_slot;
+    std::vector<size_t> slotted;   // the meshes that are top-level shapes
+    for (size_t m = 0; m < nm; m++) if (mesh_slot[m] >= 0) slotted.push_back(m);
+    for (size_t t = 0; t < nt; t++) {
+        if (Q.tri_slot[t] >= 0) continue;
+        const int64_t g = t < tri_group.size() ? tri_group[t] : -1;
+        if (g >= 0 && (size_t)g < nm && mesh_slot[(size_t)g] >= 0) { Q.tri_slot[t] = mesh_slot[(size_t)g]; continue; }
+        int32_t best = -1;   // the mesh tri_group names is in no slot: the first slot of a mesh that holds the triangle
+        for (const size_t m : slotted) {
+            const int64_t f = d->mesh_first[m], n = d->mesh_count[m];
+            if ((int64_t)t >= f && (int64_t)t < f + n && (best < 0 || mesh_slot[m] < best)) best = mesh_slot[m];
+        }
+        Q.tri_slot[t] = best;
+    }
 }
 
 std::vector<int32_t> gather_tri_src(const pt_scene_desc* d) {

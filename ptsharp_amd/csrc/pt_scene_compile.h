@@ -106,6 +106,22 @@ struct BlasRefitTables {
 // breadth-first walk from each BLAS's node 0.
 void blas_levels(const uint32_t* nodes, BlasRefitTables& T);
 
+// What pt_intersect_hits needs beside the device arrays to say which Scene.Shapes slot a hit belongs to (DESIGN.md
+// §4h): -1 for a shape in no slot; where several slots name one shape, the first.
+struct QueryTables {
+    // per source triangle (pt_scene_desc order): the first PT_SHAPE_TRIANGLE slot that names it; else the first slot
+    // of the mesh tri_group assigns it to; else the first PT_SHAPE_MESH slot whose range holds it
+    std::vector<int32_t> tri_slot;
+    // per analytic shape, the kinds one after another in pt_shape_kind order: entry ana_off[k] + j is shape j of kind k
+    // (ana_cnt[k] of them; planes, triangles and meshes have none here)
+    std::vector<int32_t> ana_slot;
+    int32_t ana_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ana_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<int32_t> plane_slot;   // per plane (pt_scene_desc order)
+};
+// tri_group: RefitTables::tri_group of the same scene.  Indices out of range are skipped (the compile validated the
+// shapes it uses; this reads nothing else).
+void query_tables(const pt_scene_desc* d, const std::vector<int32_t>& tri_group, QueryTables& Q);
+
 // A compiled scene on the host: every array pt_upload_scene uploads, and the DevScene with every
 // non-pointer field filled.
 struct HostScene {
@@ -136,6 +152,7 @@ struct HostScene {
     RefitTables refit;
     ShapeRefitTables shape_refit;
     BlasRefitTables blas_refit;
+    QueryTables query;
 };
 
 // Validates and compiles.  PT_OK, or an error code with its message in err (H is then partly filled; its

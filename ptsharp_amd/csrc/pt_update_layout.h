@@ -185,4 +185,25 @@ inline PoseDev pose_layout(const RefitTables& T, void* base) {
     return r;
 }
 
+// pt_intersect_hits' identity tables (pt_query.h): [tri_src | blas_src | tri_slot | ana_slot | plane_slot]
+struct QueryDev {
+    int32_t* tri_src;
+    int32_t* blas_src;
+    int32_t* tri_slot;
+    int32_t* ana_slot;
+    int32_t* plane_slot;
+    size_t bytes;
+};
+inline QueryDev query_layout(const RefitTables& T, const BlasRefitTables& B, const QueryTables& Q, void* base) {
+    Carver c(base);
+    QueryDev r{};
+    r.tri_src = c.take<int32_t>(T.src_of_pos.size());
+    r.blas_src = c.take<int32_t>(B.src_of_pos.size());
+    r.tri_slot = c.take<int32_t>(Q.tri_slot.size());
+    r.ana_slot = c.take<int32_t>(Q.ana_slot.size());
+    r.plane_slot = c.take<int32_t>(Q.plane_slot.size());
+    r.bytes = c.bytes();
+    return r;
+}
+
 }  // namespace pt

@@ -387,6 +387,36 @@ class Renderer:
                    "pt_intersect")
         return t, k
 
+    def IntersectHits(self, origins, dirs, flags: int = 0, want=None) -> dict:
+        """Scene.Intersect of n rays with what was hit and where (pt_intersect_hits): a dict of numpy arrays by the
+        names of pt_hit_arrays (_abi.HIT_ARRAYS: t, kind, index, prim, shape, position, normal, inside, material,
+        albedo, gloss), [n] or [n, 3].  want: the names to compute (default: all); asking for none of position ..
+        gloss runs the kernel without Hit.Info.  flags as for Intersect."""
+        self._ensure_scene()
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        assert o.shape == d.shape
+        names = list(_abi.HIT_ARRAYS) if want is None else [k for k in _abi.HIT_ARRAYS if k in set(want)]
+        unknown = set(want or ()) - set(_abi.HIT_ARRAYS)
+        if unknown:
+            raise ValueError(f"IntersectHits: unknown outputs {sorted(unknown)}")
+        out = {}
+        arrays = _abi.pt_hit_arrays()
+        for name in names:
+            dtype, comps = _abi.HIT_ARRAYS[name]
+            out[name] = np.zeros((len(o), comps) if comps > 1 else len(o), dtype)
+            setattr(arrays, name, out[name].ctypes.data_as(dict(_abi.pt_hit_arrays._fields_)[name]))
+        _abi.check(self._lib.pt_intersect_hits(self._ctx, len(o), o.ctypes.data_as(C.POINTER(C.c_float)),
+                                               d.ctypes.data_as(C.POINTER(C.c_float)), int(flags), C.byref(arrays)),
+                   "pt_intersect_hits")
+        return out
+
+    def QueryKernelMs(self) -> float:
+        """The device time of the last IntersectHits' kernels in ms (pt_query_kernel_ms)."""
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_query_kernel_ms(self._ctx, C.byref(ms)), "pt_query_kernel_ms")
+        return float(ms.value)
+
     def Occluded(self, origins, dirs, t_max, flags: int = 0) -> np.ndarray:
         """The shadow query after the light's own t (pt_occluded): [n] int32, 1 where a shape is hit
         strictly nearer than t_max."""
