@@ -766,7 +766,7 @@ static int upload_tile_list(Ctx* c, const pt_pass_params* pass, int image_tiles,
 // The wavefront engine's queues and buffers for this plan, and the plan as its launches take it.
 static int prepare_wavefront(Ctx* c, const pt_pass_params* pass, const pt::PassPlan& plan, const pt::PassKnobs& knobs,
                              pt::WfPlan& wf) {
-    if (!c->grids.trace_blocks) PT_HIP(pt::wavefront_grids(c->grids));
+    if (!c->grids.complete()) PT_HIP(pt::wavefront_grids(c->grids));
     if (int rc = ensure_wavefront(c, plan.cap, plan.scap, plan.passes_per_launch, plan.use_side)) return rc;
     if (pass->adaptive_samples > 0 || pass->firefly_samples > 0)
         if (int rc = ensure_extra(c, plan.chunk_extra)) return rc;

@@ -145,4 +145,54 @@ PassPlan plan_pass(const PassPlanInput& in) {
     return plan;
 }
 
+WfChoice choose_kernels(const WfChoiceInput& in) {
+    const PassKnobs& k = in.knobs;
+    const bool full = in.full != 0;        // shade: textures or row-4 shapes
+    const bool fullg = in.full_geom != 0;  // traversal: row-4 shapes only
+    // Per-lane refill traversal (k_wf_trace_lanes, k_wf_shadow_lanes) where rays are long
+    // enough to pay for it: lean scenes with a triangle BVH of more than kLanesMinNodes nodes.
+    const bool lanes = !fullg && (k.lanes >= 0 ? k.lanes == 1 : in.tri_num_nodes > kLanesMinNodes);
+    const bool ldsl = PT_SHADOW_LDS && in.num_lights <= kLdsLights;   // the lean shadow kernels' lights in LDS
+    // a few analytic records and planes, no triangles: k_wf_trace_linear / k_wf_shadow_linear
+    const bool linear = PT_LINEAR && k.linear != 0 && !fullg && !lanes && in.ana_linear && in.tri_num_nodes <= 0 && in.num_sdf <= 0 &&
+                        in.num_vol <= 0 && in.ana_count <= kLinRecs && in.num_planes <= kLinPlanes;
+    // Split traversal (row-4 scenes with a triangle BVH, or with a Volume: PT_SPLIT_VOL): the lean refill kernels take
+    // the planes and the triangles at their occupancy, then the FULL lockstep kernels add the analytic BVH (where
+    // the §8f row-4 shapes live) from that result.  Shadow rays split only when every light's own t is a lean
+    // intersect (spheres, cubes, planes); otherwise the unsplit FULL shadow kernel.
+    const bool split = k.lanes < 0 && fullg && (in.tri_num_nodes > kLanesMinNodes || (PT_SPLIT_VOL && in.num_vol > 0));
+    const bool split_sh = split && in.lights_lean;
+    // Head pass and list-fed refill kernels (k_wf_trace_head / k_wf_shadow_head, then the <.., LIST> forms): where
+    // the unsplit refill kernels run and their step loop is triangles only.  Every other scene keeps its kernels.
+    const bool head = k.head != 0 && lanes && !split && (in.ana_linear || in.ana_num_nodes <= 0);
+    auto family = [&](bool split_here) {
+        return split_here ? WF_SPLIT : head ? WF_HEAD : fullg ? WF_FULL : lanes ? WF_LANES : linear ? WF_LINEAR : WF_LOCKSTEP;
+    };
+    auto queue = [](bool run, int32_t lds) { return !run ? WF_Q_NONE : lds > 0 ? WF_Q_STAGED : WF_Q_PLAIN; };
+    static constexpr WfGrid kTraceGrid[][2] = {{G_TRACE, G_TRACE}, {G_FULL_TRACE, G_FULL_TRACE}, {G_LANES_TRACE, G_LANES_TRACE},
+                                               {G_HEAD_TRACE, G_LIST_TRACE}, {G_LINEAR_TRACE, G_LINEAR_TRACE}, {G_LANES_TRACE, G_FULL_TRACE}};
+    static constexpr WfGrid kShadowGrid[][2] = {{G_SHADOW, G_SHADOW}, {G_FULL_SHADOW, G_FULL_SHADOW}, {G_LANES_SHADOW, G_LANES_SHADOW},
+                                                {G_HEAD_SHADOW, G_LIST_SHADOW}, {G_LINEAR_SHADOW, G_LINEAR_SHADOW}, {G_LANES_SHADOW, G_FULL_SHADOW}};
+    WfChoice c;
+    c.trace = family(split);
+    c.shadow = family(split_sh);
+    for (int i = 0; i < 2; i++) {
+        c.trace_grid[i] = kTraceGrid[c.trace][i];
+        c.shadow_grid[i] = kShadowGrid[c.shadow][i];
+    }
+    // a counted pass takes no EARLY or LDSL form (none is instantiated); EARLY (a test switch) beats LDSL; the
+    // refill kernels have the EARLY forms, the unsplit lean kernels and the head kernel the LDSL forms
+    c.early = !in.counted && k.tail_early && (c.shadow == WF_SPLIT || c.shadow == WF_HEAD || c.shadow == WF_LANES);
+    c.ldsl = !in.counted && ldsl && !c.early && (c.shadow == WF_LANES || c.shadow == WF_LINEAR || c.shadow == WF_LOCKSTEP);
+    c.head_ldsl = !in.counted && ldsl && c.shadow == WF_HEAD;
+    c.shade = full && in.shade_route ? WF_SHADE_ROUTED : full ? WF_SHADE_FULL : WF_SHADE_LEAN;
+    c.shade_miss = c.shade == WF_SHADE_ROUTED && PT_SHADE_MISS && in.env_tex >= 0;
+    // the deferred Volume and SDF records of a split step, staged in LDS when they fit (DevScene::vol_lds / sdf_lds)
+    c.vol_hits = queue(split && in.volq && in.num_vol > 0, in.vol_lds);
+    c.sdf_hits = queue(split && in.num_sdf > 0, in.sdf_lds);
+    c.vol_shadow = queue(split_sh && in.volq_sh && in.num_vol > 0, in.vol_lds);
+    c.sdf_shadow = queue(split_sh && in.num_sdf > 0, in.sdf_lds);
+    return c;
+}
+
 }  // namespace pt

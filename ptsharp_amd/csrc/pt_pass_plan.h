@@ -1,5 +1,6 @@
 // pt_pass_plan.h — how a render pass runs, decided on the host before anything is allocated or launched
-// (pt_pass_plan.cpp): engine, chunk sizes, queue capacities, batch split, side stream.  Plain arithmetic over
+// (pt_pass_plan.cpp): engine, chunk sizes, queue capacities, batch split, side stream (plan_pass), and which kernels
+// every depth of a wavefront pass launches (choose_kernels).  Plain arithmetic over
 // plain values: no HIP header, no HIP call, no environment (pt_api.hip reads the switches into PassKnobs and
 // the device's memory into wf_max_cap / batch_passes_max), so tests/native/pass_plan_check.cpp drives it on
 // the CPU.  The deal functions below are shared with the device code (pt_wavefront.h includes this header).
@@ -121,5 +122,66 @@ PassPlan check_pass_params(const PassPlanInput& in);
 
 // Never fails otherwise than by a refusal in the result; every input is allowed.
 PassPlan plan_pass(const PassPlanInput& in);
+
+// ---- Which kernels every depth of a wavefront pass launches (choose_kernels; DESIGN.md §4 has the rules as a table).
+// The limits and build switches the choice shares with the kernels of pt_wavefront.hip:
+#ifndef PT_SHADE_MISS
+#define PT_SHADE_MISS 1   // routed shade: a textured environment's misses in k_wf_shade_miss (0: in the FULL shade)
+#endif
+#ifndef PT_LINEAR
+#define PT_LINEAR 1        // k_wf_trace_linear / k_wf_shadow_linear for a few analytic records and no triangles
+#endif
+#ifndef PT_SHADOW_LDS
+#define PT_SHADOW_LDS 1    // the lean shadow kernels read a small scene's lights and their records from LDS (stage_lights)
+#endif
+// Scenes with a Volume take the split traversal whatever their triangle count, for the Volume queue kernels
+// (k_wf_vol_*: full waves, the Volume in LDS): the Volume-only scene 495 -> 528 Mrays/s
+#ifndef PT_SPLIT_VOL
+#define PT_SPLIT_VOL 1
+#endif
+// The refill kernels run on scenes whose triangle BVH has more than this many nodes (gopher3's five
+// analytic shapes: trace 16.0 → 23.5 ms with refill).
+constexpr int kLanesMinNodes = 64;
+// The linear kernels' records and planes in LDS, at most (stage_linear); k_wf_shade stages as many (stage_shading).
+constexpr int kLinRecs = 8, kLinPlanes = 8;
+constexpr int kLdsLights = 16;   // lights in LDS, at most (stage_shading, stage_lights: the LDSL shadow kernels)
+
+// The persistent grids of WfGrids (pt_wavefront.h), in the order of wavefront_grids' table.
+enum WfGrid : int32_t {
+    G_TRACE, G_SHADE, G_SHADOW, G_LANES_TRACE, G_LANES_SHADOW, G_FULL_TRACE, G_FULL_SHADOW, G_LINEAR_TRACE, G_LINEAR_SHADOW,
+    G_HEAD_TRACE, G_HEAD_SHADOW, G_LIST_TRACE, G_LIST_SHADOW, kWfGridCount
+};
+// A traversal step's kernels.  Lockstep: k_wf_trace / k_wf_shadow<.., false>.  Full: their FULL forms (row-4 shapes).
+// Lanes: the per-lane refill kernels.  Head: k_wf_*_head, then the list-fed refill kernels.  Linear: k_wf_*_linear.
+// Split: the lean refill kernels (<.., SPLIT>), then the FULL lockstep kernels' analytic half, then the queue kernels.
+enum WfFamily : int32_t { WF_LOCKSTEP, WF_FULL, WF_LANES, WF_HEAD, WF_LINEAR, WF_SPLIT };
+// Lean / full: the direct and the SCAN form of k_wf_shade<COUNT, FULL>.  Routed: the lean SCAN and the FULL SCAN form.
+enum WfShade : int32_t { WF_SHADE_LEAN, WF_SHADE_FULL, WF_SHADE_ROUTED };
+enum WfQueueKernel : int32_t { WF_Q_NONE, WF_Q_PLAIN, WF_Q_STAGED };   // staged: its records in dynamic LDS
+
+struct WfChoiceInput {
+    // of the uploaded scene (DevScene's members of these names)
+    int32_t full = 0, full_geom = 0, tri_num_nodes = 0, ana_num_nodes = 0, ana_count = 0, ana_linear = 0, num_planes = 0;
+    int32_t num_sdf = 0, num_vol = 0, num_lights = 0, lights_lean = 0, shade_route = 0, env_tex = -1, sdf_lds = 0, vol_lds = 0;
+    bool volq = false, volq_sh = false;   // WfQueues::volq / volq_sh are allocated (they outlive a scene without Volumes)
+    PassKnobs knobs;                      // lanes, head, linear, tail_early
+    bool counted = false;
+};
+
+struct WfChoice {
+    WfFamily trace = WF_LOCKSTEP, shadow = WF_LOCKSTEP;
+    // the shadow family's traversal kernel (its list-fed one under WF_HEAD): the EARLY and LDSL forms, never both and
+    // never counted; head_ldsl: k_wf_shadow_head's LDSL form
+    bool early = false, ldsl = false, head_ldsl = false;
+    WfShade shade = WF_SHADE_LEAN;
+    bool shade_miss = false;              // k_wf_shade_miss after a routed shade
+    WfQueueKernel vol_hits = WF_Q_NONE, sdf_hits = WF_Q_NONE;       // after a split closest hit, in this order
+    WfQueueKernel vol_shadow = WF_Q_NONE, sdf_shadow = WF_Q_NONE;   // after split shadow rays
+    // what caps each launch's grid: [0] the step's first kernel, [1] its second (WF_HEAD: the list-fed kernel,
+    // WF_SPLIT: the FULL half; otherwise as [0]).  The linear kernels launch exactly their member's blocks.
+    WfGrid trace_grid[2] = {G_TRACE, G_TRACE}, shadow_grid[2] = {G_SHADOW, G_SHADOW};
+};
+
+WfChoice choose_kernels(const WfChoiceInput& in);
 
 }  // namespace pt

@@ -117,24 +117,17 @@ constexpr uint32_t kWfMaxThreads = kWfMaxBlocks * 256;
 
 // Persistent grids: the resident capacity of each kernel on this device (wavefront_grids, once per context).
 struct WfGrids {
-    uint32_t trace_blocks;     // lockstep traversal,
-    uint32_t shade_blocks;     // shade, lockstep shadow; the refill and FULL traversal kernels below
-    uint32_t shadow_blocks;
-    uint32_t lanes_trace_blocks, lanes_shadow_blocks, full_trace_blocks, full_shadow_blocks;
-    uint32_t linear_trace_blocks, linear_shadow_blocks;   // k_wf_trace_linear / k_wf_shadow_linear
-    uint32_t head_trace_blocks, head_shadow_blocks;       // k_wf_trace_head / k_wf_shadow_head
-    uint32_t list_trace_blocks, list_shadow_blocks;       // the list-fed forms of the refill kernels
+    uint32_t blocks[kWfGridCount];   // by WfGrid (pt_pass_plan.h; wavefront_grids' table names each one's kernel)
     // a zero grid: a kernel whose occupancy query was never made
     bool complete() const {
-        return trace_blocks && shade_blocks && shadow_blocks && lanes_trace_blocks && lanes_shadow_blocks && full_trace_blocks &&
-               full_shadow_blocks && linear_trace_blocks && linear_shadow_blocks && head_trace_blocks && head_shadow_blocks &&
-               list_trace_blocks && list_shadow_blocks;
+        for (uint32_t b : blocks) if (!b) return false;
+        return true;
     }
 };
 
 // One pass on the wavefront engine, as its launches take it: the context's grids, the host's plan (chunk,
 // chunk_extra, the children per sample) and the switches that choose kernels (shade_form, lanes, head, head_stats,
-// linear), all by value (pt_pass_plan.h), and the side stream's handles.
+// linear: choose_kernels), all by value (pt_pass_plan.h), and the side stream's handles.
 struct WfPlan : WfGrids, PassPlan, PassKnobs {
     // Optional second stream (PassPlan::use_side): each depth's shadow pass runs there, beside the next depth's
     // closest-hit pass (independent queues), so one fills the other's ramp and tail.

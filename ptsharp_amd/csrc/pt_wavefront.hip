@@ -128,17 +128,8 @@ constexpr uint32_t kDead = 0xFFFFFFFFu;  // queue slot reserved for a child that
 constexpr int kBlockMajorFH = 16;
 constexpr int kBlockMajorChildren = 32;
 constexpr int32_t kDeadKind = -2;         // hit-record kind of a dead camera slot (k_wf_trace)
-#ifndef PT_SHADE_MISS
-#define PT_SHADE_MISS 1   // routed shade: a textured environment's misses in k_wf_shade_miss (0: in the FULL shade)
-#endif
 #ifndef PT_SHADE_LDS
 #define PT_SHADE_LDS 1     // k_wf_shade reads a small scene's materials and lights from LDS (stage_shading)
-#endif
-#ifndef PT_LINEAR
-#define PT_LINEAR 1        // k_wf_trace_linear / k_wf_shadow_linear for a few analytic records and no triangles
-#endif
-#ifndef PT_SHADOW_LDS
-#define PT_SHADOW_LDS 1    // the lean shadow kernels read a small scene's lights and their records from LDS (stage_lights)
 #endif
 #ifndef PT_SHADE_SCAN
 #define PT_SHADE_SCAN 8    // rows of 256 per SCAN claim: 16 best before claims carried their partial round, 8 since
@@ -399,9 +390,8 @@ __global__ __launch_bounds__(kTB, FULL ? PT_FULL_TRACE_WAVES : PT_TRACE_WAVES) v
 // results), and each wave loads its next row of 64 entries before it tests the current one.  Static deal:
 // wave w of the partition's group takes rows w, w + W, ... (every ray costs the same tests).
 struct LinRay { float4 b, a; };   // the queue entry: q_d / n_n and q_o / n_o
-// The records and planes in LDS (at most kLinRecs / kLinPlanes: the launch checks), read by every ray's tests:
-// from global memory the compiler issued them as vector loads per ray (it cannot prove them unwritten).
-constexpr int kLinRecs = 8, kLinPlanes = 8;
+// The records and planes in LDS (at most kLinRecs / kLinPlanes, pt_pass_plan.h: the launch checks), read by every
+// ray's tests: from global memory the compiler issued them as vector loads per ray (it cannot prove them unwritten).
 struct LinScene { const float4* recs; const float4* planes; };
 __device__ __forceinline__ LinScene stage_linear(const DevScene& S) {   // block-uniform call
     __shared__ float4 s_rec[3 * kLinRecs];
@@ -682,9 +672,6 @@ __device__ __forceinline__ bool tri_reach(const DevScene& S, v3 o, v3 invd, floa
 #define PT_LIST_SHADOW_CLAIM 128
 #endif
 constexpr uint32_t kListClaim = PT_LIST_CLAIM, kListShClaim = PT_LIST_SHADOW_CLAIM;
-// The refill kernels run on scenes whose triangle BVH has more than this many nodes (gopher3's five
-// analytic shapes: trace 16.0 → 23.5 ms with refill).
-constexpr int kLanesMinNodes = 64;
 
 // Closest hit with per-lane refill over lean scenes (no §8f row-4 shapes; the refill half of a split
 // closest hit).  See k_wf_trace for the lockstep form.  Each lane keeps one ray in flight through ONE
@@ -1254,7 +1241,7 @@ __device__ __forceinline__ void shade_children(const DevScene& S, const DevSampl
 // triangle record), its light (after the light draw) and that light's material are dependent loads of the
 // shading chain; from LDS each costs an LDS round trip instead of an L1 / L2 one.  Returns the scene view
 // that reads them there (flat loads).  Block-uniform call.
-constexpr int kLdsMats = 32, kLdsLights = 16;
+constexpr int kLdsMats = 32;   // (kLdsLights: pt_pass_plan.h)
 static_assert(sizeof(DevMaterial) % 8 == 0 && sizeof(DevLight) % 8 == 0, "stage_shading copies 8-B words");
 __device__ __forceinline__ DevScene stage_shading(const DevScene& S0) {
     __shared__ unsigned long long s_mats[kLdsMats * sizeof(DevMaterial) / 8];
@@ -2241,36 +2228,29 @@ static unsigned grid_for(uint64_t items, unsigned block, unsigned cap_blocks) {
     return (unsigned)g;
 }
 
-// Trace / shade / shadow for every depth of one chunk whose camera rays are queued.
+// What choose_kernels (pt_pass_plan.h) reads of a pass.
+static WfChoiceInput choice_input(const DevScene& S, const WfQueues& Q, const WfPlan& plan, bool count) {
+    WfChoiceInput in;
+    in.full = S.full; in.full_geom = S.full_geom; in.tri_num_nodes = S.tri_num_nodes; in.ana_num_nodes = S.ana_num_nodes;
+    in.ana_count = S.ana_count; in.ana_linear = S.ana_linear; in.num_planes = S.num_planes; in.num_sdf = S.num_sdf;
+    in.num_vol = S.num_vol; in.num_lights = S.num_lights; in.lights_lean = S.lights_lean; in.shade_route = S.shade_route;
+    in.env_tex = S.env_tex; in.sdf_lds = S.sdf_lds; in.vol_lds = S.vol_lds;
+    in.volq = Q.volq != nullptr; in.volq_sh = Q.volq_sh != nullptr;
+    in.knobs = plan;
+    in.knobs.tail_early = Q.tail_early;
+    in.counted = count;
+    return in;
+}
+
+// Trace / shade / shadow for every depth of one chunk whose camera rays are queued.  Which kernels: choose_kernels
+// (pt_pass_plan.cpp), once per call.
+template <bool COUNT>
 static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const DevBuffer& B, const WfQueues& Q,
-                       const WfPlan& plan, bool count, hipStream_t stream, LaunchTimer* timer, uint64_t bound) {
+                             const WfPlan& plan, hipStream_t stream, LaunchTimer* timer, uint64_t bound) {
     auto begin_k = [&](int cls, hipStream_t s) { if (timer) timer->begin(cls, s); };
     auto end_k = [&](int cls, hipStream_t s) { if (timer) timer->end(cls, s); };
-    const bool full = S.full != 0;        // shade: textures or row-4 shapes
-    const bool fullg = S.full_geom != 0;  // traversal: row-4 shapes only
-    // Per-lane refill traversal (k_wf_trace_lanes, k_wf_shadow_lanes) where rays are long
-    // enough to pay for it: lean scenes with a triangle BVH of more than kLanesMinNodes nodes.
-    const bool lanes = !fullg && (plan.lanes >= 0 ? plan.lanes == 1 : S.tri_num_nodes > kLanesMinNodes);
-    const bool ldsl = PT_SHADOW_LDS && S.num_lights <= kLdsLights;   // the lean shadow kernels' lights in LDS
-    // a few analytic records and planes, no triangles: k_wf_trace_linear / k_wf_shadow_linear
-    const bool linear = PT_LINEAR && plan.linear != 0 && !fullg && !lanes && S.ana_linear && S.tri_num_nodes <= 0 && S.num_sdf <= 0 &&
-                        S.num_vol <= 0 && S.ana_count <= kLinRecs && S.num_planes <= kLinPlanes;
-    // Split traversal (row-4 scenes with a triangle BVH): the lean refill kernels take the planes and
-    // the triangles at their occupancy, then the FULL lockstep kernels add the analytic BVH (where
-    // the §8f row-4 shapes live) from that result (pt_device.h trace_ana / ana_blocked; routed:
-    // trace_heavy / heavy_blocked for the rays that reach a heavy box).  Shadow rays split only when
-    // every light's own t is a lean intersect (spheres, cubes, planes).
-    // ... and scenes with a Volume whatever their triangle count, for the Volume queue kernels (k_wf_vol_*:
-    // full waves, the Volume in LDS): the Volume-only scene 495 -> 528 Mrays/s
-#ifndef PT_SPLIT_VOL
-#define PT_SPLIT_VOL 1
-#endif
-    const bool split = plan.lanes < 0 && fullg && (S.tri_num_nodes > kLanesMinNodes || (PT_SPLIT_VOL && S.num_vol > 0));
-    const bool split_sh = split && S.lights_lean;
-    // Head pass and list-fed refill kernels (k_wf_trace_head / k_wf_shadow_head, then the <.., LIST> forms): where
-    // the unsplit refill kernels run and their step loop is triangles only; each head runs directly before its
-    // traversal kernel, on its stream and inside its timing class.  Every other scene keeps its kernels.
-    const bool head = plan.head != 0 && lanes && !split && (S.ana_linear || S.ana_num_nodes <= 0);
+    const WfChoice ch = choose_kernels(choice_input(S, Q, plan, COUNT));
+    const bool head = ch.trace == WF_HEAD;   // (then the shadow family is WF_HEAD too)
     const hipStream_t side = plan.side ? plan.side : stream;
     // PT_HEAD_STATS=1 (a diagnostic, not for timed runs: it waits for both streams at every depth): the listed
     // share of each depth's closest-hit and shadow rays, from the list counts, to stderr
@@ -2287,147 +2267,100 @@ static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const Dev
         }
         std::fprintf(stderr, "head depth %d: %s %llu listed of %llu\n", depth, shadow ? "shadow" : "closest hit", listed, rays);
     };
+    using RayKernel = void (*)(DevScene, WfQueues, int, unsigned long long*);
+    using QueueKernel = void (*)(DevScene, WfQueues, int);
+    // over the (at most) n rays of queue / shadow set q: a traversal kernel; a head kernel, 256 · kHeadRows rays a
+    // block; a linear kernel, its resident grid whatever n is
+    auto traverse = [&](RayKernel kernel, uint64_t n, WfGrid cap, hipStream_t s, int q) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(n, kTB, plan.blocks[cap])), dim3(kTB), 0, s, S, Q, q, B.counters);
+    };
+    auto head_pass = [&](RayKernel kernel, uint64_t n, WfGrid cap, hipStream_t s, int q) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(n, 256u * kHeadRows, plan.blocks[cap])), dim3(256), 0, s, S, Q, q, B.counters);
+    };
+    auto linear = [&](RayKernel kernel, WfGrid blocks, hipStream_t s, int q) {
+        hipLaunchKernelGGL(kernel, dim3(plan.blocks[blocks]), dim3(256), 0, s, S, Q, q, B.counters);
+    };
+    // a split step's queue kernel: the Volume or SDF records its refill half deferred, staged in `lds` bytes of LDS or not
+    auto queue = [&](WfQueueKernel k, QueueKernel plain, QueueKernel staged, uint64_t n, unsigned cap, int32_t lds, hipStream_t s, int q) {
+        const dim3 g(grid_for(n, 256, cap));
+        if (k == WF_Q_STAGED) hipLaunchKernelGGL(staged, g, dim3(256), (size_t)lds, s, S, Q, q);
+        else if (k == WF_Q_PLAIN) hipLaunchKernelGGL(plain, g, dim3(256), 0, s, S, Q, q);
+    };
     auto trace = [&](int qi, uint64_t n) {
+        const WfGrid g0 = ch.trace_grid[0], g1 = ch.trace_grid[1];
         begin_k(1, stream);
-        if (split) {
-            const unsigned tl = grid_for(n, kTB, plan.lanes_trace_blocks), ta = grid_for(n, kTB, plan.full_trace_blocks);
-            if (count) {
-                hipLaunchKernelGGL((k_wf_trace_lanes<true, true>), dim3(tl), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-                hipLaunchKernelGGL((k_wf_trace<true, true, true>), dim3(ta), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-            } else {
-                hipLaunchKernelGGL((k_wf_trace_lanes<false, true>), dim3(tl), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-                hipLaunchKernelGGL((k_wf_trace<false, true, true>), dim3(ta), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-            }
-            if (Q.volq && S.num_vol > 0) {   // the Volume staged in LDS when it fits (S.vol_lds); a counted pass times the march
-                const dim3 vg(grid_for(n, 256, 2048));
-                const size_t vl = (size_t)S.vol_lds;
-                if (vl > 0 && count) hipLaunchKernelGGL((k_wf_vol_hits<true, true>), vg, dim3(256), vl, stream, S, Q, qi);
-                else if (vl > 0) hipLaunchKernelGGL((k_wf_vol_hits<true, false>), vg, dim3(256), vl, stream, S, Q, qi);
-                else if (count) hipLaunchKernelGGL((k_wf_vol_hits<false, true>), vg, dim3(256), 0, stream, S, Q, qi);
-                else hipLaunchKernelGGL((k_wf_vol_hits<false, false>), vg, dim3(256), 0, stream, S, Q, qi);
-            }
-            if (S.num_sdf > 0 && S.sdf_lds > 0)
-                hipLaunchKernelGGL(k_wf_sdf_hits<true>, dim3(grid_for(n, 256, 8192)), dim3(256), (size_t)S.sdf_lds, stream, S, Q, qi);
-            else if (S.num_sdf > 0)
-                hipLaunchKernelGGL(k_wf_sdf_hits<false>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, stream, S, Q, qi);
-            end_k(1, stream);
-            return;
+        switch (ch.trace) {
+        case WF_SPLIT:   // (a counted pass times the Volume march)
+            traverse(k_wf_trace_lanes<COUNT, true>, n, g0, stream, qi);
+            traverse(k_wf_trace<COUNT, true, true>, n, g1, stream, qi);
+            queue(ch.vol_hits, k_wf_vol_hits<false, COUNT>, k_wf_vol_hits<true, COUNT>, n, 2048, S.vol_lds, stream, qi);
+            queue(ch.sdf_hits, k_wf_sdf_hits<false>, k_wf_sdf_hits<true>, n, 8192, S.sdf_lds, stream, qi);
+            break;
+        case WF_HEAD:
+            head_pass(k_wf_trace_head<COUNT>, n, g0, stream, qi);
+            traverse(k_wf_trace_lanes<COUNT, false, true>, n, g1, stream, qi);
+            break;
+        case WF_FULL: traverse(k_wf_trace<COUNT, true>, n, g0, stream, qi); break;
+        case WF_LANES: traverse(k_wf_trace_lanes<COUNT>, n, g0, stream, qi); break;
+        case WF_LINEAR: linear(k_wf_trace_linear<COUNT>, g0, stream, qi); break;
+        case WF_LOCKSTEP: traverse(k_wf_trace<COUNT, false>, n, g0, stream, qi); break;
         }
-        if (head) {
-            const unsigned th = grid_for(n, 256u * kHeadRows, plan.head_trace_blocks), tl = grid_for(n, kTB, plan.list_trace_blocks);
-            if (count) {
-                hipLaunchKernelGGL((k_wf_trace_head<true>), dim3(th), dim3(256), 0, stream, S, Q, qi, B.counters);
-                hipLaunchKernelGGL((k_wf_trace_lanes<true, false, true>), dim3(tl), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-            } else {
-                hipLaunchKernelGGL((k_wf_trace_head<false>), dim3(th), dim3(256), 0, stream, S, Q, qi, B.counters);
-                hipLaunchKernelGGL((k_wf_trace_lanes<false, false, true>), dim3(tl), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-            }
-            end_k(1, stream);
-            return;
-        }
-        const unsigned tg = grid_for(n, kTB, fullg ? plan.full_trace_blocks : lanes ? plan.lanes_trace_blocks : plan.trace_blocks);
-        if (count && fullg) hipLaunchKernelGGL((k_wf_trace<true, true>), dim3(tg), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-        else if (fullg) hipLaunchKernelGGL((k_wf_trace<false, true>), dim3(tg), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-        else if (lanes && count) hipLaunchKernelGGL((k_wf_trace_lanes<true>), dim3(tg), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-        else if (lanes) hipLaunchKernelGGL((k_wf_trace_lanes<false>), dim3(tg), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-        else if (linear && count) hipLaunchKernelGGL((k_wf_trace_linear<true>), dim3(plan.linear_trace_blocks), dim3(256), 0, stream, S, Q, qi, B.counters);
-        else if (linear) hipLaunchKernelGGL((k_wf_trace_linear<false>), dim3(plan.linear_trace_blocks), dim3(256), 0, stream, S, Q, qi, B.counters);
-        else if (count) hipLaunchKernelGGL((k_wf_trace<true, false>), dim3(tg), dim3(kTB), 0, stream, S, Q, qi, B.counters);
-        else hipLaunchKernelGGL((k_wf_trace<false, false>), dim3(tg), dim3(kTB), 0, stream, S, Q, qi, B.counters);
         end_k(1, stream);
+    };
+    // (ch.early, ch.ldsl and ch.head_ldsl are never set in a counted pass: those forms have no counted instantiation)
+    auto shadow = [&](int q, uint64_t n) {   // shadow set q, n rays at most
+        const WfGrid g0 = ch.shadow_grid[0], g1 = ch.shadow_grid[1];
+        begin_k(3, side);
+        switch (ch.shadow) {
+        case WF_SPLIT:
+            traverse(ch.early ? k_wf_shadow_lanes<false, true, true> : k_wf_shadow_lanes<COUNT, true>, n, g0, side, q);
+            traverse(k_wf_shadow<COUNT, true, true>, n, g1, side, q);
+            queue(ch.vol_shadow, k_wf_vol_shadow<false, COUNT>, k_wf_vol_shadow<true, COUNT>, n, 2048, S.vol_lds, side, q);
+            queue(ch.sdf_shadow, k_wf_sdf_shadow<false>, k_wf_sdf_shadow<true>, n, 8192, S.sdf_lds, side, q);
+            break;
+        case WF_HEAD:
+            head_pass(ch.head_ldsl ? k_wf_shadow_head<false, true> : k_wf_shadow_head<COUNT, false>, n, g0, side, q);
+            traverse(ch.early ? k_wf_shadow_lanes<false, false, true, false, true> : k_wf_shadow_lanes<COUNT, false, false, false, true>,
+                     n, g1, side, q);
+            break;
+        case WF_FULL: traverse(k_wf_shadow<COUNT, true>, n, g0, side, q); break;
+        case WF_LANES:
+            traverse(ch.early ? k_wf_shadow_lanes<false, false, true> : ch.ldsl ? k_wf_shadow_lanes<false, false, false, true>
+                                                                               : k_wf_shadow_lanes<COUNT>, n, g0, side, q);
+            break;
+        case WF_LINEAR: linear(ch.ldsl ? k_wf_shadow_linear<false, true> : k_wf_shadow_linear<COUNT, false>, g0, side, q); break;
+        case WF_LOCKSTEP: traverse(ch.ldsl ? k_wf_shadow<false, false, false, true> : k_wf_shadow<COUNT, false>, n, g0, side, q); break;
+        }
+        end_k(3, side);
     };
     int qi = 0;
     trace(qi, bound);
     list_stats(0, qi, false);
     for (int depth = 0; depth <= smp.mb; depth++) {
-        const unsigned sg = grid_for(bound, 256, plan.shade_blocks);
+        const unsigned sg = grid_for(bound, 256, plan.blocks[G_SHADE]);
+        auto shade = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
+        };
         begin_k(2, stream);
         // both forms (the one the kept count selects runs, the other returns at once); a routed shade runs
         // the lean and the FULL SCAN kernels, each on its own vertices
-        if (full && S.shade_route) {
-            if (count) {
-                hipLaunchKernelGGL((k_wf_shade<true, false, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-                hipLaunchKernelGGL((k_wf_shade<true, true, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-            } else {
-                hipLaunchKernelGGL((k_wf_shade<false, false, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-                hipLaunchKernelGGL((k_wf_shade<false, true, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-            }
-            if (PT_SHADE_MISS && S.env_tex >= 0)   // the textured environment's misses
-                hipLaunchKernelGGL(k_wf_shade_miss, dim3(grid_for(bound, 256, 8192)), dim3(256), 0, stream, S, Q, qi);
-        } else if (count && full) {
-            hipLaunchKernelGGL((k_wf_shade<true, true, false>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-            hipLaunchKernelGGL((k_wf_shade<true, true, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-        } else if (count) {
-            hipLaunchKernelGGL((k_wf_shade<true, false, false>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-            hipLaunchKernelGGL((k_wf_shade<true, false, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-        } else if (full) {
-            hipLaunchKernelGGL((k_wf_shade<false, true, false>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-            hipLaunchKernelGGL((k_wf_shade<false, true, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-        } else {
-            hipLaunchKernelGGL((k_wf_shade<false, false, false>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
-            hipLaunchKernelGGL((k_wf_shade<false, false, true>), dim3(sg), dim3(256), 0, stream, S, smp, Q, qi, B.counters, plan.shade_form);
+        switch (ch.shade) {
+        case WF_SHADE_ROUTED: shade(k_wf_shade<COUNT, false, true>); shade(k_wf_shade<COUNT, true, true>); break;
+        case WF_SHADE_FULL: shade(k_wf_shade<COUNT, true, false>); shade(k_wf_shade<COUNT, true, true>); break;
+        case WF_SHADE_LEAN: shade(k_wf_shade<COUNT, false, false>); shade(k_wf_shade<COUNT, false, true>); break;
         }
+        if (ch.shade_miss)   // a routed shade's misses of a textured environment
+            hipLaunchKernelGGL(k_wf_shade_miss, dim3(grid_for(bound, 256, 8192)), dim3(256), 0, stream, S, Q, qi);
         end_k(2, stream);
         if (plan.side) {
             (void)hipEventRecord(plan.ev_main, stream);
             (void)hipStreamWaitEvent(side, plan.ev_main, 0);
         }
         const uint64_t children = bound * (uint64_t)(depth == 0 ? plan.root_children : plan.children);
-        const unsigned hg = grid_for(children * plan.lights_per_child, kTB,
-                                     fullg ? plan.full_shadow_blocks : lanes ? plan.lanes_shadow_blocks : plan.shadow_blocks);
-        begin_k(3, side);
-        if (split_sh) {
-            const unsigned hl = grid_for(children * plan.lights_per_child, kTB, plan.lanes_shadow_blocks);
-            const unsigned ha = grid_for(children * plan.lights_per_child, kTB, plan.full_shadow_blocks);
-            const bool sq = S.num_sdf > 0;
-            if (count) {
-                hipLaunchKernelGGL((k_wf_shadow_lanes<true, true>), dim3(hl), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-                hipLaunchKernelGGL((k_wf_shadow<true, true, true>), dim3(ha), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-            } else {
-                if (Q.tail_early) hipLaunchKernelGGL((k_wf_shadow_lanes<false, true, true>), dim3(hl), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-                else hipLaunchKernelGGL((k_wf_shadow_lanes<false, true>), dim3(hl), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-                hipLaunchKernelGGL((k_wf_shadow<false, true, true>), dim3(ha), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-            }
-            if (Q.volq_sh && S.num_vol > 0) {   // (the queues outlive a re-upload of a scene without Volumes)
-                const dim3 vg(grid_for(children * plan.lights_per_child, 256, 2048));
-                const size_t vl = (size_t)S.vol_lds;
-                if (vl > 0 && count) hipLaunchKernelGGL((k_wf_vol_shadow<true, true>), vg, dim3(256), vl, side, S, Q, 1 - qi);
-                else if (vl > 0) hipLaunchKernelGGL((k_wf_vol_shadow<true, false>), vg, dim3(256), vl, side, S, Q, 1 - qi);
-                else if (count) hipLaunchKernelGGL((k_wf_vol_shadow<false, true>), vg, dim3(256), 0, side, S, Q, 1 - qi);
-                else hipLaunchKernelGGL((k_wf_vol_shadow<false, false>), vg, dim3(256), 0, side, S, Q, 1 - qi);
-            }
-            if (sq && S.sdf_lds > 0)
-                hipLaunchKernelGGL(k_wf_sdf_shadow<true>, dim3(grid_for(children * plan.lights_per_child, 256, 8192)), dim3(256),
-                                   (size_t)S.sdf_lds, side, S, Q, 1 - qi);
-            else if (sq)
-                hipLaunchKernelGGL(k_wf_sdf_shadow<false>, dim3(grid_for(children * plan.lights_per_child, 256, 8192)), dim3(256),
-                                   0, side, S, Q, 1 - qi);
-        } else if (head) {
-            const unsigned hh = grid_for(children * plan.lights_per_child, 256u * kHeadRows, plan.head_shadow_blocks);
-            const unsigned hl = grid_for(children * plan.lights_per_child, kTB, plan.list_shadow_blocks);
-            if (count) hipLaunchKernelGGL((k_wf_shadow_head<true, false>), dim3(hh), dim3(256), 0, side, S, Q, 1 - qi, B.counters);
-            else if (ldsl) hipLaunchKernelGGL((k_wf_shadow_head<false, true>), dim3(hh), dim3(256), 0, side, S, Q, 1 - qi, B.counters);
-            else hipLaunchKernelGGL((k_wf_shadow_head<false, false>), dim3(hh), dim3(256), 0, side, S, Q, 1 - qi, B.counters);
-            if (count) hipLaunchKernelGGL((k_wf_shadow_lanes<true, false, false, false, true>), dim3(hl), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-            else if (Q.tail_early) hipLaunchKernelGGL((k_wf_shadow_lanes<false, false, true, false, true>), dim3(hl), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-            else hipLaunchKernelGGL((k_wf_shadow_lanes<false, false, false, false, true>), dim3(hl), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        } else if (count && fullg) hipLaunchKernelGGL((k_wf_shadow<true, true>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else if (fullg) hipLaunchKernelGGL((k_wf_shadow<false, true>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else if (lanes && count) hipLaunchKernelGGL((k_wf_shadow_lanes<true>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else if (lanes && Q.tail_early) hipLaunchKernelGGL((k_wf_shadow_lanes<false, false, true>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else if (lanes && ldsl) hipLaunchKernelGGL((k_wf_shadow_lanes<false, false, false, true>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else if (lanes) hipLaunchKernelGGL((k_wf_shadow_lanes<false>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else if (linear && count) hipLaunchKernelGGL((k_wf_shadow_linear<true, false>), dim3(plan.linear_shadow_blocks), dim3(256), 0, side, S, Q, 1 - qi, B.counters);
-        else if (linear && ldsl) hipLaunchKernelGGL((k_wf_shadow_linear<false, true>), dim3(plan.linear_shadow_blocks), dim3(256), 0, side, S, Q, 1 - qi, B.counters);
-        else if (linear) hipLaunchKernelGGL((k_wf_shadow_linear<false, false>), dim3(plan.linear_shadow_blocks), dim3(256), 0, side, S, Q, 1 - qi, B.counters);
-        else if (count) hipLaunchKernelGGL((k_wf_shadow<true, false>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else if (ldsl) hipLaunchKernelGGL((k_wf_shadow<false, false, false, true>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        else hipLaunchKernelGGL((k_wf_shadow<false, false>), dim3(hg), dim3(kTB), 0, side, S, Q, 1 - qi, B.counters);
-        end_k(3, side);
+        shadow(1 - qi, children * plan.lights_per_child);
         begin_k(6, side);   // PT_K_ACCUM
         const unsigned ag = grid_for(children * plan.lights_per_child, 256u * kAccWin, 4096);
-        if (count) hipLaunchKernelGGL((k_wf_nee_accum<true>), dim3(ag), dim3(256), 0, side, Q, 1 - qi, B.counters);
-        else hipLaunchKernelGGL((k_wf_nee_accum<false>), dim3(ag), dim3(256), 0, side, Q, 1 - qi, B.counters);
+        hipLaunchKernelGGL((k_wf_nee_accum<COUNT>), dim3(ag), dim3(256), 0, side, Q, 1 - qi, B.counters);
         end_k(6, side);
         if (plan.side) (void)hipEventRecord(plan.ev_side[1 - qi], side);
         list_stats(depth, 1 - qi, true);
@@ -2446,6 +2379,11 @@ static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const Dev
         (void)hipStreamWaitEvent(stream, plan.ev_side[1], 0);
     }
     return hipSuccess;
+}
+static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const DevBuffer& B, const WfQueues& Q, const WfPlan& plan,
+                             bool count, hipStream_t stream, LaunchTimer* timer, uint64_t bound) {
+    return count ? depth_loop<true>(S, smp, B, Q, plan, stream, timer, bound)
+                 : depth_loop<false>(S, smp, B, Q, plan, stream, timer, bound);
 }
 
 hipError_t wavefront_pass(const DevScene& S, const DevCamera& cam, const DevSampler& smp, const DevPass& P,
@@ -2510,41 +2448,34 @@ hipError_t wavefront_extra(const DevScene& S, const DevCamera& cam, const DevSam
     return hipGetLastError();
 }
 
-hipError_t wavefront_grids(WfGrids& plan) {
+hipError_t wavefront_grids(WfGrids& grids) {
+    // every persistent grid: the kernel whose resident capacity sizes it (its family's widest form), block size, cap
+    static const struct { WfGrid grid; const void* kernel; int block; uint32_t cap; } kGrids[] = {
+        {G_TRACE, (const void*)k_wf_trace<false, false>, kTB, kWfMaxBlocks},
+        {G_SHADE, (const void*)k_wf_shade<false, false, false>, 256, 1u << 20},
+        {G_SHADOW, (const void*)k_wf_shadow<false, false>, kTB, kWfMaxBlocks},
+        {G_LANES_TRACE, (const void*)k_wf_trace_lanes<false>, kTB, kWfMaxBlocks},
+        {G_LANES_SHADOW, (const void*)k_wf_shadow_lanes<false>, kTB, kWfMaxBlocks},
+        {G_FULL_TRACE, (const void*)k_wf_trace<false, true>, kTB, kWfMaxBlocks},
+        {G_FULL_SHADOW, (const void*)k_wf_shadow<false, true>, kTB, kWfMaxBlocks},
+        {G_LINEAR_TRACE, (const void*)k_wf_trace_linear<false>, 256, 1u << 20},
+        {G_LINEAR_SHADOW, (const void*)k_wf_shadow_linear<false, true>, 256, 1u << 20},
+        {G_HEAD_TRACE, (const void*)k_wf_trace_head<false>, 256, 1u << 20},
+        {G_HEAD_SHADOW, (const void*)k_wf_shadow_head<false, true>, 256, 1u << 20},
+        {G_LIST_TRACE, (const void*)k_wf_trace_lanes<false, false, true>, kTB, kWfMaxBlocks},
+        {G_LIST_SHADOW, (const void*)k_wf_shadow_lanes<false, false, false, false, true>, kTB, kWfMaxBlocks},
+    };
+    static_assert(sizeof kGrids / sizeof kGrids[0] == kWfGridCount, "one row per WfGrid");
     int dev = 0, cus = 0, nb = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    auto resident = [&](int per_cu, uint32_t cap) {
-        uint64_t g = (uint64_t)per_cu * (uint64_t)cus / kParts * kParts;
-        if (g < (uint64_t)kParts) g = kParts;
-        return (uint32_t)(g < cap ? g : cap / kParts * kParts);
-    };
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_trace<false, false>, kTB, 0);
-    if (e == hipSuccess) plan.trace_blocks = resident(nb, kWfMaxBlocks);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_shade<false, false, false>, 256, 0);
-    if (e == hipSuccess) plan.shade_blocks = resident(nb, 1u << 20);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_shadow<false, false>, kTB, 0);
-    if (e == hipSuccess) plan.shadow_blocks = resident(nb, kWfMaxBlocks);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_trace_lanes<false>, kTB, 0);
-    if (e == hipSuccess) plan.lanes_trace_blocks = resident(nb, kWfMaxBlocks);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_shadow_lanes<false>, kTB, 0);
-    if (e == hipSuccess) plan.lanes_shadow_blocks = resident(nb, kWfMaxBlocks);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_trace<false, true>, kTB, 0);
-    if (e == hipSuccess) plan.full_trace_blocks = resident(nb, kWfMaxBlocks);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_shadow<false, true>, kTB, 0);
-    if (e == hipSuccess) plan.full_shadow_blocks = resident(nb, kWfMaxBlocks);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_trace_linear<false>, 256, 0);
-    if (e == hipSuccess) plan.linear_trace_blocks = resident(nb, 1u << 20);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_shadow_linear<false, true>, 256, 0);
-    if (e == hipSuccess) plan.linear_shadow_blocks = resident(nb, 1u << 20);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_trace_head<false>, 256, 0);
-    if (e == hipSuccess) plan.head_trace_blocks = resident(nb, 1u << 20);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_shadow_head<false, true>, 256, 0);
-    if (e == hipSuccess) plan.head_shadow_blocks = resident(nb, 1u << 20);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_trace_lanes<false, false, true>, kTB, 0);
-    if (e == hipSuccess) plan.list_trace_blocks = resident(nb, kWfMaxBlocks);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wf_shadow_lanes<false, false, false, false, true>, kTB, 0);
-    if (e == hipSuccess) plan.list_shadow_blocks = resident(nb, kWfMaxBlocks);
+    for (const auto& g : kGrids) {
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g.kernel, g.block, 0);
+        if (e != hipSuccess) break;
+        uint64_t blocks = (uint64_t)nb * (uint64_t)cus / kParts * kParts;
+        if (blocks < (uint64_t)kParts) blocks = kParts;
+        grids.blocks[g.grid] = (uint32_t)(blocks < g.cap ? blocks : g.cap / kParts * kParts);
+    }
     return e;
 }
 

@@ -1,7 +1,8 @@
-// pass_plan_check.cpp — the render-pass plan (ptsharp_amd/csrc/pt_pass_plan.cpp) on the CPU.
+// pass_plan_check.cpp — the render-pass plan and the kernel choice (ptsharp_amd/csrc/pt_pass_plan.cpp) on the CPU.
 //
 //   pass_plan_check            a dense sweep of valid inputs; every plan is checked against what the queues must
-//                              hold, worked out here from the sampler alone (not with the plan's own helpers)
+//                              hold, worked out here from the sampler alone (not with the plan's own helpers); then
+//                              every choice of the grid of tests/test_wf_choice_host.py against what must hold of it
 //   pass_plan_check --rows     reads requests from stdin, one per line, and prints one answer line each
 //                              (tests/test_pass_plan_host.py feeds it tests/golden/pass_plan_v1.json):
 //       plan <19 inputs in the golden table's column order>
@@ -10,11 +11,15 @@
 //       budget <bytes>                            -> wf_cap_for_budget
 //       limit <entries>                           -> wf_cap_for_limit
 //       batch <total bytes> <bytes per pass> <knob>  -> batch_passes_for
+//       choice <22 inputs in the column order of tests/golden/wf_kernel_choice_v1.json>
+//            -> trace shadow early ldsl head_ldsl shade shade_miss vol_hits sdf_hits vol_shadow sdf_shadow
+//               and the four grids (closest hit, shadow; first and second launch), all by name
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
+#include <set>
 
 #include "../../ptsharp_amd/csrc/pt_pass_plan.h"
 
@@ -111,14 +116,132 @@ static void sweep() {
     }
 }
 
+// ---- the kernel choice (pt::choose_kernels)
+static const char* const kFamilyNames[] = {"lockstep", "full", "lanes", "head", "linear", "split"};
+static const char* const kShadeNames[] = {"lean", "full", "routed"};
+static const char* const kQueueNames[] = {"none", "plain", "staged"};
+static const char* const kGridNames[] = {"trace", "shade", "shadow", "lanes_trace", "lanes_shadow", "full_trace", "full_shadow",
+                                         "linear_trace", "linear_shadow", "head_trace", "head_shadow", "list_trace", "list_shadow"};
+static_assert(sizeof kGridNames / sizeof kGridNames[0] == pt::kWfGridCount, "the 13 grids");
+
+static bool in_range(int v, int n) { return v >= 0 && v < n; }
+
+// The choice's value as one number (every field in range: check_choice looks first), for counting distinct outcomes.
+static uint64_t choice_key(const pt::WfChoice& c) {
+    uint64_t k = 0;
+    for (int v : {(int)c.trace, (int)c.shadow, (int)c.early, (int)c.ldsl, (int)c.head_ldsl, (int)c.shade, (int)c.shade_miss, (int)c.vol_hits,
+                  (int)c.sdf_hits, (int)c.vol_shadow, (int)c.sdf_shadow, (int)c.trace_grid[0], (int)c.trace_grid[1], (int)c.shadow_grid[0],
+                  (int)c.shadow_grid[1]})
+        k = k * 16 + (uint64_t)v;
+    return k;
+}
+
+#define CHECK_CHOICE(cond)                                                   \
+    do {                                                                     \
+        if (!(cond) && g_fail++ < 20) std::printf("FAILED %s (line %d) at choice %ld\n", #cond, __LINE__, g_choices); \
+    } while (0)
+
+static long g_choices = 0, g_family[2][6];
+static std::set<uint64_t> g_outcomes;
+static uint64_t g_last_outcome = 0;
+
+// What must hold of every choice, from the inputs alone (none of choose_kernels' own predicates is used).
+static void check_choice(const pt::WfChoiceInput& in) {
+    using namespace pt;
+    const WfChoice c = choose_kernels(in);
+    g_choices++;
+    // exactly one closest-hit family, one shadow family, one shade family; every grid named is one of the 13
+    const bool ranges = in_range(c.trace, 6) && in_range(c.shadow, 6) && in_range(c.shade, 3) && in_range(c.vol_hits, 3) &&
+                        in_range(c.sdf_hits, 3) && in_range(c.vol_shadow, 3) && in_range(c.sdf_shadow, 3) &&
+                        in_range(c.trace_grid[0], kWfGridCount) && in_range(c.trace_grid[1], kWfGridCount) &&
+                        in_range(c.shadow_grid[0], kWfGridCount) && in_range(c.shadow_grid[1], kWfGridCount);
+    CHECK_CHOICE(ranges);
+    if (!ranges) return;
+    g_family[0][c.trace]++;
+    g_family[1][c.shadow]++;
+    if (g_outcomes.empty() || choice_key(c) != g_last_outcome) g_outcomes.insert(g_last_outcome = choice_key(c));
+    // a counted pass has no LDSL and no EARLY form; the two never combine
+    if (in.counted) CHECK_CHOICE(!c.early && !c.ldsl && !c.head_ldsl);
+    CHECK_CHOICE(!(c.early && c.ldsl));
+    if (c.early) CHECK_CHOICE(in.knobs.tail_early != 0);
+    if (c.ldsl || c.head_ldsl) CHECK_CHOICE(in.num_lights <= kLdsLights);
+    if (c.head_ldsl) CHECK_CHOICE(c.shadow == WF_HEAD);
+    // head: the refill kernels run (a lean scene; forced, or by its BVH's size), unsplit, for both kinds of ray
+    const bool refill = !in.full_geom && (in.knobs.lanes == 1 || (in.knobs.lanes < 0 && in.tri_num_nodes > kLanesMinNodes));
+    CHECK_CHOICE((c.trace == WF_HEAD) == (c.shadow == WF_HEAD));
+    if (c.trace == WF_HEAD) CHECK_CHOICE(refill && in.knobs.head != 0);
+    if (c.trace == WF_LANES || c.shadow == WF_LANES) CHECK_CHOICE(refill);
+    if (in.knobs.lanes == 0) CHECK_CHOICE(c.trace != WF_LANES && c.trace != WF_HEAD && c.trace != WF_SPLIT);
+    // row-4 shapes are traversed by the FULL kernels only, whole or as the second half of a split
+    CHECK_CHOICE((in.full_geom != 0) == (c.trace == WF_FULL || c.trace == WF_SPLIT));
+    CHECK_CHOICE((in.full_geom != 0) == (c.shadow == WF_FULL || c.shadow == WF_SPLIT));
+    if (c.shadow == WF_SPLIT) CHECK_CHOICE(c.trace == WF_SPLIT && in.lights_lean);
+    if (c.trace == WF_SPLIT) CHECK_CHOICE(in.knobs.lanes < 0);
+    // linear: no triangles, no SDF, no Volume, what fits its LDS
+    if (c.trace == WF_LINEAR || c.shadow == WF_LINEAR)
+        CHECK_CHOICE(c.trace == c.shadow && in.tri_num_nodes <= 0 && in.num_sdf <= 0 && in.num_vol <= 0 && in.ana_count <= kLinRecs &&
+                     in.num_planes <= kLinPlanes && in.ana_linear && in.knobs.linear != 0);
+    // each launch's grid is its own kernel's
+    const int tg[6][2] = {{G_TRACE, G_TRACE}, {G_FULL_TRACE, G_FULL_TRACE}, {G_LANES_TRACE, G_LANES_TRACE}, {G_HEAD_TRACE, G_LIST_TRACE},
+                          {G_LINEAR_TRACE, G_LINEAR_TRACE}, {G_LANES_TRACE, G_FULL_TRACE}};
+    const int sg[6][2] = {{G_SHADOW, G_SHADOW}, {G_FULL_SHADOW, G_FULL_SHADOW}, {G_LANES_SHADOW, G_LANES_SHADOW}, {G_HEAD_SHADOW, G_LIST_SHADOW},
+                          {G_LINEAR_SHADOW, G_LINEAR_SHADOW}, {G_LANES_SHADOW, G_FULL_SHADOW}};
+    CHECK_CHOICE(c.trace_grid[0] == tg[c.trace][0] && c.trace_grid[1] == tg[c.trace][1]);
+    CHECK_CHOICE(c.shadow_grid[0] == sg[c.shadow][0] && c.shadow_grid[1] == sg[c.shadow][1]);
+    // the queue kernels: after a split step only, where the scene has such records (and the Volume queue exists)
+    CHECK_CHOICE((c.vol_hits != WF_Q_NONE) == (c.trace == WF_SPLIT && in.volq && in.num_vol > 0));
+    CHECK_CHOICE((c.sdf_hits != WF_Q_NONE) == (c.trace == WF_SPLIT && in.num_sdf > 0));
+    CHECK_CHOICE((c.vol_shadow != WF_Q_NONE) == (c.shadow == WF_SPLIT && in.volq_sh && in.num_vol > 0));
+    CHECK_CHOICE((c.sdf_shadow != WF_Q_NONE) == (c.shadow == WF_SPLIT && in.num_sdf > 0));
+    for (pt::WfQueueKernel q : {c.vol_hits, c.vol_shadow}) CHECK_CHOICE(q == WF_Q_NONE || (q == WF_Q_STAGED) == (in.vol_lds > 0));
+    for (pt::WfQueueKernel q : {c.sdf_hits, c.sdf_shadow}) CHECK_CHOICE(q == WF_Q_NONE || (q == WF_Q_STAGED) == (in.sdf_lds > 0));
+    // shade
+    CHECK_CHOICE((c.shade == WF_SHADE_LEAN) == !in.full && (c.shade == WF_SHADE_ROUTED) == (in.full && in.shade_route));
+    CHECK_CHOICE(c.shade_miss == (c.shade == WF_SHADE_ROUTED && in.env_tex >= 0));
+}
+
+// The grid of tests/test_wf_choice_host.py, whole (the test feeds every kChoiceStride-th row of it through --rows).
+static void sweep_choices() {
+    pt::WfChoiceInput in;
+    for (int tri : {0, 1, pt::kLanesMinNodes, pt::kLanesMinNodes + 1})
+    for (int recs : {0, pt::kLinRecs, pt::kLinRecs + 1})
+    for (int planes : {0, pt::kLinPlanes, pt::kLinPlanes + 1})
+    for (int lights : {1, pt::kLdsLights, pt::kLdsLights + 1})
+    for (int ana_nodes : {0, 3})
+    for (int full = 0; full < 2; full++)
+    for (int full_geom = 0; full_geom <= full; full_geom++)
+    for (int bits = 0; bits < 1 << 14; bits++)
+    for (int lanes = -1; lanes <= 1; lanes++) {
+        auto bit = [&](int b) { return (bits >> b) & 1; };
+        in.tri_num_nodes = tri; in.ana_count = recs; in.num_planes = planes; in.num_lights = lights; in.ana_num_nodes = ana_nodes;
+        in.full = full; in.full_geom = full_geom; in.knobs.lanes = lanes;
+        in.ana_linear = bit(0); in.lights_lean = bit(1); in.shade_route = bit(2); in.env_tex = bit(3) - 1;
+        in.sdf_lds = 64 * bit(4); in.vol_lds = 64 * bit(5); in.num_sdf = 2 * bit(6); in.num_vol = bit(7);
+        in.volq = bit(8) != 0; in.volq_sh = bit(9) != 0; in.knobs.head = bit(10); in.knobs.linear = bit(11) - 1;
+        in.knobs.tail_early = bit(12); in.counted = bit(13) != 0;
+        check_choice(in);
+    }
+}
+
 static int rows() {
     char line[1024];
     while (std::fgets(line, sizeof line, stdin)) {
         unsigned long long a = 0, b = 0;
         long long k = 0;
         pt::PassPlanInput in;
-        int counted = 0;
-        if (std::sscanf(line, "budget %llu", &a) == 1) std::printf("%u\n", pt::wf_cap_for_budget((size_t)a));
+        pt::WfChoiceInput ci;
+        int counted = 0, volq = 0, volq_sh = 0;
+        if (std::sscanf(line, "choice %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d", &ci.full, &ci.full_geom,
+                        &ci.tri_num_nodes, &ci.ana_num_nodes, &ci.ana_count, &ci.ana_linear, &ci.num_planes, &ci.num_sdf, &ci.num_vol,
+                        &ci.num_lights, &ci.lights_lean, &ci.shade_route, &ci.env_tex, &ci.sdf_lds, &ci.vol_lds, &volq, &volq_sh,
+                        &ci.knobs.lanes, &ci.knobs.head, &ci.knobs.linear, &ci.knobs.tail_early, &counted) == 22) {
+            ci.volq = volq != 0; ci.volq_sh = volq_sh != 0; ci.counted = counted != 0;
+            const pt::WfChoice c = pt::choose_kernels(ci);
+            std::printf("%s %s %d %d %d %s %d %s %s %s %s %s %s %s %s\n", kFamilyNames[c.trace], kFamilyNames[c.shadow], (int)c.early, (int)c.ldsl,
+                        (int)c.head_ldsl, kShadeNames[c.shade], (int)c.shade_miss, kQueueNames[c.vol_hits], kQueueNames[c.sdf_hits],
+                        kQueueNames[c.vol_shadow], kQueueNames[c.sdf_shadow], kGridNames[c.trace_grid[0]], kGridNames[c.trace_grid[1]],
+                        kGridNames[c.shadow_grid[0]], kGridNames[c.shadow_grid[1]]);
+        } else if (std::sscanf(line, "budget %llu", &a) == 1) std::printf("%u\n", pt::wf_cap_for_budget((size_t)a));
         else if (std::sscanf(line, "limit %llu", &a) == 1) std::printf("%u\n", pt::wf_cap_for_limit(a));
         else if (std::sscanf(line, "batch %llu %llu %lld", &a, &b, &k) == 3)
             std::printf("%d\n", pt::batch_passes_for((size_t)a, (size_t)b, (int64_t)k));
@@ -146,7 +269,12 @@ static int rows() {
 int main(int argc, char** argv) {
     if (argc > 1 && !std::strcmp(argv[1], "--rows")) return rows();
     sweep();
-    std::printf("plans %ld: wavefront %ld (in several chunks %ld), split %ld, refused %ld\n", g_plans, g_wavefront, g_multi_chunk,
+    sweep_choices();
+    std::printf("choices %ld: distinct %zu; closest hit", g_choices, g_outcomes.size());
+    for (int f = 0; f < 6; f++) std::printf(" %s %ld", kFamilyNames[f], g_family[0][f]);
+    std::printf("; shadow");
+    for (int f = 0; f < 6; f++) std::printf(" %s %ld", kFamilyNames[f], g_family[1][f]);
+    std::printf("\nplans %ld: wavefront %ld (in several chunks %ld), split %ld, refused %ld\n", g_plans, g_wavefront, g_multi_chunk,
                 g_split, g_refused);
     std::printf("pass_plan_check: %ld failures\n", g_fail);
     return g_fail ? 1 : 0;
