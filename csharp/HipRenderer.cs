@@ -231,6 +231,15 @@ namespace PTSharpCore
             public IntPtr mesh_mask;       // [num_meshes] int or null (= all); 0: the mesh takes its rest values verbatim
         }
 
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_volume_update
+        {
+            public int num_volumes;        // must equal the uploaded scene's
+            public fixed int reserved[3];  // 0
+            public IntPtr data;            // null, or [num_volumes] pointers: null = the volume keeps its voxels, else [d][h][w] double
+            public IntPtr windows;         // null, or [num_volumes] pointers: null = kept, else the uploaded num_windows pt_volume_window
+        }
+
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_get_version();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_device_count(out int count);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_create(ref pt_device_opts opts, out IntPtr ctx);
@@ -275,6 +284,9 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, ref pt_mesh_update u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, IntPtr u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_tri_bvh_cost(IntPtr ctx, double[] out3);
+        // new voxels and iso-windows for the scene's Volumes: their derived tables rebuilt on the device (DESIGN.md §4i)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_volumes(IntPtr ctx, ref pt_volume_update u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_volume(IntPtr ctx, int index, long[] info, double[] data, [In, Out] pt_volume_window[] windows, sbyte[] runs, double[] cells);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
         // what a host's rays hit and where: identity in the host's numbering and Hit.Info (DESIGN.md §4h)
@@ -872,6 +884,44 @@ namespace PTSharpCore
         {
             PtHip.Check(PtHip.pt_rebuild_meshes(ctx, IntPtr.Zero, out double ms), "pt_rebuild_meshes");
             return ms;
+        }
+
+        /// <summary>New voxels and new iso-windows for the Volumes of the uploaded scene, in the upload's volume order
+        /// (pt_update_volumes): data[i] holds W*H*D doubles (Data[x + y*W + z*W*H]) or is null (volume i keeps its
+        /// voxels); windows[i] holds the volume's uploaded number of windows with new lo and hi (the materials must be
+        /// the uploaded ones) or is null.  Either array may be null.  The volumes' derived tables are rebuilt on the
+        /// device; a volume given windows only sends no voxels.  An edit that would make a Volume start or stop being
+        /// a light is refused (PT_ERR_UNSUPPORTED): upload the scene again.  Returns the device time of the kernels in
+        /// ms.</summary>
+        public double UpdateVolumes(int numVolumes, double[][] data = null, PtHip.pt_volume_window[][] windows = null)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            IntPtr PinHeld(Array a)
+            {
+                if (a == null) return IntPtr.Zero;
+                var h = GCHandle.Alloc(a, GCHandleType.Pinned);
+                held.Add(h);
+                return h.AddrOfPinnedObject();
+            }
+            try
+            {
+                // the pointer arrays and every array they name stay pinned for the call
+                IntPtr[] dp = data == null ? null : new IntPtr[Math.Max(1, numVolumes)];
+                IntPtr[] wp = windows == null ? null : new IntPtr[Math.Max(1, numVolumes)];
+                for (int i = 0; i < numVolumes; i++)
+                {
+                    if (dp != null && i < data.Length) dp[i] = PinHeld(data[i]);
+                    if (wp != null && i < windows.Length) wp[i] = PinHeld(windows[i]);
+                }
+                var u = new PtHip.pt_volume_update { num_volumes = numVolumes, data = PinHeld(dp), windows = PinHeld(wp) };
+                PtHip.Check(PtHip.pt_update_volumes(ctx, ref u, out double ms), "pt_update_volumes");
+                return ms;
+            }
+            finally
+            {
+                foreach (var h in held) h.Free();
+            }
         }
 
         /// <summary>The hits of n rays with their identity and Hit.Info (pt_intersect_hits).</summary>

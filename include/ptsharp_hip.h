@@ -30,6 +30,8 @@
  *   / pt_tri_bvh_cost  triangle BVH into a balanced median tree on the device  builds a new tree for every frame's scene)
  *                      for the new positions; the SAH cost of the tree as it
  *                      stands, the host's trigger for "refit or rebuild"
+ *   pt_update_volumes  (new) new voxels and iso-windows for the scene's         Volume.NewVolume, Volume.cs:48-71, and
+ *   / pt_read_volume   Volumes: their derived tables rebuilt on the device      VolumeWindow, Volume.cs:8-19
  *   pt_render_pass    one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
@@ -791,6 +793,57 @@ int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms)
  * the device.  No triangle in the BVH (or A == 0): zeros.  Synchronises and changes nothing.  A NULL argument:
  * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_tri_bvh_cost(void* ctx, double out[3]);
+
+/* New voxels and new iso-windows for the Volumes of the uploaded scene: what a user edits
+ * interactively (an iso-window dragged to another tissue, the next grid of a time series), without the re-upload
+ * that recompiles and re-sends the whole scene.  data[i] non-NULL gives volume i new voxels, [d][h][w] doubles of
+ * the uploaded dimensions; windows[i] non-NULL gives it new lo and hi for each of its uploaded num_windows windows
+ * (the materials must equal the uploaded ones).  Volumes are in pt_scene_desc order; the arrays are copied during
+ * the call.
+ * Equivalence: afterwards every ray query, feature pass and render pass sees the scene a fresh pt_upload_scene of
+ * the same pt_scene_desc with these voxels and windows substituted would see, and every word of the volume state on
+ * the device equals that upload's: the voxels, the window rows, the uniform-cell signs of the march skip (1 B per
+ * cell of the (w+1)(h+1)(d+1) lattice), the cell-major corners (64 B per cell) where the upload made them, and the
+ * header's zero_sign.  No tie-order caveat: nothing is re-sorted.  The dimensions, zscale, the box, the window
+ * count and the materials stay, and with them what the upload decided from them: which volumes have cell-major
+ * corners, the LDS staging of a scene's one Volume, the routing and every BVH (the box is given, not derived from
+ * the voxels, so no box, record or light sphere moves).  A Volume reached through a pt_transformed_shape is served
+ * too: that shape reads the same volume.  New dimensions, zscale, box, window count or window materials need a
+ * pt_upload_scene.
+ * Rebuild scope: a volume given new data has its voxels copied in and both tables rebuilt on the device from them;
+ * a volume given only new windows has its window rows, its signs and zero_sign rebuilt, and its voxels are neither
+ * sent nor copied (24 B per window cross the bus).
+ * Lights: Scene.Add registers a shape as a light when MaterialAt(origin).Emittance > 0 (Scene.cs:29-38).  For a
+ * Volume, and for a TransformedShape over one (whose MaterialAt passes the point on unmapped), that is the material
+ * of the sample at the origin, which is 0 whatever the voxels (Sample's z index there is d, past the last slice), so
+ * it depends on the windows alone.  The set of lights is fixed at upload: before anything is copied or launched the
+ * call evaluates the test with the new windows and refuses with PT_ERR_UNSUPPORTED when any shape's membership
+ * would differ.  A light that stays one takes the material the test now gives.
+ * Ordering: runs on the context's stream after every pass issued before it and synchronises before returning.  The
+ * Buffer, the pass state, the counters, the feature buffers, the query tables and the process-wide build cache are
+ * untouched.  out_kernel_ms (may be NULL) is the device time of the call's kernels.
+ * Non-finite voxels, lo and hi behave as at upload: a cell with a non-finite corner is "cannot vouch" (sign 0); no
+ * access leaves its array.
+ * Errors (nothing launched, the scene untouched): a NULL ctx or u, reserved != 0, num_volumes different from the
+ * scene's, a window's material different from the uploaded one: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; a
+ * changed light membership: PT_ERR_UNSUPPORTED.  Both arrays NULL, every entry NULL, or a scene without volumes and
+ * num_volumes 0: PT_OK, nothing launched, *out_kernel_ms = 0. */
+typedef struct pt_volume_update {
+    int32_t num_volumes;                       /* must equal the uploaded scene's */
+    int32_t reserved[3];                       /* 0 */
+    const double* const * data;                /* NULL, or [num_volumes]: data[i] NULL = volume i keeps its voxels,
+                                                  else [d][h][w] doubles of the uploaded dimensions */
+    const pt_volume_window* const * windows;   /* NULL, or [num_volumes]: windows[i] NULL = kept, else the uploaded
+                                                  num_windows entries; lo and hi are taken, material must equal the uploaded one */
+} pt_volume_update;
+int pt_update_volumes(void* ctx, const pt_volume_update* u, double* out_kernel_ms);
+/* What the device holds for volume `index` (tests and tools): info = {w, h, d, num_windows, zero_sign, has_cells,
+ * cells in the table = (w+1)(h+1)(d+1), 0}; data receives w h d doubles, windows num_windows entries, runs one int8
+ * per cell, cells 8 doubles per cell when has_cells (else it is left alone).  Every pointer but ctx may be NULL.
+ * Synchronises and changes nothing.  A NULL ctx, or an index outside the scene's volumes: PT_ERR_INVALID_ARG; no
+ * scene: PT_ERR_NO_SCENE. */
+int pt_read_volume(void* ctx, int32_t index, int64_t info[8], double* data, pt_volume_window* windows,
+                   int8_t* runs, double* cells);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

@@ -152,6 +152,11 @@ class pt_mesh_pose(C.Structure):
                 ("matrices", _d), ("mesh_mask", _i)]
 
 
+class pt_volume_update(C.Structure):
+    _fields_ = [("num_volumes", C.c_int32), ("reserved", C.c_int32 * 3), ("data", C.POINTER(_d)),
+                ("windows", C.POINTER(C.POINTER(pt_volume_window)))]
+
+
 # pt_hit_arrays' outputs in the header's order: name -> (numpy dtype, components per ray)
 HIT_ARRAYS = {"t": ("f8", 1), "kind": ("i4", 1), "index": ("i4", 1), "prim": ("i4", 1), "shape": ("i4", 1),
               "position": ("f4", 3), "normal": ("f4", 3), "inside": ("i4", 1), "material": ("i4", 1),
@@ -200,6 +205,9 @@ SIGNATURES = {
     "pt_read_pose": (C.c_int, [C.c_void_p, _f, _f, _f, _f, _f, _f]),
     "pt_rebuild_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_update), _d]),
     "pt_tri_bvh_cost": (C.c_int, [C.c_void_p, _d]),
+    "pt_update_volumes": (C.c_int, [C.c_void_p, C.POINTER(pt_volume_update), _d]),
+    "pt_read_volume": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _d, C.POINTER(pt_volume_window),
+                                 C.POINTER(C.c_int8), _d]),
     "pt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_sampler), C.POINTER(pt_pass_params)]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_reset_buffer": (C.c_int, [C.c_void_p]),

@@ -34,6 +34,7 @@
 #include "pt_scene_compile.h"
 #include "pt_shape_refit.h"
 #include "pt_update_layout.h"
+#include "pt_volume_update.h"
 #include "pt_wavefront.h"
 
 #pragma clang fp contract(off)
@@ -135,6 +136,8 @@ hipError_t launch_bvh_cost(int64_t num_nodes, const uint32_t* nodes, void* ws, d
 // pt_pose.hip
 hipError_t launch_pose(int64_t n, int32_t num_meshes, const int32_t* group, const int32_t* mask, const double* matrices,
                        bool normals, const float* const rest[6], float* const out[6], hipStream_t stream);
+// pt_volume.hip
+hipError_t launch_vol_rebuild(const DevVolume& v, bool new_data, hipStream_t stream);
 }
 
 namespace {
@@ -216,6 +219,12 @@ struct SceneDyn {
     pt::QueryTables query;                // the slot tables pt_intersect_hits uploads at its first call
     std::vector<pt::DevLight> h_lights;   // the uploaded lights; the ones that follow geometry are moved by the updates
     bool has_blas = false;                // an instanced mesh: pt_update_triangles and pt_rebuild_meshes refuse
+    // pt_update_volumes: the volumes' headers with their device addresses and zero_sign as the device
+    // holds them, the window rows it holds now (volume i's start at vol_win_off[i]), the light test's inputs; no grid
+    pt::VolumeTables volume_update;
+    std::vector<pt::DevVolume> vols;
+    std::vector<pt::DevWindow> vol_windows;
+    std::vector<size_t> vol_win_off;
     Workspace<pt::RefitDev> refit_ws;       // first update, or pt_read_tri_normals
     Workspace<pt::NormalsDev> normals_ws;   // first PT_NORMALS_SMOOTH
     Workspace<pt::ShapesDev> shapes_ws;     // first pt_update_shapes, or pt_update_meshes on instanced meshes
@@ -689,6 +698,10 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     c->dyn.query = std::move(H.query);
     c->dyn.h_lights = std::move(H.lights);
     c->dyn.has_blas = !H.blas.empty();
+    c->dyn.volume_update = std::move(H.volume_update);
+    c->dyn.vols = std::move(vols);
+    c->dyn.vol_windows = std::move(H.windows);
+    for (const pt::HostVolume& v : H.volumes) c->dyn.vol_win_off.push_back(v.win_off);
     c->stats.bvh_nodes = H.bvh_nodes;
     c->stats.traversal_bytes = H.traversal_bytes;
     c->stats.bvh_bytes = H.bvh_bytes;
@@ -1956,6 +1969,103 @@ int pt_read_shape_bvh(void* ctx, int64_t counts[4], uint32_t* nodes, uint32_t* r
         for (int k = 0; k < 3; k++) lights[4 * i + k] = (double)dl[i].center[k];
         lights[4 * i + 3] = dl[i].radius;
     }
+    return PT_OK;
+}
+
+// ---- Volumes edited in place
+static_assert(sizeof(pt_volume_window) == sizeof(pt::DevWindow), "pt_read_volume copies window rows as they are");
+
+int pt_update_volumes(void* ctx, const pt_volume_update* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!u) return fail(PT_ERR_INVALID_ARG, "update volumes: u is NULL");
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const int32_t nv = (int32_t)Y.vols.size();
+    std::vector<pt::VolState> state((size_t)nv);
+    for (int32_t i = 0; i < nv; i++) state[(size_t)i] = pt::VolState{Y.vols[(size_t)i], Y.vol_windows.data() + Y.vol_win_off[(size_t)i]};
+    const char* why = "";
+    if (const int rc = pt::vol_update_check(u, nv, state.data(), &why)) return fail(rc, std::string("update volumes: ") + why);
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (!pt::vol_update_any(u)) return PT_OK;
+    // the window rows the call would leave, and the light test with them, before anything is copied or launched
+    std::vector<pt::DevWindow> rows = Y.vol_windows;
+    std::vector<const pt::DevWindow*> win((size_t)nv);
+    std::vector<pt::DevVolume> hdrs = Y.vols;
+    for (int32_t i = 0; i < nv; i++) {
+        pt::DevWindow* r = rows.data() + Y.vol_win_off[(size_t)i];
+        win[(size_t)i] = r;
+        if (!u->windows || !u->windows[i]) continue;
+        for (int32_t k = 0; k < hdrs[(size_t)i].nwin; k++) { r[k].lo = u->windows[i][k].lo; r[k].hi = u->windows[i][k].hi; }
+        pt::DevVolume view = hdrs[(size_t)i];
+        view.windows = r;
+        hdrs[(size_t)i].zero_sign = pt::vol_zero_sign(view);
+    }
+    const pt::VolumeTables& T = Y.volume_update;
+    std::vector<int32_t> mats(T.slots.size());
+    if (const int rc = pt::vol_update_lights(T.slots.data(), T.slots.size(), hdrs.data(), win.data(), T.emittance.data(),
+                                             (int32_t)T.emittance.size(), mats.data(), &why))
+        return fail(rc, std::string("update volumes: ") + why);
+    PT_HIP(hipSetDevice(c->device));
+    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
+    // the copies, then the header words and the windows
+    for (int32_t i = 0; i < nv; i++) {
+        const pt::DevVolume& v = hdrs[(size_t)i];
+        if (u->data && u->data[i])
+            PT_HIP(hipMemcpyAsync(const_cast<double*>(v.data), u->data[i], (size_t)v.w * v.h * v.d * sizeof(double),
+                                  hipMemcpyHostToDevice, c->stream));
+    }
+    for (int32_t i = 0; i < nv; i++) {
+        if (!u->windows || !u->windows[i]) continue;
+        const pt::DevVolume& v = hdrs[(size_t)i];
+        PT_HIP(hipMemcpyAsync(const_cast<pt::DevVolume*>(c->S.volumes) + i, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
+        if (v.nwin > 0)
+            PT_HIP(hipMemcpyAsync(const_cast<pt::DevWindow*>(v.windows), win[(size_t)i], (size_t)v.nwin * sizeof(pt::DevWindow),
+                                  hipMemcpyHostToDevice, c->stream));
+    }
+    // one launch per changed volume
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    for (int32_t i = 0; i < nv; i++) {
+        const bool new_data = u->data && u->data[i];
+        if (!new_data && !(u->windows && u->windows[i])) continue;
+        PT_HIP(pt::launch_vol_rebuild(hdrs[(size_t)i], new_data, c->stream));
+    }
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    // a light made from a Volume keeps its place and takes the material the test gives now
+    bool lights_changed = false;
+    for (size_t s = 0; s < T.slots.size(); s++) {
+        const int32_t L = T.slots[s].light;
+        if (L < 0 || Y.h_lights[(size_t)L].mat == mats[s]) continue;
+        Y.h_lights[(size_t)L].mat = mats[s];
+        lights_changed = true;
+    }
+    if (lights_changed) if (const int rc = upload_lights(c)) return rc;
+    PT_HIP(hipStreamSynchronize(c->stream));
+    Y.vols = std::move(hdrs);
+    Y.vol_windows = std::move(rows);
+    return kernel_ms(c, out_kernel_ms);
+}
+
+int pt_read_volume(void* ctx, int32_t index, int64_t info[8], double* data, pt_volume_window* windows, int8_t* runs,
+                   double* cells) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    if (index < 0 || (size_t)index >= c->dyn.vols.size()) return fail(PT_ERR_INVALID_ARG, "read volume: index outside the scene's volumes");
+    PT_HIP(hipSetDevice(c->device));
+    pt::DevVolume v{};   // the header the device holds, not the host's copy
+    PT_HIP(hipMemcpyAsync(&v, c->S.volumes + index, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    const uint64_t ncells = pt::vol_cell_count(v.w, v.h, v.d);
+    if (info) {
+        const int64_t o[8] = {v.w, v.h, v.d, v.nwin, v.zero_sign, v.cells ? 1 : 0, (int64_t)ncells, 0};
+        std::memcpy(info, o, sizeof o);
+    }
+    PT_HIP(read_back(c, data, v.data, (size_t)v.w * v.h * v.d * sizeof(double)));
+    PT_HIP(read_back(c, windows, v.windows, (size_t)v.nwin * sizeof(pt::DevWindow)));
+    PT_HIP(read_back(c, runs, v.runs, v.runs ? (size_t)ncells : 0));
+    PT_HIP(read_back(c, cells, v.cells, v.cells ? (size_t)pt::vol_cell_byte(ncells) : 0));
+    PT_HIP(hipStreamSynchronize(c->stream));
     return PT_OK;
 }
 

@@ -432,31 +432,7 @@ PT_HD int vol_band(const DevVolume& v, double s) {
     }
     return 2 * v.nwin;
 }
-// Host: fill out[(x0+1) + (y0+1)(w+1) + (z0+1)(w+1)(h+1)] for cells x0 in -1..w-1, y0 in -1..h-1,
-// z0 in -1..d-1 (a cell outside that range has every corner outside the grid: zero_sign).
-inline void vol_build_runs(const DevVolume& v, int8_t* out, int32_t& zero_sign) {
-    const int sx = v.w + 1, sy = v.h + 1;
-    auto sign_of_band = [&](int b) { return (b & 1) ? 0 : (b == 2 * v.nwin ? v.nwin + 1 : 1); };
-    zero_sign = sign_of_band(vol_band(v, 0.0));
-    for (int z0 = -1; z0 < v.d; z0++)
-        for (int y0 = -1; y0 < v.h; y0++)
-            for (int x0 = -1; x0 < v.w; x0++) {
-                double mn = 0, mx = 0;
-                bool first = true, finite = true;   // a NaN / infinite corner can interpolate to NaN (Sign 0)
-                for (int c = 0; c < 8; c++) {
-                    const double g = vol_get(v, x0 + (c >> 2 & 1), y0 + (c >> 1 & 1), z0 + (c & 1));
-                    finite = finite && isfinite(g);
-                    if (first || g < mn) mn = g;
-                    if (first || g > mx) mx = g;
-                    first = false;
-                }
-                const double margin = 1e-9 * (1.0 + fabs(mn) + fabs(mx));
-                const int b0 = vol_band(v, mn - margin), b1 = vol_band(v, mx + margin);
-                const int sg = (finite && b0 == b1) ? sign_of_band(b0) : 0;
-                // a Sign past int8 (above every window of 127 or more) is stored as 0: "no shortcut"
-                out[(x0 + 1) + (size_t)(y0 + 1) * sx + (size_t)(z0 + 1) * sx * sy] = (int8_t)(sg > 127 ? 0 : sg);
-            }
-}
+// (The host loop that fills the table, vol_build_runs, is in pt_volume_update.h with the per-cell rule it runs.)
 // t after k more additions of step (a power of two) made one at a time, as Volume.Intersect's
 // `t += step`: inside one binade, with t's ulp dividing step, every partial sum is exact, so k·step
 // is added at once; the addition that crosses into the next binade rounds, and is made alone.
@@ -501,15 +477,7 @@ PT_HD int vol_key_sign(const DevVolume& v, VolKey k) {
     if (k.x < -1 || k.y < -1 || k.z < -1 || k.x >= v.w || k.y >= v.h || k.z >= v.d) return v.zero_sign;
     return v.runs[(k.x + 1) + (size_t)(k.y + 1) * (v.w + 1) + (size_t)(k.z + 1) * (v.w + 1) * (v.h + 1)];
 }
-// Host: fill out[8·((x0+1) + (y0+1)(w+1) + (z0+1)(w+1)(h+1)) + c] = corner c of cell (x0, y0, z0), the runs table's
-// cells, c = 4·dx + 2·dy + dz (vol_sample's v000 v001 v010 v011 v100 v101 v110 v111).
-inline void vol_build_cells(const DevVolume& v, double* out) {
-    size_t i = 0;
-    for (int z0 = -1; z0 < v.d; z0++)
-        for (int y0 = -1; y0 < v.h; y0++)
-            for (int x0 = -1; x0 < v.w; x0++, i++)
-                for (int c = 0; c < 8; c++) out[8 * i + (size_t)c] = vol_get(v, x0 + (c >> 2), y0 + (c >> 1 & 1), z0 + (c & 1));
-}
+// (vol_build_cells, the host loop that fills the cell-major corners vol_corners reads, is in pt_volume_update.h.)
 // The Sign of march position t (vol_key_sign of a uniform cell, else Volume.Sign of the sample) with the
 // lattice coordinates computed once: vol_key and Volume.Sample (vol_sample) scale the same position by
 // the same operations, so the key and the sample share them (one fp64 division by zscale, not two).
@@ -586,3 +554,5 @@ PT_HD double vol_t(const DevVolume& v, v3 o, v3 d, uint32_t* samples = nullptr) 
 }
 
 }  // namespace pt
+
+#include "pt_volume_update.h"   // the tables' per-cell rules and host builders (vol_build_runs, vol_build_cells)

@@ -790,7 +790,12 @@ void Compiler::lights() {
     for (int i = 0; i < d->num_shapes; i++) {
         int k = d->shape_kind[i], j = d->shape_index[i];
         int mat = k == PT_SHAPE_TRIANGLE ? d->tri_material[j] : k == PT_SHAPE_MESH ? -1 : shape_mat_any(k, j, origin);
-        if (mat < 0 || mat >= d->num_materials || !(d->materials[mat].emittance > 0)) continue;  // Mesh: `default`
+        const bool lit = !(mat < 0 || mat >= d->num_materials || !(d->materials[mat].emittance > 0));  // Mesh: `default`
+        // what a later pt_update_volumes tests again with its new windows (VolumeTables)
+        const int vj = k == PT_SHAPE_VOLUME ? j
+                     : (k == PT_SHAPE_TRANSFORMED && d->transformed[j].shape_kind == PT_SHAPE_VOLUME) ? d->transformed[j].shape_index : -1;
+        if (vj >= 0) H.volume_update.slots.push_back(VolLightSlot{vj, lit ? (int32_t)H.lights.size() : -1});
+        if (!lit) continue;
         DevLight L{};
         L.kind = k; L.mat = mat; L.phantom = 0;
         if (k == PT_SHAPE_SPHERE) {   // Sampler.cs:218-223
@@ -818,6 +823,8 @@ void Compiler::lights() {
         H.shape_refit.light_index.push_back(moves ? j : -1);
     }
     H.S.num_lights = (int32_t)H.lights.size();
+    H.volume_update.emittance.resize((size_t)std::max(d->num_materials, 0));
+    for (size_t i = 0; i < H.volume_update.emittance.size(); i++) H.volume_update.emittance[i] = d->materials[i].emittance;
 }
 
 // the traversal lines: [ana_nodes | tri_nodes | tri_chunks], 8 float4 per node / chunk; the statistics

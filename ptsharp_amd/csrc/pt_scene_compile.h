@@ -122,6 +122,14 @@ struct QueryTables {
 // shapes it uses; this reads nothing else).
 void query_tables(const pt_scene_desc* d, const std::vector<int32_t>& tri_group, QueryTables& Q);
 
+// What pt_update_volumes needs beside the device arrays: the light test's inputs.  (The volumes'
+// headers and window rows are HostScene::volumes and ::windows; the context keeps copies of those, never the grid.)
+struct VolumeTables {
+    std::vector<VolLightSlot> slots;   // every Scene.Shapes slot that is a Volume or a TransformedShape over one, and the
+                                       // HostScene::lights entry it registered (-1: none)
+    std::vector<double> emittance;     // per material of the scene (pt_scene_desc order)
+};
+
 // A compiled scene on the host: every array pt_upload_scene uploads, and the DevScene with every
 // non-pointer field filled.
 struct HostScene {
@@ -153,6 +161,7 @@ struct HostScene {
     ShapeRefitTables shape_refit;
     BlasRefitTables blas_refit;
     QueryTables query;
+    VolumeTables volume_update;
 };
 
 // Validates and compiles.  PT_OK, or an error code with its message in err (H is then partly filled; its

@@ -563,6 +563,103 @@ class Renderer:
                                                lights.ctypes.data_as(C.POINTER(C.c_double))), "pt_read_shape_bvh")
         return out[0], out[1], out[2], lights
 
+    def UpdateVolumes(self, updates, mirror=True) -> float:
+        """New voxels and new iso-windows for Volumes of the scene (pt_update_volumes).  `updates` maps a Volume
+        object, or its index among the compiled scene's volumes, to (data or None, windows or None): data holds
+        W*H*D float64 values in the Volume's own order (Data[x + y*W + z*W*H]); windows is one (lo, hi) pair, or a
+        VolumeWindow whose Lo and Hi are taken, per uploaded window (the materials stay).  The volume's derived tables
+        are rebuilt on the device; nothing else is re-sent or rebuilt, and a volume given windows only sends no
+        voxels.  With `mirror` the new Data, Lo and Hi are written into the Python Volume and the uploaded FlatScene,
+        so a later OracleScene(scene) or re-upload sees the same scene.  Returns the device time of the kernels in
+        ms."""
+        from .scene import VolumeWindow
+        self._ensure_scene()
+        flat = self._uploaded
+        nv = flat.counts_ext[2]
+        per = [None] * nv
+        for key, val in dict(updates).items():
+            if isinstance(key, (int, np.integer)):
+                idx = [int(key)]
+            else:
+                idx = [i for i, o in enumerate(flat.volume_objects) if o is key]
+            if not idx or min(idx) < 0 or max(idx) >= nv:
+                raise ValueError(f"{key!r} is not a Volume of the uploaded scene")
+            for i in idx:
+                per[i] = tuple(val)
+        u = _abi.pt_volume_update()
+        u.num_volumes = nv
+        dp = C.POINTER(C.c_double)
+        dptr = (dp * max(1, nv))()
+        wptr = (C.POINTER(_abi.pt_volume_window) * max(1, nv))()
+        staged = [None] * nv
+        for i, e in enumerate(per):
+            if e is None:
+                continue
+            data, windows = e
+            v, obj = flat.volumes[i], flat.volume_objects[i]
+            a = rows = wa = None
+            if data is not None:
+                a = np.ascontiguousarray(data, np.float64).reshape(-1)
+                if a.size != v.w * v.h * v.d:
+                    raise ValueError(f"volume {i} holds {v.w}x{v.h}x{v.d} voxels")
+                dptr[i] = a.ctypes.data_as(dp)
+            if windows is not None:
+                rows = []
+                for k, w in enumerate(windows):
+                    if isinstance(w, VolumeWindow):
+                        if k < len(obj.Windows) and w.VolumeWindowMaterial is not obj.Windows[k].VolumeWindowMaterial:
+                            raise ValueError(f"volume {i}, window {k}: the material of an uploaded window stays")
+                        rows.append((w.Lo, w.Hi))
+                    else:
+                        rows.append((float(w[0]), float(w[1])))
+                if len(rows) != v.num_windows:
+                    raise ValueError(f"volume {i} has {v.num_windows} windows")
+                wa = (_abi.pt_volume_window * max(1, len(rows)))()
+                for k, (lo, hi) in enumerate(rows):
+                    wa[k] = _abi.pt_volume_window(lo, hi, v.windows[k].material, 0)
+                wptr[i] = C.cast(wa, C.POINTER(_abi.pt_volume_window))
+            staged[i] = (a, rows, wa)
+        if any(s is not None and s[0] is not None for s in staged):
+            u.data = C.cast(dptr, C.POINTER(dp))
+        if any(s is not None and s[1] is not None for s in staged):
+            u.windows = C.cast(wptr, C.POINTER(C.POINTER(_abi.pt_volume_window)))
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_update_volumes(self._ctx, C.byref(u), C.byref(ms)), "pt_update_volumes")
+        if mirror:
+            for i, s in enumerate(staged):
+                if s is None:
+                    continue
+                a, rows, _ = s
+                obj = flat.volume_objects[i]
+                if a is not None:
+                    obj.Data[...] = a   # the array the FlatScene's pt_volume points at
+                if rows is not None:
+                    for k, (lo, hi) in enumerate(rows):
+                        obj.Windows[k].Lo, obj.Windows[k].Hi = lo, hi
+                        flat.volumes[i].windows[k].lo, flat.volumes[i].windows[k].hi = lo, hi
+        return float(ms.value)
+
+    def ReadVolume(self, i: int) -> dict:
+        """What the device holds for volume i (pt_read_volume): a dict with `info` (int64 [8]: w, h, d, windows,
+        zero_sign, has_cells, cells, 0), `data` [d, h, w] float64, `windows` [n, 2] float64 (lo, hi), `materials` [n]
+        int32, `runs` [d+1, h+1, w+1] int8 and `cells` [cells, 8] float64, or None for a volume without them."""
+        self._ensure_scene()
+        info = (C.c_int64 * 8)()
+        _abi.check(self._lib.pt_read_volume(self._ctx, int(i), info, None, None, None, None), "pt_read_volume")
+        w, h, d, nwin, _, has_cells, ncells = (int(x) for x in info[:7])
+        data = np.zeros((d, h, w), np.float64)
+        wins = (_abi.pt_volume_window * max(1, nwin))()
+        runs = np.zeros((d + 1, h + 1, w + 1), np.int8)
+        cells = np.zeros((ncells, 8), np.float64) if has_cells else None
+        dp = C.POINTER(C.c_double)
+        _abi.check(self._lib.pt_read_volume(self._ctx, int(i), info, data.ctypes.data_as(dp),
+                                            C.cast(wins, C.POINTER(_abi.pt_volume_window)),
+                                            runs.ctypes.data_as(C.POINTER(C.c_int8)),
+                                            cells.ctypes.data_as(dp) if has_cells else None), "pt_read_volume")
+        return {"info": np.array(list(info), np.int64), "data": data,
+                "windows": np.array([[wins[k].lo, wins[k].hi] for k in range(nwin)], np.float64).reshape(nwin, 2),
+                "materials": np.array([wins[k].material for k in range(nwin)], np.int32), "runs": runs, "cells": cells}
+
     def UpdateMeshes(self, v1, v2, v3, n1=None, n2=None, n3=None, normals=None) -> float:
         """UpdateTriangles for a scene that may hold instanced meshes (pt_update_meshes; UpdateTriangles refuses
         such a scene): new vertex positions for every triangle of the scene, instanced meshes' included, with the

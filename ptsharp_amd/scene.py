@@ -650,6 +650,7 @@ class FlatScene:
         mesh_first, mesh_count = [], []
         sdf_nodes, sdf_children, sdf_ids = [], [], {}
         sdf_shapes, volumes, vol_keep, xforms = [], [], [], []
+        vol_objs = []   # the Volume object of each entry of `volumes` (Renderer.UpdateVolumes' mirror)
         inner_meshes = {}
 
         def sdf_node(n) -> int:   # post-order: children before their parent
@@ -689,6 +690,7 @@ class FlatScene:
                 for k, w in enumerate(s.Windows):
                     wins[k] = _abi.pt_volume_window(w.Lo, w.Hi, mid(w.VolumeWindowMaterial), 0)
                 vol_keep.append((s.Data, wins))
+                vol_objs.append(s)
                 volumes.append(_abi.pt_volume(s.W, s.H, s.D, len(s.Windows), s.ZScale,
                                               s.Data.ctypes.data_as(C.POINTER(C.c_double)),
                                               C.cast(wins, C.POINTER(_abi.pt_volume_window)),
@@ -758,6 +760,7 @@ class FlatScene:
         self.sdf_nodes, self.sdf_children = arr(_abi.pt_sdf_node, sdf_nodes), np.array(sdf_children or [0], np.int32)
         self.sdf_shapes = arr(_abi.pt_sdf_shape, [_abi.pt_sdf_shape(r, m) for r, m in sdf_shapes])
         self.volumes, self._vol_keep = arr(_abi.pt_volume, volumes), vol_keep
+        self.volume_objects = vol_objs
         self.transformed = arr(_abi.pt_transformed_shape, xforms)
         self.counts_ext = (len(sdf_nodes), len(sdf_shapes), len(volumes), len(xforms))
         self.env_texture = tid(scene.Texture)
