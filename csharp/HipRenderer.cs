@@ -284,6 +284,10 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, ref pt_mesh_update u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, IntPtr u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_tri_bvh_cost(IntPtr ctx, double[] out3);
+        public const int PT_REBUILD_WORLD = 1, PT_REBUILD_BLAS = 2;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_blas(IntPtr ctx, ref pt_mesh_update u, int what, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_blas(IntPtr ctx, IntPtr u, int what, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_blas_cost(IntPtr ctx, int numBlas, double[] out3PerBlas);
         // new voxels and iso-windows for the scene's Volumes: their derived tables rebuilt on the device (DESIGN.md §4i)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_volumes(IntPtr ctx, ref pt_volume_update u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_volume(IntPtr ctx, int index, long[] info, double[] data, [In, Out] pt_volume_window[] windows, sbyte[] runs, double[] cells);
@@ -884,6 +888,58 @@ namespace PTSharpCore
         {
             PtHip.Check(PtHip.pt_rebuild_meshes(ctx, IntPtr.Zero, out double ms), "pt_rebuild_meshes");
             return ms;
+        }
+
+        /// <summary>UpdateMeshes that also re-sorts every instanced mesh's BLAS on the device into a balanced median
+        /// tree for the new positions (pt_rebuild_blas), and with PT_REBUILD_WORLD in <paramref name="what"/> (0: both)
+        /// the world triangle BVH as RebuildMeshes does.  A BLAS whose balanced tree needs more nodes than the upload
+        /// gave it is refitted instead.  Returns the device time of the kernels in ms.</summary>
+        public double RebuildBlas(float[] v1, float[] v2, float[] v3, float[] n1 = null, float[] n2 = null, float[] n3 = null,
+                                  int normalsMode = 0, int what = 0)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            IntPtr PinHeld(Array a)
+            {
+                if (a == null) return IntPtr.Zero;
+                var h = GCHandle.Alloc(a, GCHandleType.Pinned);
+                held.Add(h);
+                return h.AddrOfPinnedObject();
+            }
+            try
+            {
+                var u = new PtHip.pt_mesh_update
+                {
+                    num_triangles = v1.Length / 3, normals_mode = normalsMode,
+                    v1 = PinHeld(v1), v2 = PinHeld(v2), v3 = PinHeld(v3), n1 = PinHeld(n1), n2 = PinHeld(n2), n3 = PinHeld(n3),
+                };
+                PtHip.Check(PtHip.pt_rebuild_blas(ctx, ref u, what, out double ms), "pt_rebuild_blas");
+                return ms;
+            }
+            finally
+            {
+                foreach (var h in held) h.Free();
+            }
+        }
+
+        /// <summary>RebuildBlas from the pose the last PoseMeshes left staged on the device: nothing is copied.</summary>
+        public double RebuildBlas(int what = 0)
+        {
+            PtHip.Check(PtHip.pt_rebuild_blas(ctx, IntPtr.Zero, what, out double ms), "pt_rebuild_blas");
+            return ms;
+        }
+
+        /// <summary>The surface-area cost of every BLAS as it stands (pt_blas_cost): per BLAS the inner cost and the
+        /// leaf cost relative to its root box's area, and that area.  Its growth since the upload tells when
+        /// RebuildBlas pays.</summary>
+        public double[] BlasCost()
+        {
+            if (!uploaded) Upload();
+            var counts = new long[3];
+            PtHip.Check(PtHip.pt_read_blas(ctx, counts, null, null, null, null, null), "pt_read_blas");
+            var o = new double[Math.Max(1, counts[0] * 3)];
+            PtHip.Check(PtHip.pt_blas_cost(ctx, (int)counts[0], o), "pt_blas_cost");
+            return o;
         }
 
         /// <summary>New voxels and new iso-windows for the Volumes of the uploaded scene, in the upload's volume order

@@ -30,6 +30,8 @@
  *   / pt_tri_bvh_cost  triangle BVH into a balanced median tree on the device  builds a new tree for every frame's scene)
  *                      for the new positions; the SAH cost of the tree as it
  *                      stands, the host's trigger for "refit or rebuild"
+ *   pt_rebuild_blas    (new) the same for every instanced mesh's BLAS, and    Mesh.Compile under TransformedShape,
+ *   / pt_blas_cost     the cost of each BLAS as it stands                     Mesh.cs / TransformedShape.cs
  *   pt_update_volumes  (new) new voxels and iso-windows for the scene's         Volume.NewVolume, Volume.cs:48-71, and
  *   / pt_read_volume   Volumes: their derived tables rebuilt on the device      VolumeWindow, Volume.cs:8-19
  *   pt_render_pass    one Renderer.RenderParallel() pass                  Renderer.cs:199-338
@@ -781,8 +783,9 @@ int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n
  * synchronises before returning; out_kernel_ms (may be NULL) covers every kernel of the call.  Non-finite positions:
  * the order is unspecified, still a permutation; no access leaves its array.
  * Errors (nothing launched, the scene untouched): those of pt_update_meshes (u == NULL without a staged pose:
- * PT_ERR_INVALID_ARG); a scene with an instanced mesh, whose BLAS is not rebuilt: PT_ERR_UNSUPPORTED; more than 9
- * levels, or more node and chunk lines together than the upload allocated (nodes and chunks share one run of lines,
+ * PT_ERR_INVALID_ARG); a scene with an instanced mesh, whose BLAS is not rebuilt: PT_ERR_UNSUPPORTED (pt_rebuild_blas
+ * below serves such a scene); more than 9 levels, or more node and chunk lines together than the upload allocated
+ * (nodes and chunks share one run of lines,
  * so a tree with more nodes than the uploaded one starts its chunks later; short only when the uploaded tree was
  * within a few lines of perfectly full): PT_ERR_UNSUPPORTED; the workspace (about 130 B per triangle, kept until the
  * next upload) not allocated: PT_ERR_OUT_OF_MEMORY.  A scene with no triangle in the BVH: PT_OK, nothing launched. */
@@ -793,6 +796,39 @@ int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms)
  * the device.  No triangle in the BVH (or A == 0): zeros.  Synchronises and changes nothing.  A NULL argument:
  * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_tri_bvh_cost(void* ctx, double out[3]);
+
+/* Re-sorting instanced meshes' BLASes on the device.  pt_rebuild_blas takes pt_update_meshes' struct and
+ * does everything that call does (positions; normals given, kept or derived; u == NULL: the staged pose, as
+ * pt_rebuild_meshes takes it), and re-sorts what `what` names: PT_REBUILD_WORLD the world triangle BVH, exactly as
+ * pt_rebuild_meshes does (its refusals for too many levels or lines included; on a scene without an instanced mesh the
+ * device then holds, word for word, what pt_rebuild_meshes leaves), PT_REBUILD_BLAS every BLAS, 0 both.  A BLAS of n
+ * triangles gets a balanced object-median BVH4 whose shape depends on n alone: leaves of four consecutive positions,
+ * h = the least integer >= 1 with 4 * 4^h >= n levels of nodes that group 4 consecutive leaves, then 4 consecutive nodes,
+ * numbered level by level from the root; the order comes from 2 h rounds of stable sorts of ever halved position
+ * segments, by pt_rebuild_meshes' key and axis rule (pt_blas_rebuild.h states it exactly).  Then pt_update_meshes' BLAS
+ * refit and pt_update_shapes' refit run over the new order.  A BLAS whose balanced tree needs more nodes than the upload
+ * gave it is refitted, not rebuilt: it keeps its topology and order, the call still succeeds.  pt_read_blas' node count
+ * of a rebuilt BLAS becomes the new tree's and stays for a kept one; counts[1] and every offset stay, lines past a
+ * BLAS's new count are left as they are.  A scene whose only triangles are instanced launches nothing for the world.
+ * Afterwards every ray query, feature pass and render pass sees what a fresh pt_upload_scene with these arrays and the
+ * current shape parameters would see, up to the exact-t tie order of DESIGN.md §5; pt_intersect_hits' identities stay
+ * the source numbering; every later pt_update_meshes, pt_pose_meshes and pt_read_blas works on the new topology.
+ * Stream order, synchronisation, out_kernel_ms, the Buffer, pass state, counters and non-finite inputs are as for
+ * pt_rebuild_meshes.  PT_BLAS_TAIL in the environment, read at each call, sizes the segments one workgroup finishes in
+ * LDS (0: none, every round a device sort; else the largest 4 * 4^k in [64, 1024] it holds); the words left on the
+ * device do not depend on it.
+ * Errors (nothing launched, the scene untouched): those of pt_update_meshes (u == NULL without a staged pose:
+ * PT_ERR_INVALID_ARG); `what` outside 0..3: PT_ERR_INVALID_ARG; a BLAS of more than 10 levels: PT_ERR_UNSUPPORTED; a
+ * workspace (about 100 B per BLAS triangle, kept until the next upload) not allocated: PT_ERR_OUT_OF_MEMORY. */
+#define PT_REBUILD_WORLD 1 /* what pt_rebuild_meshes re-sorts */
+#define PT_REBUILD_BLAS 2  /* every BLAS */
+int pt_rebuild_blas(void* ctx, const pt_mesh_update* u, int32_t what, double* out_kernel_ms);
+/* pt_tri_bvh_cost for each BLAS, from the BVH4 node words as they stand (plain fp32 child boxes, widened to fp64):
+ * with A = the area of the union of the root's slot boxes, out[3 b] = (A + the area of every inner slot) / A,
+ * out[3 b + 1] = the area of every leaf slot / A, out[3 b + 2] = A; A == 0: zeros.  Summed on the device, per BLAS in a
+ * fixed order.  num_blas must equal pt_read_blas' counts[0].  Synchronises and changes nothing.  A NULL argument or a
+ * wrong count: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+int pt_blas_cost(void* ctx, int32_t num_blas, double* out /* [num_blas][3] */);
 
 /* New voxels and new iso-windows for the Volumes of the uploaded scene: what a user edits
  * interactively (an iso-window dragged to another tissue, the next grid of a time series), without the re-upload

@@ -36,6 +36,7 @@ SHAPE_SPHERE, SHAPE_CUBE, SHAPE_PLANE, SHAPE_TRIANGLE, SHAPE_MESH = 0, 1, 2, 3, 
 SHAPE_SDF, SHAPE_VOLUME, SHAPE_TRANSFORMED = 5, 6, 7
 MARCH_LANE, MARCH_WAVE = 1, 2   # pt_intersect / pt_occluded flags (PT_MARCH_*)
 NORMALS_FACE, NORMALS_SMOOTH = 1, 2   # pt_normals_mode (pt_update_triangles_normals)
+REBUILD_WORLD, REBUILD_BLAS = 1, 2    # pt_rebuild_blas' `what`
 
 _f = C.POINTER(C.c_float)
 _d = C.POINTER(C.c_double)
@@ -205,6 +206,8 @@ SIGNATURES = {
     "pt_read_pose": (C.c_int, [C.c_void_p, _f, _f, _f, _f, _f, _f]),
     "pt_rebuild_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_update), _d]),
     "pt_tri_bvh_cost": (C.c_int, [C.c_void_p, _d]),
+    "pt_rebuild_blas": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_update), C.c_int32, _d]),
+    "pt_blas_cost": (C.c_int, [C.c_void_p, C.c_int32, _d]),
     "pt_update_volumes": (C.c_int, [C.c_void_p, C.POINTER(pt_volume_update), _d]),
     "pt_read_volume": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _d, C.POINTER(pt_volume_window),
                                  C.POINTER(C.c_int8), _d]),

@@ -24,6 +24,7 @@
 
 #include "../../include/ptsharp_hip.h"
 #include "pt_blas_refit.h"
+#include "pt_blas_rebuild.h"
 #include "pt_bvh.h"
 #include "pt_device.h"
 #include "pt_math.h"
@@ -133,6 +134,16 @@ hipError_t launch_rebuild(const RebuildPlan& R, void* ws, size_t temp_bytes, uin
                           hipStream_t stream);
 hipError_t bvh_cost_workspace_bytes(int64_t num_nodes, size_t* bytes);
 hipError_t launch_bvh_cost(int64_t num_nodes, const uint32_t* nodes, void* ws, double* sums, hipStream_t stream);
+// pt_blas_rebuild.hip
+int64_t blas_tail_max();
+hipError_t blas_rebuild_workspace_bytes(int64_t num_blas, int64_t P, size_t* temp_bytes, size_t* bytes);
+hipError_t blas_rebuild_upload(void* ws, size_t temp_bytes, int64_t num_blas, int64_t P, const int32_t* pos_blas, hipStream_t stream);
+hipError_t launch_blas_rebuild(void* ws, size_t temp_bytes, int64_t num_blas, int64_t P, int64_t total_nodes, const int32_t* items,
+                               const int32_t* tail, int64_t num_tail, int64_t tail_T, uint32_t* nodes, uint32_t* shade, uint32_t* uv,
+                               int32_t* src_of_pos, const float* v1, const float* v2, const float* v3, hipStream_t stream);
+size_t blas_cost_workspace_bytes(int64_t total_nodes);
+hipError_t launch_blas_cost(int64_t num_blas, int64_t total_nodes, int64_t max_nodes, const int32_t* desc, const uint32_t* nodes,
+                            void* ws, double* out, hipStream_t stream);
 // pt_pose.hip
 hipError_t launch_pose(int64_t n, int32_t num_meshes, const int32_t* group, const int32_t* mask, const double* matrices,
                        bool normals, const float* const rest[6], float* const out[6], hipStream_t stream);
@@ -233,6 +244,14 @@ struct SceneDyn {
     Workspace<RebuildDev> rebuild_ws;       // first pt_rebuild_meshes
     Workspace<pt::QueryDev> query_ws;       // first pt_intersect_hits: its own copies of the identity tables
     bool query_src_stale = false;           // a pt_rebuild_meshes permuted refit.src_of_pos after query_ws took its copy
+    // pt_rebuild_blas: its workspace (carved by pt_blas_rebuild.hip), the upload's DevBlas rows with the
+    // node counts the device holds now, the node count the upload gave each BLAS, and the host tables its copies are
+    // issued from (they live until the call's synchronisation)
+    Workspace<RebuildDev> blas_rebuild_ws;   // first pt_rebuild_blas on instanced meshes
+    std::vector<pt::DevBlas> h_blas;
+    std::vector<int32_t> blas_node_cap;
+    std::vector<int32_t> blas_items, blas_tail, blas_pos;
+    bool query_blas_src_stale = false;       // a pt_rebuild_blas permuted blas_refit.src_of_pos after query_ws took its copy
     // pt_set_rest_pose: the rest vertices of the lights that are loose triangles, 9 floats per h_lights entry
     std::vector<float> rest_light_verts;
     bool pose_staged = false;            // refit_ws' staged arrays hold the last pt_pose_meshes' (pt_read_pose)
@@ -244,6 +263,7 @@ struct SceneDyn {
         blas_ws.release();
         pose_ws.release();
         rebuild_ws.release();
+        blas_rebuild_ws.release();
         query_ws.release();
     }
 };
@@ -698,6 +718,8 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     c->dyn.query = std::move(H.query);
     c->dyn.h_lights = std::move(H.lights);
     c->dyn.has_blas = !H.blas.empty();
+    c->dyn.h_blas = H.blas;
+    for (const pt::DevBlas& b : H.blas) c->dyn.blas_node_cap.push_back(b.num_nodes);
     c->dyn.volume_update = std::move(H.volume_update);
     c->dyn.vols = std::move(vols);
     c->dyn.vol_windows = std::move(H.windows);
@@ -1483,6 +1505,72 @@ int blas_refit_finish(Ctx* c) {
     return PT_OK;
 }
 
+// ---- pt_rebuild_blas' part for instanced meshes
+// PT_BLAS_TAIL, read at each call (tests set it): 0 switches the LDS tail off, else the largest 4 * 4^k in [64, the
+// kernel's] that the value holds
+int64_t blas_tail_knob() {
+    const int64_t most = pt::blas_tail_max();
+    const char* e = std::getenv("PT_BLAS_TAIL");
+    if (!e || !*e) return most;
+    const int64_t v = (int64_t)std::atoll(e);
+    if (v <= 0) return 0;
+    int64_t t = 64;
+    while (t * 4 <= v && t * 4 <= most) t *= 4;
+    return t;
+}
+// The plan of every BLAS and the fallback decision, then the workspace: before anything is staged.  A BLAS whose
+// balanced tree needs more nodes than the upload gave it keeps its topology (h == 0 in its item).
+int blas_rebuild_prepare(Ctx* c) {
+    SceneDyn& Y = c->dyn;
+    const pt::BlasRefitTables& T = Y.blas_refit;
+    const size_t nb = T.num_blas();
+    std::vector<int32_t> items;
+    size_t refused = 0;
+    if (!pt::blas_rebuild_items(T, Y.blas_node_cap, items, &refused))
+        return fail(PT_ERR_UNSUPPORTED, "rebuild blas: " + std::to_string(T.desc[4 * refused + 3]) + " triangles need more than " +
+                                            std::to_string(pt::kBlasRebuildMaxLevels) + " levels");
+    RebuildDev sized{};   // pt_blas_rebuild.hip sizes and carves this one
+    if (!Y.blas_rebuild_ws.mem.ptr) {
+        PT_HIP(pt::blas_rebuild_workspace_bytes((int64_t)nb, T.num_tris, &sized.temp_bytes, &sized.bytes));
+        Y.blas_pos.assign((size_t)T.num_tris, -1);
+        for (size_t b = 0; b < nb; b++)
+            for (int64_t q = 0; q < T.desc[4 * b + 3]; q++) {
+                const int64_t p = (int64_t)T.desc[4 * b + 2] + q;
+                if (p >= 0 && p < T.num_tris) Y.blas_pos[(size_t)p] = (int32_t)b;
+            }
+    }
+    if (const int rc = ensure_workspace(c, Y.blas_rebuild_ws, "BLAS rebuild", [&](void*) { return sized; },
+                                        [&](const RebuildDev& D, Uploader& up) {   // each position's BLAS
+                                            up.err = pt::blas_rebuild_upload(Y.blas_rebuild_ws.mem.ptr, D.temp_bytes, (int64_t)nb,
+                                                                             T.num_tris, Y.blas_pos.data(), c->stream);
+                                        }))
+        return rc;
+    Y.blas_items = std::move(items);
+    return PT_OK;
+}
+// The re-sort and the new topologies on the context's stream, before blas_refit_launch, and what follows from the new
+// node counts: the host tables (desc, the level lists) and their device copies, the DevBlas rows
+int blas_rebuild_launch(Ctx* c, const float* const in[6]) {
+    SceneDyn& Y = c->dyn;
+    pt::BlasRefitTables& T = Y.blas_refit;
+    const pt::BlasDev& D = Y.blas_ws.at;
+    const size_t nb = T.num_blas();
+    const int64_t tail_T = blas_tail_knob();
+    pt::blas_tail_table(Y.blas_items.data(), (int64_t)nb, tail_T, Y.blas_tail);
+    PT_HIP(pt::launch_blas_rebuild(Y.blas_rebuild_ws.mem.ptr, Y.blas_rebuild_ws.at.temp_bytes, (int64_t)nb, T.num_tris, T.num_nodes,
+                                   Y.blas_items.data(), Y.blas_tail.data(), (int64_t)Y.blas_tail.size() / 4, tail_T,
+                                   (uint32_t*)const_cast<float4*>(c->S.blas_nodes), (uint32_t*)const_cast<float4*>(c->S.blas_shade),
+                                   (uint32_t*)const_cast<float4*>(c->S.blas_uv), D.src_of_pos, in[0], in[1], in[2], c->stream));
+    pt::blas_rebuild_tables(T, Y.blas_items);
+    for (size_t b = 0; b < nb && b < Y.h_blas.size(); b++) Y.h_blas[b].num_nodes = T.desc[4 * b + 1];
+    Uploader up{c->stream};
+    up(D.desc, T.desc);
+    up(D.level_nodes, T.level_nodes);   // no longer than the upload's lists: a rebuilt BLAS has no more nodes than it had
+    up(D.level_blas, T.level_blas);
+    up(const_cast<pt::DevBlas*>(c->S.blas), Y.h_blas);
+    return check_hip(up.err, "the rebuilt BLAS tables");
+}
+
 // ---- moving triangles: the path every triangle update takes
 int ensure_refit_ws(Ctx* c) {
     const pt::RefitTables& T = c->dyn.refit;
@@ -1512,6 +1600,7 @@ struct UpdateCall {
     const float* light_verts[3];   // the vertices of the lights that are loose emissive triangles: the caller's v1, v2, v3
                                    // (pt_scene_desc order), or NULL: the rest vertices pt_set_rest_pose kept
     const RebuildRun* rebuild;     // pt_rebuild_meshes: re-sorted before the refit (NULL: the topology stays)
+    bool rebuild_blas = false;     // pt_rebuild_blas: every BLAS re-sorted before its refit (blas_rebuild_prepare planned it)
 };
 // Whether the scene's instanced meshes take part in an update (update_prepare refused it for an entry point that
 // does not refit them)
@@ -1594,6 +1683,7 @@ int update_run(Ctx* c, const UpdateCall& U, double* out_kernel_ms) {
     PT_HIP(pt::launch_refit(T.num_chunks, (int64_t)T.level_off.size() - 1, T.level_off.data(), D.level_nodes, nodes,
                             (uint32_t*)const_cast<float4*>(c->S.tri_chunks), (uint32_t*)const_cast<float4*>(c->S.tri_recs),
                             D.src_of_pos, in[0], in[1], in[2], in[3], in[4], in[5], D.node_box, D.chunk_box, c->stream));
+    if (U.rebuild_blas && refits_blas(c, U)) if (const int rc = blas_rebuild_launch(c, in)) return rc;
     if (refits_blas(c, U)) if (const int rc = blas_refit_launch(c, U.num_triangles, in)) return rc;
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     // the root box follows (pt_wavefront.hip's refill kernels skip the triangle phase of a ray that misses it)
@@ -1602,6 +1692,11 @@ int update_run(Ctx* c, const UpdateCall& U, double* out_kernel_ms) {
     if (U.rebuild) {
         PT_HIP(hipMemcpyAsync(T.src_of_pos.data(), D.src_of_pos, T.src_of_pos.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         Y.query_src_stale = true;   // pt_intersect_hits' copy follows at its next call
+    }
+    if (U.rebuild_blas && refits_blas(c, U)) {
+        std::vector<int32_t>& src = Y.blas_refit.src_of_pos;
+        PT_HIP(hipMemcpyAsync(src.data(), Y.blas_ws.at.src_of_pos, src.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        Y.query_blas_src_stale = true;
     }
     // lights that are loose emissive triangles: their sphere from the new vertices
     bool lights_moved = false;
@@ -1796,7 +1891,59 @@ int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n
     return PT_OK;
 }
 
-// ---- re-sorting the triangle BVH on the device
+}  // extern "C"
+
+// ---- re-sorting the triangle BVH on the device, and the BLASes (§4j)
+namespace {
+// The world tree's new topology, checked against what the upload allocated, and the rebuild workspace: before anything
+// is staged.  `who` starts the messages.
+int rebuild_world_prepare(Ctx* c, const std::string& who, RebuildRun& run) {
+    SceneDyn& Y = c->dyn;
+    pt::RebuildPlan& R = run.R;
+    const int64_t P = (int64_t)Y.refit.src_of_pos.size();
+    if (!pt::rebuild_plan(P, R) || pt::rebuild_stack_bound(R) > pt::kStackMax)
+        return fail(PT_ERR_UNSUPPORTED, who + ": " + std::to_string(P) + " triangles need more than " +
+                                            std::to_string(pt::kRebuildMaxLevels) + " levels");
+    const int64_t node_cap = (int64_t)c->S.tri_chunk_line0 - (int64_t)c->S.tri_node_line0;
+    const int64_t chunk_cap = (int64_t)c->S.lines_n - (int64_t)c->S.tri_chunk_line0;
+    if (R.num_nodes + R.num_chunks > node_cap + chunk_cap)
+        return fail(PT_ERR_UNSUPPORTED, who + ": the balanced tree needs " + std::to_string(R.num_nodes) + " nodes and " +
+                                            std::to_string(R.num_chunks) + " chunks, the upload allocated " +
+                                            std::to_string(node_cap + chunk_cap) + " lines");
+    run.chunk_line0 = R.num_nodes <= node_cap && R.num_chunks <= chunk_cap ? c->S.tri_chunk_line0
+                                                                            : c->S.tri_node_line0 + (uint32_t)R.num_nodes;
+    RebuildDev sized{};   // pt_rebuild.hip sizes and carves this one: nothing to lay out or upload here
+    if (!Y.rebuild_ws.mem.ptr) PT_HIP(pt::rebuild_workspace_bytes(P, &sized.temp_bytes, &sized.bytes));
+    return ensure_workspace(c, Y.rebuild_ws, "rebuild", [&](void*) { return sized; }, [](const RebuildDev&, Uploader&) {});
+}
+
+// pt_rebuild_meshes and pt_rebuild_blas after their own argument checks: world / blas say which trees are re-sorted
+int rebuild_call(Ctx* c, const std::string& who, const pt_mesh_update* u, bool world, bool blas, double* out_kernel_ms) {
+    SceneDyn& Y = c->dyn;
+    // u NULL: the staged pose with its normals, the lights at their rest vertices
+    RebuildRun run{};
+    UpdateCall U{Y.refit.num_triangles, Normals::Given, {nullptr, nullptr, nullptr}, nullptr};
+    if (u) U = UpdateCall{u->num_triangles, normals_of(u->normals_mode, u->n1), {u->v1, u->v2, u->v3}, nullptr};
+    bool launch = false;
+    if (const int rc = update_prepare(c, U, true, out_kernel_ms, &launch)) return rc;
+    if (!launch) return PT_OK;
+    // the new topologies and the workspaces: before anything is staged
+    if (world && Y.refit.num_chunks > 0) {   // a scene whose only triangles are instanced launches nothing for the world
+        if (const int rc = rebuild_world_prepare(c, who, run)) return rc;
+        U.rebuild = &run;
+    }
+    if (blas && refits_blas(c, U)) {
+        if (const int rc = blas_rebuild_prepare(c)) return rc;
+        U.rebuild_blas = true;
+    }
+    const float* const src[6] = {u ? u->v1 : nullptr, u ? u->v2 : nullptr, u ? u->v3 : nullptr, u ? u->n1 : nullptr,
+                                 u ? u->n2 : nullptr, u ? u->n3 : nullptr};
+    return update_stage_and_run(c, U, u ? src : nullptr, out_kernel_ms);
+}
+}  // namespace
+
+extern "C" {
+
 int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
@@ -1808,34 +1955,55 @@ int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms)
     if (Y.has_blas)
         return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
                                         "BLASes are not rebuilt");
-    // u NULL: the staged pose with its normals, the lights at their rest vertices
-    RebuildRun run{};
-    UpdateCall U{Y.refit.num_triangles, Normals::Given, {nullptr, nullptr, nullptr}, &run};
-    if (u) U = UpdateCall{u->num_triangles, normals_of(u->normals_mode, u->n1), {u->v1, u->v2, u->v3}, &run};
-    bool launch = false;
-    if (const int rc = update_prepare(c, U, false, out_kernel_ms, &launch)) return rc;
-    if (!launch) return PT_OK;
-    // the new topology, checked against what the upload allocated, and the workspace: before anything is staged
-    pt::RebuildPlan& R = run.R;
-    const int64_t P = (int64_t)Y.refit.src_of_pos.size();
-    if (!pt::rebuild_plan(P, R) || pt::rebuild_stack_bound(R) > pt::kStackMax)
-        return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: " + std::to_string(P) + " triangles need more than " +
-                                            std::to_string(pt::kRebuildMaxLevels) + " levels");
-    const int64_t node_cap = (int64_t)c->S.tri_chunk_line0 - (int64_t)c->S.tri_node_line0;
-    const int64_t chunk_cap = (int64_t)c->S.lines_n - (int64_t)c->S.tri_chunk_line0;
-    if (R.num_nodes + R.num_chunks > node_cap + chunk_cap)
-        return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: the balanced tree needs " + std::to_string(R.num_nodes) + " nodes and " +
-                                            std::to_string(R.num_chunks) + " chunks, the upload allocated " +
-                                            std::to_string(node_cap + chunk_cap) + " lines");
-    run.chunk_line0 = R.num_nodes <= node_cap && R.num_chunks <= chunk_cap ? c->S.tri_chunk_line0
-                                                                            : c->S.tri_node_line0 + (uint32_t)R.num_nodes;
-    RebuildDev sized{};   // pt_rebuild.hip sizes and carves this one: nothing to lay out or upload here
-    if (!Y.rebuild_ws.mem.ptr) PT_HIP(pt::rebuild_workspace_bytes(P, &sized.temp_bytes, &sized.bytes));
-    if (const int rc = ensure_workspace(c, Y.rebuild_ws, "rebuild", [&](void*) { return sized; }, [](const RebuildDev&, Uploader&) {}))
-        return rc;
-    const float* const src[6] = {u ? u->v1 : nullptr, u ? u->v2 : nullptr, u ? u->v3 : nullptr, u ? u->n1 : nullptr,
-                                 u ? u->n2 : nullptr, u ? u->n3 : nullptr};
-    return update_stage_and_run(c, U, u ? src : nullptr, out_kernel_ms);
+    return rebuild_call(c, "rebuild meshes", u, true, false, out_kernel_ms);
+}
+
+int pt_rebuild_blas(void* ctx, const pt_mesh_update* u, int32_t what, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (u) if (const int rc = check_mesh_update("rebuild blas", u)) return rc;
+    if (what < 0 || what > (PT_REBUILD_WORLD | PT_REBUILD_BLAS))
+        return fail(PT_ERR_INVALID_ARG, "rebuild blas: what " + std::to_string(what) + " is not 0 or PT_REBUILD_WORLD | PT_REBUILD_BLAS");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    if (!u && (!Y.pose_staged || !Y.refit_ws.mem.ptr))
+        return fail(PT_ERR_INVALID_ARG, "rebuild blas: u is NULL and the staged arrays hold no pose (pt_pose_meshes)");
+    if (what == 0) what = PT_REBUILD_WORLD | PT_REBUILD_BLAS;
+    return rebuild_call(c, "rebuild blas", u, (what & PT_REBUILD_WORLD) != 0, (what & PT_REBUILD_BLAS) != 0, out_kernel_ms);
+}
+
+int pt_blas_cost(void* ctx, int32_t num_blas, double* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!out && num_blas != 0) return fail(PT_ERR_INVALID_ARG, "blas cost: out is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::BlasRefitTables& T = c->dyn.blas_refit;
+    const size_t nb = T.num_blas();
+    if (num_blas < 0 || (size_t)num_blas != nb)
+        return fail(PT_ERR_INVALID_ARG, "blas cost: num_blas is " + std::to_string(num_blas) + ", the uploaded scene has " +
+                                            std::to_string(nb));
+    if (nb == 0) return PT_OK;
+    PT_HIP(hipSetDevice(c->device));
+    // [inner | leaf | out | desc]
+    const size_t arrays = pt::blas_cost_workspace_bytes(T.num_nodes), out_bytes = nb * 3 * sizeof(double);
+    DeviceArray ws;
+    if (hipMalloc(&ws.ptr, arrays + out_bytes + nb * 4 * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, "blas cost workspace allocation");
+    }
+    double* d_out = (double*)((char*)ws.ptr + arrays);
+    int32_t* d_desc = (int32_t*)((char*)ws.ptr + arrays + out_bytes);
+    int64_t max_nodes = 0;
+    for (size_t b = 0; b < nb; b++) max_nodes = std::max(max_nodes, (int64_t)T.desc[4 * b + 1]);
+    hipError_t e = hipStreamSynchronize(c->side);   // after every pass issued before
+    if (e == hipSuccess) e = hipMemcpyAsync(d_desc, T.desc.data(), nb * 4 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = pt::launch_blas_cost((int64_t)nb, T.num_nodes, max_nodes, d_desc, (const uint32_t*)c->S.blas_nodes, ws.ptr, d_out, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    ws.release();
+    PT_HIP(e);
+    return PT_OK;
 }
 
 int pt_tri_bvh_cost(void* ctx, double out[3]) {
@@ -2094,7 +2262,13 @@ int ensure_query_ws(Ctx* c) {
         up(Y.query_ws.at.tri_src, Y.refit.src_of_pos);
         if (const int rc = check_hip(up.err, "query: the rebuilt triangle order")) return rc;
     }
+    if (!first && Y.query_blas_src_stale) {
+        Uploader up{c->stream};
+        up(Y.query_ws.at.blas_src, Y.blas_refit.src_of_pos);
+        if (const int rc = check_hip(up.err, "query: the rebuilt BLAS order")) return rc;
+    }
     Y.query_src_stale = false;
+    Y.query_blas_src_stale = false;
     return PT_OK;
 }
 

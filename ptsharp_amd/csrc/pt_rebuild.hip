@@ -181,6 +181,14 @@ static RebuildDev rebuild_layout(int64_t P, size_t temp_bytes, void* base) {
     return r;
 }
 
+// k_rebuild_tri_keys on `stream` (pt_blas_rebuild.hip forms the keys of the BLAS positions with it)
+hipError_t launch_rebuild_tri_keys(int64_t P, const int32_t* src_of_pos, const float* v1, const float* v2, const float* v3,
+                                   uint32_t* keys3, uint32_t* vals, hipStream_t stream) {
+    if (P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rebuild_tri_keys, rebuild_blocks(P), dim3(kRebuildBlock), 0, stream, P, src_of_pos, v1, v2, v3, keys3, vals);
+    return hipGetLastError();
+}
+
 // The sort's temporary for P pairs, and the whole workspace's size with it.
 hipError_t rebuild_workspace_bytes(int64_t P, size_t* temp_bytes, size_t* bytes) {
     *temp_bytes = 0;
@@ -207,9 +215,7 @@ hipError_t launch_rebuild(const RebuildPlan& R, void* ws, size_t temp_bytes, uin
     rocprim::double_buffer<uint64_t> keys(D.keys[0], D.keys[1]);
     rocprim::double_buffer<uint32_t> vals(D.vals[0], D.vals[1]);
     hipError_t e;
-    hipLaunchKernelGGL(k_rebuild_tri_keys, rebuild_blocks(P), dim3(kRebuildBlock), 0, stream, P, src_of_pos, v1, v2, v3, D.keys3,
-                       vals.current());
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_rebuild_tri_keys(P, src_of_pos, v1, v2, v3, D.keys3, vals.current(), stream)) != hipSuccess) return e;
     for (int r = 1; r <= rebuild_rounds(R); r++) {
         if (!rebuild_round_sorts(R, r)) continue;
         const int shift = rebuild_shift(R, r);

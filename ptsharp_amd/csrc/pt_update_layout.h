@@ -1,7 +1,8 @@
-// pt_update_layout.h — how the moving-geometry entry points (pt_api.hip, DESIGN.md §4c-§4g) carve their per-scene
-// device workspaces: one allocation each, its parts 256-B aligned and in the order listed.  Host code only: no HIP
-// call, compiles with g++ (tests/native/rebuild_check.cpp, blas_check.cpp and shapes_check.cpp check the layouts
-// against what the kernels index).  With a null base the pointers are the parts' offsets.
+// pt_update_layout.h — how the moving-geometry entry points (pt_api.hip, DESIGN.md §4c-§4j) carve their per-scene
+// device workspaces: one allocation each, its parts 256-B aligned and in the order listed; and pt_rebuild_blas' host
+// tables (its plans, level lists and tail workgroups).  Host code only: no HIP call, compiles with g++
+// (tests/native/rebuild_check.cpp, blas_check.cpp, shapes_check.cpp and blas_rebuild_check.cpp check the layouts and
+// tables against what the kernels index).  With a null base the pointers are the parts' offsets.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -9,6 +10,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "pt_blas_rebuild.h"
+#include "pt_bvh.h"
 #include "pt_rebuild.h"
 #include "pt_scene_compile.h"
 
@@ -164,6 +167,86 @@ inline BlasDev blas_layout(const BlasRefitTables& T, size_t num_blocks, void* ba
     r.num_blocks = num_blocks;
     r.bytes = c.bytes();
     return r;
+}
+
+// pt_rebuild_blas' plan for the BLASes of T: four int32 per BLAS (pt_blas_rebuild.hip BlasRbItem: rec_off, n, h,
+// node_off), h == 0 for a BLAS that keeps its topology: an empty one, or one whose balanced tree needs more nodes than
+// node_cap[b], the count the upload gave it.  false: BLAS *refused needs more than kBlasRebuildMaxLevels levels.
+inline bool blas_rebuild_items(const BlasRefitTables& T, const std::vector<int32_t>& node_cap, std::vector<int32_t>& items,
+                               size_t* refused) {
+    const size_t nb = T.num_blas();
+    items.assign(4 * nb, 0);
+    for (size_t b = 0; b < nb; b++) {
+        const int32_t n = T.desc[4 * b + 3];
+        BlasPlan R;
+        if (!blas_rebuild_plan(n, R) || blas_rebuild_stack_bound(R) > kStack4Budget) { *refused = b; return false; }
+        const bool fits = n > 0 && b < node_cap.size() && R.num_nodes <= (int64_t)node_cap[b];
+        items[4 * b] = T.desc[4 * b + 2];
+        items[4 * b + 1] = n;
+        items[4 * b + 2] = fits ? R.h : 0;
+        items[4 * b + 3] = T.desc[4 * b];
+    }
+    return true;
+}
+// What follows in T from the new topologies: a rebuilt BLAS's node count (desc) and its levels from its plan, a kept
+// one's as they were.  The lists never grow: a rebuilt BLAS has no more nodes than the upload gave it.
+inline void blas_rebuild_tables(BlasRefitTables& T, const std::vector<int32_t>& items) {
+    const size_t nb = T.num_blas();
+    std::vector<std::vector<std::vector<uint32_t>>> kept(nb);   // [BLAS][level] -> its nodes
+    for (size_t l = 0; l + 1 < T.level_off.size(); l++)
+        for (uint32_t q = T.level_off[l]; q < T.level_off[l + 1]; q++) {
+            const size_t b = (size_t)T.level_blas[q];
+            if (b >= nb || items[4 * b + 2] > 0) continue;
+            if (kept[b].size() <= l) kept[b].resize(l + 1);
+            kept[b][l].push_back(T.level_nodes[q]);
+        }
+    size_t depth = 0;
+    std::vector<BlasPlan> plans(nb);
+    for (size_t b = 0; b < nb; b++) {
+        const int32_t h = items[4 * b + 2];
+        if (h > 0) {
+            blas_rebuild_plan(T.desc[4 * b + 3], plans[b]);
+            T.desc[4 * b + 1] = (int32_t)plans[b].num_nodes;
+        }
+        depth = std::max(depth, h > 0 ? (size_t)h : kept[b].size());
+    }
+    T.level_nodes.clear();
+    T.level_blas.clear();
+    T.level_off.assign(1, 0u);
+    for (size_t l = 0; l < depth; l++) {
+        for (size_t b = 0; b < nb; b++) {
+            const int32_t h = items[4 * b + 2];
+            if (h > 0) {
+                if ((int32_t)l >= h) continue;
+                const int64_t off = blas_rebuild_level_off(plans[b].num_leaves, h, (int)l);
+                const int64_t cnt = blas_rebuild_level_count(plans[b].num_leaves, h, (int)l);
+                for (int64_t i = 0; i < cnt; i++) { T.level_nodes.push_back((uint32_t)(off + i)); T.level_blas.push_back((int32_t)b); }
+            } else if (l < kept[b].size()) {
+                for (const uint32_t n : kept[b][l]) { T.level_nodes.push_back(n); T.level_blas.push_back((int32_t)b); }
+            }
+        }
+        T.level_off.push_back((uint32_t)T.level_nodes.size());
+    }
+}
+
+// The tail's workgroups for the BLASes in `items` (four int32 each: BlasRbItem) and a tail of T positions (0: no tail,
+// else 4 * 4^k, at most pt_blas_rebuild.hip's kBlasTailMax): four int32 per workgroup.  A BLAS whose first segment fits T is one workgroup from
+// its first shift; a larger one is cut into segments of T positions that start at T's shift.  Depends on n alone.
+inline void blas_tail_table(const int32_t* items, int64_t num_blas, int64_t T, std::vector<int32_t>& tail) {
+    tail.clear();
+    if (T <= 0) return;
+    int sT = 0;
+    while (((int64_t)4 << sT) < T) sT++;
+    for (int64_t b = 0; b < num_blas; b++) {
+        const int64_t r0 = items[4 * b], n = items[4 * b + 1], h = items[4 * b + 2];
+        if (h <= 0 || n <= 0) continue;
+        const int s0 = 2 * (int)h < sT ? 2 * (int)h : sT;
+        const int64_t seg = (int64_t)4 << s0;
+        for (int64_t at = 0; at < n; at += seg) {
+            const int32_t row[4] = {(int32_t)(r0 + at), (int32_t)(at + seg < n ? seg : n - at), s0, 0};
+            tail.insert(tail.end(), row, row + 4);
+        }
+    }
 }
 
 // pt_pose_meshes: [rest v1 v2 v3 n1 n2 n3 | group | matrices | mask]

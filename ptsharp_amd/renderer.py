@@ -738,6 +738,60 @@ class Renderer:
             dst[...] = a
         return float(ms.value)
 
+    def RebuildBlas(self, v1=None, v2=None, v3=None, n1=None, n2=None, n3=None, normals=None, what=0) -> float:
+        """UpdateMeshes that also re-sorts every instanced mesh's BLAS on the device (pt_rebuild_blas): each BLAS gets a
+        balanced object-median tree for the new positions (BlasCost tells when that pays); one whose balanced tree
+        needs more nodes than the upload gave it is refitted instead.  `what` is _abi.REBUILD_WORLD (the world
+        triangle BVH, as RebuildMeshes re-sorts it), _abi.REBUILD_BLAS, or both (0).  RebuildBlas() with no arrays
+        takes the pose the last PoseMeshes left staged on the device.  The uploaded FlatScene is kept as UpdateMeshes
+        keeps it.  Returns the device time of the kernels in ms."""
+        self._ensure_scene()
+        ms = C.c_double(0.0)
+        if v1 is None:
+            if any(a is not None for a in (v2, v3, n1, n2, n3)) or normals is not None:
+                raise ValueError("RebuildBlas() takes the staged pose: no other argument goes with it")
+            _abi.check(self._lib.pt_rebuild_blas(self._ctx, None, int(what), C.byref(ms)), "pt_rebuild_blas")
+            self._refresh_mirror()
+            return float(ms.value)
+        self._refresh_mirror()
+        flat = self._uploaded
+        n = len(flat.tri_material)
+        if (n1 is None) != (n2 is None) or (n1 is None) != (n3 is None):
+            raise ValueError("n1, n2 and n3 must be all given or all None")
+        if normals is not None and n1 is not None:
+            raise ValueError("normals= derives the normals: n1, n2 and n3 cannot be given with it")
+        if normals not in (None, "face", "smooth"):
+            raise ValueError('normals is None, "face" or "smooth"')
+        arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (v1, v2, v3)]
+        if n1 is not None:
+            arrs += [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (n1, n2, n3)]
+        if any(len(a) != n for a in arrs):
+            raise ValueError(f"the scene has {n} triangles")
+        fp = C.POINTER(C.c_float)
+        u = _abi.pt_mesh_update()
+        u.num_triangles = n
+        u.normals_mode = 0 if normals is None else _abi.NORMALS_FACE if normals == "face" else _abi.NORMALS_SMOOTH
+        for name, a in zip(("v1", "v2", "v3", "n1", "n2", "n3"), arrs):
+            setattr(u, name, a.ctypes.data_as(fp))
+        _abi.check(self._lib.pt_rebuild_blas(self._ctx, C.byref(u), int(what), C.byref(ms)), "pt_rebuild_blas")
+        if normals is not None:
+            arrs += self._derived_normals(arrs)
+        for dst, a in zip((flat.tri_v1, flat.tri_v2, flat.tri_v3, flat.tri_n1, flat.tri_n2, flat.tri_n3), arrs):
+            dst[...] = a
+        return float(ms.value)
+
+    def BlasCost(self):
+        """The surface-area cost of every BLAS as it stands on the device (pt_blas_cost): [B, 3] float64 of (inner,
+        leaf, root_area), the first two relative to the BLAS's root box's area.  A refit keeps the topology, so the cost
+        grows as a mesh deforms; its growth since the upload is the trigger for RebuildBlas."""
+        self._ensure_scene()
+        counts = (C.c_int64 * 3)()
+        _abi.check(self._lib.pt_read_blas(self._ctx, counts, None, None, None, None, None), "pt_read_blas")
+        nb = int(counts[0])
+        out = np.zeros((nb, 3), np.float64)
+        _abi.check(self._lib.pt_blas_cost(self._ctx, nb, out.ctypes.data_as(C.POINTER(C.c_double))), "pt_blas_cost")
+        return out
+
     def TriBvhCost(self):
         """The surface-area cost of the world triangle BVH as it stands on the device (pt_tri_bvh_cost): (inner,
         leaf, root_area), the first two relative to the root box's area.  A refit keeps the topology, so the cost
