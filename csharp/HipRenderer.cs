@@ -240,6 +240,48 @@ namespace PTSharpCore
             public IntPtr windows;         // null, or [num_volumes] pointers: null = kept, else the uploaded num_windows pt_volume_window
         }
 
+        public const int PT_LOOK_ENV = 1;   // pt_material_update.flags
+        public const int PT_TEXELS_F64 = 0, PT_TEXELS_RGB8 = 1, PT_TEXELS_RGBA8 = 2;   // pt_texel_format
+
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_material_update
+        {
+            public int num_materials;      // must equal the uploaded scene's
+            public int flags;              // 0 or PT_LOOK_ENV: the env_* fields are taken
+            public fixed int reserved[2];  // 0
+            public IntPtr materials;       // [num_materials] pt_material, or null = kept
+            public fixed double env_color[3];
+            public int env_texture, _pad;  // 1-based, 0 = null
+            public double env_texture_angle;
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_look_info
+        {
+            public int num_materials, num_textures, num_lights;
+            public int lights_lean, route, shade_route;
+            public int env_texture, _pad;
+            public fixed double env_color[3];
+            public double env_texture_angle;
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        public struct pt_texture_image
+        {
+            public int width, height;      // must equal the uploaded texture's
+            public int format, reserved;   // pt_texel_format; 0
+            public IntPtr data;            // F64: [h][w][3] double; RGB8 / RGBA8: [h][w][3|4] bytes, rows packed
+            public IntPtr lut;             // [256] double, required for the 8-bit formats
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_texture_update
+        {
+            public int num_textures;       // must equal the uploaded scene's
+            public fixed int reserved[3];  // 0
+            public IntPtr images;          // null, or [num_textures] pointers to pt_texture_image: null = the texture stays
+        }
+
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_get_version();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_device_count(out int count);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_create(ref pt_device_opts opts, out IntPtr ctx);
@@ -290,6 +332,10 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_blas_cost(IntPtr ctx, int numBlas, double[] out3PerBlas);
         // new voxels and iso-windows for the scene's Volumes: their derived tables rebuilt on the device (DESIGN.md §4i)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_volumes(IntPtr ctx, ref pt_volume_update u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_materials(IntPtr ctx, ref pt_material_update u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_materials(IntPtr ctx, out pt_look_info info, [In, Out] pt_material[] materials, int[] lightRows, double[] lightSpheres);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_update_textures(IntPtr ctx, ref pt_texture_update u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_texture(IntPtr ctx, int index, int[] info, double[] data);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_volume(IntPtr ctx, int index, long[] info, double[] data, [In, Out] pt_volume_window[] windows, sbyte[] runs, double[] cells);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_intersect(IntPtr ctx, long n, float[] origins, float[] dirs, int flags, double[] t, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_occluded(IntPtr ctx, long n, float[] origins, float[] dirs, double[] tMax, int flags, int[] blocked);
@@ -977,6 +1023,67 @@ namespace PTSharpCore
             finally
             {
                 foreach (var h in held) h.Free();
+            }
+        }
+
+        /// <summary>New materials and a new environment for the uploaded scene (pt_update_materials): materials holds
+        /// the scene's whole table in the upload's order, or is null (kept); with env the environment colour, texture
+        /// slot (1-based, 0 = none) and angle are taken.  The lights and the routing flags follow on the device as at
+        /// an upload: a shape whose material now emits becomes a light, one that no longer does stops being one.  No
+        /// geometry is re-sent.  Returns 0: the call launches no kernel.</summary>
+        public unsafe double UpdateMaterials(PtHip.pt_material[] materials, bool env = false, double[] envColor = null,
+                                             int envTexture = 0, double envTextureAngle = 0)
+        {
+            if (!uploaded) Upload();
+            var h = materials == null ? default : GCHandle.Alloc(materials, GCHandleType.Pinned);
+            try
+            {
+                var u = new PtHip.pt_material_update
+                {
+                    num_materials = materials?.Length ?? 0,
+                    flags = env ? PtHip.PT_LOOK_ENV : 0,
+                    materials = materials == null ? IntPtr.Zero : h.AddrOfPinnedObject(),
+                    env_texture = envTexture,
+                    env_texture_angle = envTextureAngle
+                };
+                for (int k = 0; k < 3 && envColor != null; k++) u.env_color[k] = envColor[k];
+                PtHip.Check(PtHip.pt_update_materials(ctx, ref u, out double ms), "pt_update_materials");
+                return ms;
+            }
+            finally
+            {
+                if (materials != null) h.Free();
+            }
+        }
+
+        /// <summary>New texels for the textures of the uploaded scene, in the upload's texture order
+        /// (pt_update_textures): images[i] is null (texture i stays) or an image of the uploaded size whose data and
+        /// lut the caller keeps pinned for the call.  The 8-bit formats are decoded on the device through lut.  Returns
+        /// the device time of the decode kernels in ms.</summary>
+        public double UpdateTextures(PtHip.pt_texture_image?[] images)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            try
+            {
+                var ptrs = new IntPtr[Math.Max(1, images.Length)];
+                for (int i = 0; i < images.Length; i++)
+                {
+                    if (images[i] == null) continue;
+                    var one = new[] { images[i].Value };
+                    var hh = GCHandle.Alloc(one, GCHandleType.Pinned);
+                    held.Add(hh);
+                    ptrs[i] = hh.AddrOfPinnedObject();
+                }
+                var hp = GCHandle.Alloc(ptrs, GCHandleType.Pinned);
+                held.Add(hp);
+                var u = new PtHip.pt_texture_update { num_textures = images.Length, images = hp.AddrOfPinnedObject() };
+                PtHip.Check(PtHip.pt_update_textures(ctx, ref u, out double ms), "pt_update_textures");
+                return ms;
+            }
+            finally
+            {
+                foreach (var hh in held) hh.Free();
             }
         }
 

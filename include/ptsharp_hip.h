@@ -34,6 +34,10 @@
  *   / pt_blas_cost     the cost of each BLAS as it stands                     Mesh.cs / TransformedShape.cs
  *   pt_update_volumes  (new) new voxels and iso-windows for the scene's         Volume.NewVolume, Volume.cs:48-71, and
  *   / pt_read_volume   Volumes: their derived tables rebuilt on the device      VolumeWindow, Volume.cs:8-19
+ *   pt_update_materials (new) new materials and environment for the uploaded    Scene.Add, Scene.cs:29-38 (the lights
+ *   / pt_read_materials scene: the lights and routing flags derived again        follow the emittances), Material.cs:8-62
+ *   pt_update_textures (new) new texels for the scene's textures, 8-bit images   ColorTexture.NewTexture, Texture.cs:150-166,
+ *   / pt_read_texture  decoded on the device through the host's 256-entry table  ITexture.Pow / MulScalar
  *   pt_render_pass    one Renderer.RenderParallel() pass                  Renderer.cs:199-338
  *                      (flag PT_PASS_SERIAL: one Renderer.Render() pass  Renderer.cs:80-198)
  *                      = spp × Camera.CastRay → DefaultSampler.Sample      Camera.cs:98-119, Sampler.cs:40-145,191-296
@@ -852,9 +856,9 @@ int pt_blas_cost(void* ctx, int32_t num_blas, double* out /* [num_blas][3] */);
  * Lights: Scene.Add registers a shape as a light when MaterialAt(origin).Emittance > 0 (Scene.cs:29-38).  For a
  * Volume, and for a TransformedShape over one (whose MaterialAt passes the point on unmapped), that is the material
  * of the sample at the origin, which is 0 whatever the voxels (Sample's z index there is d, past the last slice), so
- * it depends on the windows alone.  The set of lights is fixed at upload: before anything is copied or launched the
- * call evaluates the test with the new windows and refuses with PT_ERR_UNSUPPORTED when any shape's membership
- * would differ.  A light that stays one takes the material the test now gives.
+ * it depends on the windows alone.  This call does not change the set of lights (the upload's, or the one the last
+ * pt_update_materials left): before anything is copied or launched it evaluates the test with the new windows and
+ * refuses with PT_ERR_UNSUPPORTED when any shape's membership in the current set would differ.  A light that stays one takes the material the test now gives.
  * Ordering: runs on the context's stream after every pass issued before it and synchronises before returning.  The
  * Buffer, the pass state, the counters, the feature buffers, the query tables and the process-wide build cache are
  * untouched.  out_kernel_ms (may be NULL) is the device time of the call's kernels.
@@ -880,6 +884,92 @@ int pt_update_volumes(void* ctx, const pt_volume_update* u, double* out_kernel_m
  * scene: PT_ERR_NO_SCENE. */
 int pt_read_volume(void* ctx, int32_t index, int64_t info[8], double* data, pt_volume_window* windows,
                    int8_t* runs, double* cells);
+
+/* New materials and a new environment for the uploaded scene: a light dimmed, a material recoloured,
+ * an emitter switched on, the environment map turned or swapped, without the re-upload that recompiles both BVHs and
+ * re-sends the geometry.  materials non-NULL replaces every row of the material table; flags & PT_LOOK_ENV takes
+ * env_color, env_texture and env_texture_angle (else the environment stays).  The arrays are copied during the call.
+ * Equivalence: afterwards every ray query, feature pass and render pass sees what a fresh pt_upload_scene of the same
+ * pt_scene_desc with these materials and environment values substituted, and the geometry the device holds now,
+ * would see; every word of the material table and of the light table, num_lights, lights_lean, route and
+ * shade_route equal that upload's.  No tie-order caveat: nothing is re-sorted.  Which material a shape uses (the
+ * *_material arrays, window and SDF materials), the number of materials and the number and size of the textures
+ * stay; changing those needs a pt_upload_scene.
+ * Lights follow: Scene.Add makes a shape a light when MaterialAt(origin).Emittance > 0 (Scene.cs:29-38), so with new
+ * emittances the set of lights may grow, shrink or reorder; the call runs the upload's own light and flag
+ * derivation on the new table and the shapes' current parameters (a light's sphere comes from where pt_update_shapes,
+ * pt_update_triangles, pt_update_meshes or pt_pose_meshes left its shape), and the later updates move the lights of
+ * the new list.  pt_update_volumes tests light membership against the set this call left.  The device light array
+ * grows once to num_shapes entries when the list outgrows the upload's (PT_ERR_OUT_OF_MEMORY before anything
+ * changes if it cannot).
+ * Ordering: runs on the context's stream after every pass issued before it and synchronises before returning.
+ * Everything is validated and derived on the host before the first copy.  The Buffer, the pass state, the counters,
+ * the feature buffers, the query tables and the build cache are untouched.  out_kernel_ms (may be NULL) is 0: the
+ * call launches no kernel.
+ * Errors (nothing copied, the scene untouched): a NULL ctx or u, reserved != 0, flags outside {0, PT_LOOK_ENV},
+ * materials given with num_materials different from the scene's, a texture slot of a material or of the environment
+ * outside [0, num_textures]: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE.  materials NULL and no flag: PT_OK,
+ * nothing done.  Values are not range-checked, as at upload.  A copy that fails after the checks is PT_ERR_HIP, as
+ * in the other updates: the device's tables are then part old, part new, and the context needs a pt_upload_scene. */
+#define PT_LOOK_ENV 1                 /* flags: the env_* fields are taken; else the environment stays */
+typedef struct pt_material_update {
+    int32_t num_materials;            /* must equal the uploaded scene's */
+    int32_t flags;                    /* 0 or PT_LOOK_ENV */
+    int32_t reserved[2];              /* 0 */
+    const pt_material* materials;     /* [num_materials], or NULL = kept */
+    double  env_color[3];             /* Scene.Color */
+    int32_t env_texture, _pad;        /* Scene.Texture, 1-based, 0 = null, <= the uploaded num_textures */
+    double  env_texture_angle;        /* Scene.TextureAngle */
+} pt_material_update;
+int pt_update_materials(void* ctx, const pt_material_update* u, double* out_kernel_ms);
+/* What the device holds now (tests and tools).  info: the counts, the flags the passes are planned from and the
+ * environment; materials receives num_materials rows, texture slots 1-based again, read back from the device;
+ * light_rows receives per light {kind (DevLight: 0 sphere, 1 cube, 2 plane, 3 triangle, 5 SDF, 6 Volume, 7
+ * transformed), index, material, phantom}, light_spheres per light {centre x, y, z widened to double, radius},
+ * both in the lights' order and read back from the device (a scene has at most num_shapes lights).  Every pointer but
+ * ctx may be NULL.  Synchronises and changes nothing.  A NULL ctx: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+typedef struct pt_look_info {
+    int32_t num_materials, num_textures, num_lights;
+    int32_t lights_lean, route, shade_route;   /* DevScene's flags */
+    int32_t env_texture, _pad;                 /* 1-based, 0 = null */
+    double env_color[3];
+    double env_texture_angle;
+} pt_look_info;
+int pt_read_materials(void* ctx, pt_look_info* info, pt_material* materials, int32_t* light_rows, double* light_spheres);
+
+/* New texels for the textures of the uploaded scene: the next frame of a video texture, a swapped
+ * image.  images[i] non-NULL gives texture i new texels of the uploaded width and height.  PT_TEXELS_F64 is a copy
+ * into place of [h][w][3] doubles, as pt_texture::data.  The 8-bit formats send the image's bytes and a 256-entry
+ * table: a texture made from an 8-bit image is (byte / 255)^2.2 per channel (ColorTexture.NewTexture,
+ * Texture.cs:150-166), and ITexture.Pow and MulScalar map every texel through one function, so every texel channel is
+ * lut[byte].  The host computes the table with its own pow, the bit patterns it would have sent; the device
+ * (k_tex_decode, pt_texture.hip) looks the bytes up and writes the doubles, and never calls pow: the texels are
+ * bit-equal to the F64 route by construction, for 3 or 4 bytes per texel over the bus instead of 24.
+ * Equivalence: the texel words equal a fresh upload's with the host-decoded pt_texture; everything else is
+ * untouched (ordering and scope as pt_update_materials).  out_kernel_ms (may be NULL): the decode kernels' device
+ * time, 0 when none ran.
+ * Errors (nothing copied, the scene untouched): a NULL ctx or u, reserved != 0, num_textures different from the
+ * scene's, an image whose width or height differ from the uploaded texture's, a format outside the enum, a NULL data
+ * in a non-NULL image, a NULL lut with an 8-bit format: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; the byte
+ * staging (4 B per texel of the scene plus the tables, kept until the next upload) not allocated:
+ * PT_ERR_OUT_OF_MEMORY.  images NULL or every entry NULL: PT_OK, nothing launched. */
+typedef enum pt_texel_format { PT_TEXELS_F64 = 0, PT_TEXELS_RGB8 = 1, PT_TEXELS_RGBA8 = 2 } pt_texel_format;
+typedef struct pt_texture_image {
+    int32_t width, height;            /* must equal the uploaded texture's */
+    int32_t format, reserved;         /* pt_texel_format; 0 */
+    const void*   data;               /* F64: [h][w][3] double; RGB8 / RGBA8: [h][w][3|4] bytes, rows packed, A ignored */
+    const double* lut;                /* [256], required for the 8-bit formats: texel channel = lut[byte] */
+} pt_texture_image;
+typedef struct pt_texture_update {
+    int32_t num_textures;             /* must equal the uploaded scene's */
+    int32_t reserved[3];              /* 0 */
+    const pt_texture_image* const * images;  /* NULL, or [num_textures]; a NULL entry = that texture stays */
+} pt_texture_update;
+int pt_update_textures(void* ctx, const pt_texture_update* u, double* out_kernel_ms);
+/* The texels the device holds for texture `index` (tests and tools): info = {width, height, 0, 0}; data receives
+ * [h][w][3] doubles.  info and data may be NULL.  A NULL ctx or an index outside the scene's textures:
+ * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+int pt_read_texture(void* ctx, int32_t index, int32_t info[4], double* data);
 
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {

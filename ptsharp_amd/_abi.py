@@ -37,6 +37,8 @@ SHAPE_SDF, SHAPE_VOLUME, SHAPE_TRANSFORMED = 5, 6, 7
 MARCH_LANE, MARCH_WAVE = 1, 2   # pt_intersect / pt_occluded flags (PT_MARCH_*)
 NORMALS_FACE, NORMALS_SMOOTH = 1, 2   # pt_normals_mode (pt_update_triangles_normals)
 REBUILD_WORLD, REBUILD_BLAS = 1, 2    # pt_rebuild_blas' `what`
+LOOK_ENV = 1                          # pt_material_update.flags (PT_LOOK_ENV)
+TEXELS_F64, TEXELS_RGB8, TEXELS_RGBA8 = 0, 1, 2   # pt_texel_format
 
 _f = C.POINTER(C.c_float)
 _d = C.POINTER(C.c_double)
@@ -158,6 +160,29 @@ class pt_volume_update(C.Structure):
                 ("windows", C.POINTER(C.POINTER(pt_volume_window)))]
 
 
+class pt_material_update(C.Structure):
+    _fields_ = [("num_materials", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("materials", C.POINTER(pt_material)), ("env_color", C.c_double * 3), ("env_texture", C.c_int32),
+                ("_pad", C.c_int32), ("env_texture_angle", C.c_double)]
+
+
+class pt_look_info(C.Structure):
+    _fields_ = [("num_materials", C.c_int32), ("num_textures", C.c_int32), ("num_lights", C.c_int32),
+                ("lights_lean", C.c_int32), ("route", C.c_int32), ("shade_route", C.c_int32),
+                ("env_texture", C.c_int32), ("_pad", C.c_int32), ("env_color", C.c_double * 3),
+                ("env_texture_angle", C.c_double)]
+
+
+class pt_texture_image(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("format", C.c_int32), ("reserved", C.c_int32),
+                ("data", C.c_void_p), ("lut", _d)]
+
+
+class pt_texture_update(C.Structure):
+    _fields_ = [("num_textures", C.c_int32), ("reserved", C.c_int32 * 3),
+                ("images", C.POINTER(C.POINTER(pt_texture_image)))]
+
+
 # pt_hit_arrays' outputs in the header's order: name -> (numpy dtype, components per ray)
 HIT_ARRAYS = {"t": ("f8", 1), "kind": ("i4", 1), "index": ("i4", 1), "prim": ("i4", 1), "shape": ("i4", 1),
               "position": ("f4", 3), "normal": ("f4", 3), "inside": ("i4", 1), "material": ("i4", 1),
@@ -211,6 +236,10 @@ SIGNATURES = {
     "pt_update_volumes": (C.c_int, [C.c_void_p, C.POINTER(pt_volume_update), _d]),
     "pt_read_volume": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _d, C.POINTER(pt_volume_window),
                                  C.POINTER(C.c_int8), _d]),
+    "pt_update_materials": (C.c_int, [C.c_void_p, C.POINTER(pt_material_update), _d]),
+    "pt_read_materials": (C.c_int, [C.c_void_p, C.POINTER(pt_look_info), C.POINTER(pt_material), _i, _d]),
+    "pt_update_textures": (C.c_int, [C.c_void_p, C.POINTER(pt_texture_update), _d]),
+    "pt_read_texture": (C.c_int, [C.c_void_p, C.c_int32, _i, _d]),
     "pt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_sampler), C.POINTER(pt_pass_params)]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_reset_buffer": (C.c_int, [C.c_void_p]),

@@ -34,6 +34,7 @@
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
 #include "pt_shape_refit.h"
+#include "pt_texture.h"
 #include "pt_update_layout.h"
 #include "pt_volume_update.h"
 #include "pt_wavefront.h"
@@ -149,6 +150,9 @@ hipError_t launch_pose(int64_t n, int32_t num_meshes, const int32_t* group, cons
                        bool normals, const float* const rest[6], float* const out[6], hipStream_t stream);
 // pt_volume.hip
 hipError_t launch_vol_rebuild(const DevVolume& v, bool new_data, hipStream_t stream);
+// pt_texture.hip
+hipError_t launch_tex_decode(const uint8_t* src, uint64_t src_off, int format, uint64_t pixels, const double* lut, double* dst,
+                             hipStream_t stream);
 }
 
 namespace {
@@ -252,8 +256,18 @@ struct SceneDyn {
     std::vector<int32_t> blas_node_cap;
     std::vector<int32_t> blas_items, blas_tail, blas_pos;
     bool query_blas_src_stale = false;       // a pt_rebuild_blas permuted blas_refit.src_of_pos after query_ws took its copy
-    // pt_set_rest_pose: the rest vertices of the lights that are loose triangles, 9 floats per h_lights entry
-    std::vector<float> rest_light_verts;
+    // pt_set_rest_pose: the rest vertices of every loose triangle of Scene.Shapes, laid out as look.tri_verts (a light
+    // that is one returns to them at every pose)
+    std::vector<float> rest_tri_verts;
+    // pt_update_materials and pt_update_textures: the slots the light test runs over, with the loose
+    // triangles' vertices as the device holds them now; the material table the device holds (the scene's rows, then
+    // `new Material()`); the entries S.lights has room for; the textures with their device addresses; the byte
+    // staging of the 8-bit formats (every texture's table, then 4 B per texel of the scene)
+    pt::LookTables look;
+    std::vector<pt::DevMaterial> h_mats;
+    size_t lights_cap = 0;
+    std::vector<pt::DevTexture> texs;
+    DeviceArray tex_stage;
     bool pose_staged = false;            // refit_ws' staged arrays hold the last pt_pose_meshes' (pt_read_pose)
     bool blas_boxes_on_device = false;   // blas_ws holds the meshes' boxes (after the first pt_update_meshes)
     void release_device() {
@@ -265,6 +279,7 @@ struct SceneDyn {
         rebuild_ws.release();
         blas_rebuild_ws.release();
         query_ws.release();
+        tex_stage.release();
     }
 };
 
@@ -717,6 +732,10 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     c->dyn.blas_refit = std::move(H.blas_refit);
     c->dyn.query = std::move(H.query);
     c->dyn.h_lights = std::move(H.lights);
+    c->dyn.lights_cap = c->dyn.h_lights.size();
+    c->dyn.look = std::move(H.look);
+    c->dyn.h_mats = std::move(H.mats);
+    c->dyn.texs = std::move(texs);
     c->dyn.has_blas = !H.blas.empty();
     c->dyn.h_blas = H.blas;
     for (const pt::DevBlas& b : H.blas) c->dyn.blas_node_cap.push_back(b.num_nodes);
@@ -1698,15 +1717,22 @@ int update_run(Ctx* c, const UpdateCall& U, double* out_kernel_ms) {
         PT_HIP(hipMemcpyAsync(src.data(), Y.blas_ws.at.src_of_pos, src.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         Y.query_blas_src_stale = true;
     }
-    // lights that are loose emissive triangles: their sphere from the new vertices
+    // the loose triangles' vertices as the device holds them from here on (a later pt_update_materials may make any
+    // of them a light), then the lights that are loose emissive triangles: their sphere from the new vertices
+    for (const pt::LookSlot& slot : Y.look.slots) {
+        if (slot.vert < 0) continue;
+        float* m = &Y.look.tri_verts[(size_t)slot.vert];
+        const float* const* v = U.light_verts;
+        const size_t j = (size_t)slot.index;
+        if (v[0]) for (int k = 0; k < 3; k++) std::memcpy(m + 3 * k, v[k] + 3 * j, 3 * sizeof(float));
+        else if (Y.rest_tri_verts.size() == Y.look.tri_verts.size()) std::memcpy(m, &Y.rest_tri_verts[(size_t)slot.vert], 9 * sizeof(float));
+    }
     bool lights_moved = false;
     for (size_t i = 0; i < Y.h_lights.size() && i < T.light_tri.size(); i++) {
         const int64_t j = T.light_tri[i];
         if (j < 0) continue;
-        const float* const* v = U.light_verts;
-        const float* kept = v[0] ? nullptr : &Y.rest_light_verts[9 * i];
-        if (v[0]) pt::tri_light_sphere(v[0] + 3 * j, v[1] + 3 * j, v[2] + 3 * j, Y.h_lights[i]);
-        else pt::tri_light_sphere(kept, kept + 3, kept + 6, Y.h_lights[i]);
+        const float* m = &Y.look.tri_verts[(size_t)Y.look.slots[(size_t)Y.look.light_slot[i]].vert];
+        pt::tri_light_sphere(m, m + 3, m + 6, Y.h_lights[i]);
         lights_moved = true;
     }
     if (lights_moved) if (const int rc = upload_lights(c)) return rc;
@@ -1834,12 +1860,11 @@ int pt_set_rest_pose(void* ctx, int32_t num_triangles, const float* v1, const fl
         stage_arrays(up, Y.pose_ws.at.rest, src, num_triangles);
         if (const int rc = check_hip(up.err, "staging the rest pose")) return rc;
     }
-    // the lights that are loose emissive triangles return to these at every pose
-    Y.rest_light_verts.assign(9 * Y.h_lights.size(), 0.f);
-    for (size_t i = 0; i < Y.h_lights.size() && i < T.light_tri.size(); i++) {
-        const int64_t j = T.light_tri[i];
-        if (j < 0 || j >= num_triangles) continue;
-        for (int k = 0; k < 3; k++) std::memcpy(&Y.rest_light_verts[9 * i + 3 * k], src[k] + 3 * j, 3 * sizeof(float));
+    // the loose triangles (the lights among them) return to these at every pose
+    Y.rest_tri_verts.assign(Y.look.tri_verts.size(), 0.f);
+    for (const pt::LookSlot& slot : Y.look.slots) {
+        if (slot.vert < 0 || slot.index < 0 || slot.index >= num_triangles) continue;
+        for (int k = 0; k < 3; k++) std::memcpy(&Y.rest_tri_verts[(size_t)slot.vert + 3 * k], src[k] + 3 * (size_t)slot.index, 3 * sizeof(float));
     }
     PT_HIP(hipStreamSynchronize(c->stream));
     return PT_OK;
@@ -2209,6 +2234,11 @@ int pt_update_volumes(void* ctx, const pt_volume_update* u, double* out_kernel_m
     }
     if (lights_changed) if (const int rc = upload_lights(c)) return rc;
     PT_HIP(hipStreamSynchronize(c->stream));
+    {   // the light test's slots take the materials too: a later pt_update_materials derives the lights from them
+        size_t at = 0;
+        for (pt::LookSlot& slot : Y.look.slots)
+            if (slot.volume >= 0 && at < mats.size()) slot.mat = mats[at++];
+    }
     Y.vols = std::move(hdrs);
     Y.vol_windows = std::move(rows);
     return kernel_ms(c, out_kernel_ms);
@@ -2233,6 +2263,211 @@ int pt_read_volume(void* ctx, int32_t index, int64_t info[8], double* data, pt_v
     PT_HIP(read_back(c, windows, v.windows, (size_t)v.nwin * sizeof(pt::DevWindow)));
     PT_HIP(read_back(c, runs, v.runs, v.runs ? (size_t)ncells : 0));
     PT_HIP(read_back(c, cells, v.cells, v.cells ? (size_t)pt::vol_cell_byte(ncells) : 0));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// ---- the look edited in place
+int pt_update_materials(void* ctx, const pt_material_update* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!u) return fail(PT_ERR_INVALID_ARG, "update materials: u is NULL");
+    if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "update materials: reserved must be 0");
+    if (u->flags != 0 && u->flags != PT_LOOK_ENV) return fail(PT_ERR_INVALID_ARG, "update materials: flags must be 0 or PT_LOOK_ENV");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const int32_t nm = (int32_t)Y.h_mats.size() - 1, nt = (int32_t)Y.texs.size();   // (the last row is `new Material()`)
+    auto slot_ok = [&](int32_t t) { return t >= 0 && t <= nt; };
+    if (u->materials) {
+        if (u->num_materials != nm)
+            return fail(PT_ERR_INVALID_ARG, "update materials: num_materials is " + std::to_string(u->num_materials) +
+                                                ", the uploaded scene has " + std::to_string(nm));
+        for (int32_t i = 0; i < nm; i++) {
+            const pt_material& m = u->materials[i];
+            if (!slot_ok(m.texture) || !slot_ok(m.normal_texture) || !slot_ok(m.bump_texture) || !slot_ok(m.gloss_texture))
+                return fail(PT_ERR_INVALID_ARG, "update materials: material " + std::to_string(i) + ": texture reference out of range");
+        }
+    }
+    const bool env = (u->flags & PT_LOOK_ENV) != 0;
+    if (env && !slot_ok(u->env_texture)) return fail(PT_ERR_INVALID_ARG, "update materials: env_texture out of range");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (!u->materials && !env) return PT_OK;
+    // everything the call would leave, derived on the host before the first copy: the table, the lights with their
+    // side tables, the flags (the upload's own derivation, pt_scene_compile.cpp look_lights / look_flags)
+    std::vector<pt::DevMaterial> mats = Y.h_mats;
+    if (u->materials) for (int32_t i = 0; i < nm; i++) pt::pack_material(u->materials[i], mats[(size_t)i]);
+    pt::LookLights L;
+    pt::look_lights(Y.look, Y.shape_refit, mats, L);
+    pt::DevScene S = c->S;
+    pt::look_flags(Y.look, L.lights, mats, S.tri_num_nodes, S);
+    S.num_lights = (int32_t)L.lights.size();
+    if (env) {
+        S.env_tex = u->env_texture - 1;
+        S.env_angle = u->env_texture_angle;
+        for (int k = 0; k < 3; k++) S.env[k] = u->env_color[k];
+    }
+    PT_HIP(hipSetDevice(c->device));
+    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
+    if (L.lights.size() > Y.lights_cap) {    // once, to the most a scene can have: one light per Scene.Shapes slot
+        DeviceArray a;
+        a.bytes = Y.look.slots.size() * sizeof(pt::DevLight);
+        if (hipMalloc(&a.ptr, a.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PT_ERR_OUT_OF_MEMORY, "update materials: light array allocation");
+        }
+        c->scene_arrays.push_back(a);   // (the upload's array goes with the scene too)
+        S.lights = (const pt::DevLight*)a.ptr;
+        c->S.lights = S.lights;
+        Y.lights_cap = Y.look.slots.size();
+        if (!Y.h_lights.empty()) if (const int rc = upload_lights(c)) return rc;   // the current lights, in the new array
+    }
+    // (as in the other updates, a copy or the synchronisation failing from here on is PT_ERR_HIP with the device's
+    // tables part old, part new: the context needs a pt_upload_scene)
+    if (u->materials)
+        PT_HIP(hipMemcpyAsync(const_cast<pt::DevMaterial*>(c->S.mats), mats.data(), mats.size() * sizeof(pt::DevMaterial),
+                              hipMemcpyHostToDevice, c->stream));
+    if (!L.lights.empty())
+        PT_HIP(hipMemcpyAsync(const_cast<pt::DevLight*>(S.lights), L.lights.data(), L.lights.size() * sizeof(pt::DevLight),
+                              hipMemcpyHostToDevice, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    c->S = S;
+    Y.h_mats = std::move(mats);
+    Y.h_lights = std::move(L.lights);
+    Y.refit.light_tri = std::move(L.light_tri);
+    Y.shape_refit.light_kind = std::move(L.light_kind);
+    Y.shape_refit.light_index = std::move(L.light_index);
+    Y.volume_update.slots = std::move(L.vol_slots);
+    Y.volume_update.emittance = std::move(L.emittance);
+    Y.look.light_slot = std::move(L.light_slot);
+    return PT_OK;
+}
+
+int pt_read_materials(void* ctx, pt_look_info* info, pt_material* materials, int32_t* light_rows, double* light_spheres) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    const pt::DevScene& S = c->S;
+    const size_t nm = (size_t)S.default_mat, nl = (size_t)S.num_lights;
+    if (info) {
+        std::memset(info, 0, sizeof *info);
+        info->num_materials = (int32_t)nm;
+        info->num_textures = (int32_t)c->dyn.texs.size();
+        info->num_lights = S.num_lights;
+        info->lights_lean = S.lights_lean; info->route = S.route; info->shade_route = S.shade_route;
+        info->env_texture = S.env_tex + 1;
+        for (int k = 0; k < 3; k++) info->env_color[k] = S.env[k];
+        info->env_texture_angle = S.env_angle;
+    }
+    PT_HIP(hipSetDevice(c->device));
+    std::vector<pt::DevMaterial> dm(materials ? nm : 0);   // what the device holds, not the host's copies
+    std::vector<pt::DevLight> dl(light_rows || light_spheres ? nl : 0);
+    PT_HIP(read_back(c, dm.data(), S.mats, dm.size() * sizeof(pt::DevMaterial)));
+    PT_HIP(read_back(c, dl.data(), S.lights, dl.size() * sizeof(pt::DevLight)));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < dm.size(); i++) {
+        const pt::DevMaterial& m = dm[i];
+        pt_material& o = materials[i];
+        std::memset(&o, 0, sizeof o);
+        for (int k = 0; k < 3; k++) o.color[k] = m.color[k];
+        o.emittance = m.emittance; o.index = m.index; o.gloss = m.gloss; o.tint = m.tint; o.reflectivity = m.reflectivity;
+        o.transparent = m.transparent;
+        o.texture = m.tex + 1; o.normal_texture = m.ntex + 1; o.bump_texture = m.btex + 1; o.gloss_texture = m.gtex + 1;
+        o.bump_multiplier = m.bump_multiplier;
+    }
+    for (size_t i = 0; i < dl.size(); i++) {
+        if (light_rows) { light_rows[4 * i] = dl[i].kind; light_rows[4 * i + 1] = dl[i].index; light_rows[4 * i + 2] = dl[i].mat; light_rows[4 * i + 3] = dl[i].phantom; }
+        if (light_spheres) {
+            for (int k = 0; k < 3; k++) light_spheres[4 * i + k] = (double)dl[i].center[k];
+            light_spheres[4 * i + 3] = dl[i].radius;
+        }
+    }
+    return PT_OK;
+}
+
+int pt_update_textures(void* ctx, const pt_texture_update* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!u) return fail(PT_ERR_INVALID_ARG, "update textures: u is NULL");
+    if (u->reserved[0] != 0 || u->reserved[1] != 0 || u->reserved[2] != 0) return fail(PT_ERR_INVALID_ARG, "update textures: reserved must be 0");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const int32_t nt = (int32_t)Y.texs.size();
+    if (u->num_textures != nt)
+        return fail(PT_ERR_INVALID_ARG, "update textures: num_textures is " + std::to_string(u->num_textures) +
+                                            ", the uploaded scene has " + std::to_string(nt));
+    bool any = false, any8 = false;
+    for (int32_t i = 0; u->images && i < nt; i++) {
+        const pt_texture_image* im = u->images[i];
+        if (!im) continue;
+        const std::string who = "update textures: image " + std::to_string(i);
+        if (im->reserved != 0) return fail(PT_ERR_INVALID_ARG, who + ": reserved must be 0");
+        if (im->width != Y.texs[(size_t)i].w || im->height != Y.texs[(size_t)i].h)
+            return fail(PT_ERR_INVALID_ARG, who + ": width and height differ from the uploaded texture's");
+        if (im->format != PT_TEXELS_F64 && im->format != PT_TEXELS_RGB8 && im->format != PT_TEXELS_RGBA8)
+            return fail(PT_ERR_INVALID_ARG, who + ": format is not a pt_texel_format");
+        if (!im->data) return fail(PT_ERR_INVALID_ARG, who + ": data is NULL");
+        if (im->format != PT_TEXELS_F64 && !im->lut) return fail(PT_ERR_INVALID_ARG, who + ": an 8-bit format needs lut");
+        any = true;
+        any8 = any8 || im->format != PT_TEXELS_F64;
+    }
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (!any) return PT_OK;
+    PT_HIP(hipSetDevice(c->device));
+    // the byte staging: every texture's table (2 KiB each), then room for every texture as RGBA8; before the first copy
+    const size_t luts = (size_t)nt * pt::kTexLut * sizeof(double);
+    if (any8 && !Y.tex_stage.ptr) {
+        size_t bytes = luts;
+        for (const pt::DevTexture& t : Y.texs) bytes += (size_t)pt::tex_pixels(t.w, t.h) * 4;
+        if (hipMalloc(&Y.tex_stage.ptr, bytes) != hipSuccess) {
+            Y.tex_stage.ptr = nullptr;
+            (void)hipGetLastError();
+            return fail(PT_ERR_OUT_OF_MEMORY, "update textures: byte staging allocation");
+        }
+        Y.tex_stage.bytes = bytes;
+    }
+    PT_HIP(hipStreamSynchronize(c->side));   // after every pass issued before, the side stream's work included
+    uint8_t* stage = (uint8_t*)Y.tex_stage.ptr;
+    std::vector<uint64_t> src_off((size_t)nt, 0);
+    uint64_t at = luts;   // the images packed one after another, in the formats this call gives
+    for (int32_t i = 0; i < nt; i++) {
+        const pt_texture_image* im = u->images[i];
+        if (!im) continue;
+        const pt::DevTexture& t = Y.texs[(size_t)i];
+        const uint64_t pixels = pt::tex_pixels(t.w, t.h);
+        if (im->format == PT_TEXELS_F64) {
+            PT_HIP(hipMemcpyAsync(const_cast<double*>(t.data), im->data, (size_t)pixels * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            continue;
+        }
+        const size_t bytes = (size_t)pixels * (size_t)pt::tex_bpp(im->format);
+        src_off[(size_t)i] = at;
+        PT_HIP(hipMemcpyAsync(stage + (size_t)i * pt::kTexLut * sizeof(double), im->lut, pt::kTexLut * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        PT_HIP(hipMemcpyAsync(stage + at, im->data, bytes, hipMemcpyHostToDevice, c->stream));
+        at += bytes;
+    }
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    for (int32_t i = 0; i < nt && any8; i++) {
+        const pt_texture_image* im = u->images[i];
+        if (!im || im->format == PT_TEXELS_F64) continue;
+        const pt::DevTexture& t = Y.texs[(size_t)i];
+        PT_HIP(pt::launch_tex_decode(stage, src_off[(size_t)i], im->format, pt::tex_pixels(t.w, t.h),
+                                     (const double*)(stage + (size_t)i * pt::kTexLut * sizeof(double)), const_cast<double*>(t.data), c->stream));
+    }
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return any8 ? kernel_ms(c, out_kernel_ms) : PT_OK;
+}
+
+int pt_read_texture(void* ctx, int32_t index, int32_t info[4], double* data) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    if (index < 0 || (size_t)index >= c->dyn.texs.size()) return fail(PT_ERR_INVALID_ARG, "read texture: index outside the scene's textures");
+    PT_HIP(hipSetDevice(c->device));
+    pt::DevTexture t{};   // the header the device holds, not the host's copy
+    PT_HIP(hipMemcpyAsync(&t, c->S.texs + index, sizeof t, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    if (info) { info[0] = t.w; info[1] = t.h; info[2] = 0; info[3] = 0; }
+    PT_HIP(read_back(c, data, t.data, (size_t)pt::tex_pixels(t.w, t.h) * 3 * sizeof(double)));
     PT_HIP(hipStreamSynchronize(c->stream));
     return PT_OK;
 }

@@ -392,17 +392,7 @@ struct Compiler {
 void Compiler::materials_and_textures() {
     H.mats.resize((size_t)d->num_materials);
     for (int i = 0; i < d->num_materials; i++) {
-        const pt_material& m = d->materials[i];
-        DevMaterial& o = H.mats[(size_t)i];
-        for (int k = 0; k < 3; k++) o.color[k] = m.color[k];
-        o.emittance = m.emittance;
-        o.tint = m.tint;
-        o.transparent = m.transparent;
-        o.index = m.index;
-        o.gloss = m.gloss;
-        o.reflectivity = m.reflectivity;
-        o.tex = m.texture - 1; o.ntex = m.normal_texture - 1; o.btex = m.bump_texture - 1; o.gtex = m.gloss_texture - 1;
-        o.bump_multiplier = m.bump_multiplier;
+        pack_material(d->materials[i], H.mats[(size_t)i]);
     }
     H.mats.push_back(DevMaterial{});   // `new Material()` (Volume.MaterialAt's fallback), after the scene's own
     for (auto& m : H.mats.back().color) m = 0.0;
@@ -785,46 +775,39 @@ void Compiler::planes() {
     H.S.num_planes = (int32_t)plane_scene.size();
 }
 
-// Scene.Add order (Scene.cs:29-38): MaterialAt(new Vector()).Emittance > 0
+// Scene.Add's light test (Scene.cs:29-38) is look_lights below; this stage states the scene's slots as its tables
 void Compiler::lights() {
+    LookTables& K = H.look;
+    K.slots.reserve((size_t)std::max(d->num_shapes, 0));
+    K.fixed_box.assign(6 * (size_t)std::max(d->num_shapes, 0), 0.f);
     for (int i = 0; i < d->num_shapes; i++) {
-        int k = d->shape_kind[i], j = d->shape_index[i];
-        int mat = k == PT_SHAPE_TRIANGLE ? d->tri_material[j] : k == PT_SHAPE_MESH ? -1 : shape_mat_any(k, j, origin);
-        const bool lit = !(mat < 0 || mat >= d->num_materials || !(d->materials[mat].emittance > 0));  // Mesh: `default`
-        // what a later pt_update_volumes tests again with its new windows (VolumeTables)
-        const int vj = k == PT_SHAPE_VOLUME ? j
-                     : (k == PT_SHAPE_TRANSFORMED && d->transformed[j].shape_kind == PT_SHAPE_VOLUME) ? d->transformed[j].shape_index : -1;
-        if (vj >= 0) H.volume_update.slots.push_back(VolLightSlot{vj, lit ? (int32_t)H.lights.size() : -1});
-        if (!lit) continue;
-        DevLight L{};
-        L.kind = k; L.mat = mat; L.phantom = 0;
-        if (k == PT_SHAPE_SPHERE) {   // Sampler.cs:218-223
-            L.index = ana_pos[PT_SHAPE_SPHERE][(size_t)j];
-            sphere_light_sphere(d->sphere_center + 3 * j, d->sphere_radius[j], L);
-        } else if (k == PT_SHAPE_PLANE) {
-            L.index = plane_pos[(size_t)j];
-            light_sphere_of_box(mk(-1e9, -1e9, -1e9), mk(1e9, 1e9, 1e9), L);  // Plane.BoundingBox
-        } else if (k == PT_SHAPE_TRIANGLE) {  // a directly-added struct Triangle: never passes the identity test
-            L.index = -1; L.phantom = 1;
-            tri_light_sphere(d->tri_v1 + 3 * j, d->tri_v2 + 3 * j, d->tri_v3 + 3 * j, L);
-        } else {   // Cube, SDFShape, Volume: class shapes; TransformedShape: a struct, never identical
-            const int32_t kind = k == PT_SHAPE_CUBE ? KIND_CUBE : k == PT_SHAPE_SDF ? KIND_SDF
-                               : k == PT_SHAPE_VOLUME ? KIND_VOLUME : KIND_XFORM;
-            L.kind = kind;
-            L.index = ana_pos[(size_t)k][(size_t)j];
-            L.phantom = k == PT_SHAPE_TRANSFORMED;
-            HostBox b = k == PT_SHAPE_TRANSFORMED ? xform_boxes[(size_t)j] : shape_box(k, j);   // light.BoundingBox()
-            light_sphere_of_box(b.mn, b.mx, L);
+        const int k = d->shape_kind[i], j = d->shape_index[i];
+        LookSlot s{k, j, -1, -1, -1, -1};
+        s.mat = k == PT_SHAPE_TRIANGLE ? d->tri_material[j] : k == PT_SHAPE_MESH ? -1 : shape_mat_any(k, j, origin);   // Mesh: `default`
+        s.volume = k == PT_SHAPE_VOLUME ? j
+                 : (k == PT_SHAPE_TRANSFORMED && d->transformed[j].shape_kind == PT_SHAPE_VOLUME) ? d->transformed[j].shape_index : -1;
+        if (k == PT_SHAPE_PLANE) s.pos = plane_pos[(size_t)j];
+        else if (k == PT_SHAPE_TRIANGLE) {
+            s.vert = (int32_t)K.tri_verts.size();
+            for (const float* v : {d->tri_v1, d->tri_v2, d->tri_v3}) K.tri_verts.insert(K.tri_verts.end(), v + 3 * (size_t)j, v + 3 * (size_t)j + 3);
+        } else if (k != PT_SHAPE_MESH) s.pos = ana_pos[(size_t)k][(size_t)j];
+        if (k == PT_SHAPE_SDF || k == PT_SHAPE_VOLUME) {
+            const HostBox b = shape_box(k, j);   // light.BoundingBox()
+            const float f[6] = {b.mn.x, b.mn.y, b.mn.z, b.mx.x, b.mx.y, b.mx.z};
+            std::memcpy(&K.fixed_box[6 * (size_t)i], f, sizeof f);
         }
-        H.lights.push_back(L);
-        H.refit.light_tri.push_back(k == PT_SHAPE_TRIANGLE ? j : -1);
-        const bool moves = k == PT_SHAPE_SPHERE || k == PT_SHAPE_CUBE || k == PT_SHAPE_TRANSFORMED;
-        H.shape_refit.light_kind.push_back(moves ? k : -1);
-        H.shape_refit.light_index.push_back(moves ? j : -1);
+        K.slots.push_back(s);
     }
+    LookLights L;
+    look_lights(K, H.shape_refit, H.mats, L);
+    H.lights = std::move(L.lights);
+    H.refit.light_tri = std::move(L.light_tri);
+    H.shape_refit.light_kind = std::move(L.light_kind);
+    H.shape_refit.light_index = std::move(L.light_index);
+    H.volume_update.slots = std::move(L.vol_slots);
+    H.volume_update.emittance = std::move(L.emittance);
+    K.light_slot = std::move(L.light_slot);
     H.S.num_lights = (int32_t)H.lights.size();
-    H.volume_update.emittance.resize((size_t)std::max(d->num_materials, 0));
-    for (size_t i = 0; i < H.volume_update.emittance.size(); i++) H.volume_update.emittance[i] = d->materials[i].emittance;
 }
 
 // the traversal lines: [ana_nodes | tri_nodes | tri_chunks], 8 float4 per node / chunk; the statistics
@@ -861,19 +844,14 @@ void Compiler::flags() {
     // C4's floor cube and two light spheres: a linear test of 3 records at refill costs less than a BVH
     // node step (seven loads through the texture path) and leaf record loads per ray
     S.ana_linear = (na > 0 && na <= (size_t)PT_ANA_LINEAR && !S.full_geom) ? 1 : 0;
-    S.lights_lean = 1;
-    for (const DevLight& L : H.lights)
-        if (!L.phantom && (L.kind == KIND_SDF || L.kind == KIND_VOLUME || L.kind == KIND_XFORM)) S.lights_lean = 0;
     // Routed split (C5's kind of scene: the 1M-triangle mesh, a floor cube, light spheres, one SDF shape and
     // one transformed Volume): only the rays whose segment reaches a row-4 box take the FULL kernels
     // (CompileOptions::route off: every ray through the FULL analytic half, as a -DPT_ROUTE=0 build;
     // tests compare the two, whose only possible difference is the exact-t tie order of DESIGN.md §5)
     const bool route_on = PT_ROUTE && opt.route;
-    S.route = (route_on && S.full_geom && S.lights_lean && na <= (size_t)PT_ANA_LINEAR && !H.heavy.empty() &&
-               S.tri_num_nodes > 64) ? 1 : 0;
-    bool mat_tex = false;
-    for (const auto& m : H.mats) mat_tex = mat_tex || m.tex >= 0 || m.ntex >= 0 || m.btex >= 0 || m.gtex >= 0;
-    S.shade_route = (PT_SHADE_ROUTE && S.full && !mat_tex && S.lights_lean) ? 1 : 0;   // (a Volume light's colour is FULL work)
+    H.look.route_geom = route_on && S.full_geom && na <= (size_t)PT_ANA_LINEAR && !H.heavy.empty();
+    H.look.shade_full = PT_SHADE_ROUTE && S.full;
+    look_flags(H.look, H.lights, H.mats, S.tri_num_nodes, S);
 }
 
 // The order of the stages shows in the error a bad scene reports first; each stage's output order
@@ -930,36 +908,100 @@ void sphere_light_sphere(const float* center, double radius, DevLight& L) {
 
 void box_light_sphere(const float* mn, const float* mx, DevLight& L) { light_sphere_of_box(ld3(mn), ld3(mx), L); }
 
+// The sphere of a light that is sphere j, cube j or transformed shape j of T's current parameters; false for an
+// index outside them
+static bool shape_light_sphere(const ShapeRefitTables& T, int k, int64_t j, DevLight& L) {
+    if (k == PT_SHAPE_SPHERE && j >= 0 && j < T.num_spheres) {
+        sphere_light_sphere(&T.sphere_center[3 * (size_t)j], T.sphere_radius[(size_t)j], L);
+    } else if (k == PT_SHAPE_CUBE && j >= 0 && j < T.num_cubes) {
+        box_light_sphere(&T.cube_min[3 * (size_t)j], &T.cube_max[3 * (size_t)j], L);
+    } else if (k == PT_SHAPE_TRANSFORMED && j >= 0 && j < T.num_transformed) {   // light.BoundingBox(): the unpadded box
+        const int32_t ik = T.xf_kind[(size_t)j];
+        const int64_t ij = T.xf_index[(size_t)j];
+        const float* ib = &T.xf_inner_box[6 * (size_t)j];
+        v3 imn = ld3(ib), imx = ld3(ib + 3), bmn, bmx;
+        if (ik == kShapeSphere && ij >= 0 && ij < T.num_spheres)
+            shape_sphere_bounds(&T.sphere_center[3 * (size_t)ij], T.sphere_radius[(size_t)ij], imn, imx);
+        else if (ik == kShapeCube && ij >= 0 && ij < T.num_cubes) {
+            imn = ld3(&T.cube_min[3 * (size_t)ij]);
+            imx = ld3(&T.cube_max[3 * (size_t)ij]);
+        }
+        float lo[3], hi[3];
+        shape_xform_boxes(&T.xf_matrix[16 * (size_t)j], ik, imn, imx, lo, hi, bmn, bmx);
+        const float mn[3] = {bmn.x, bmn.y, bmn.z}, mx[3] = {bmx.x, bmx.y, bmx.z};
+        box_light_sphere(mn, mx, L);
+    } else {
+        return false;
+    }
+    return true;
+}
+
 bool shape_refit_lights(const ShapeRefitTables& T, std::vector<DevLight>& lights) {
     bool any = false;
-    for (size_t i = 0; i < lights.size() && i < T.light_kind.size(); i++) {
-        const int k = T.light_kind[i];
-        const int64_t j = T.light_index[i];
-        if (k == PT_SHAPE_SPHERE && j >= 0 && j < T.num_spheres) {
-            sphere_light_sphere(&T.sphere_center[3 * (size_t)j], T.sphere_radius[(size_t)j], lights[i]);
-        } else if (k == PT_SHAPE_CUBE && j >= 0 && j < T.num_cubes) {
-            box_light_sphere(&T.cube_min[3 * (size_t)j], &T.cube_max[3 * (size_t)j], lights[i]);
-        } else if (k == PT_SHAPE_TRANSFORMED && j >= 0 && j < T.num_transformed) {   // light.BoundingBox(): the unpadded box
-            const int32_t ik = T.xf_kind[(size_t)j];
-            const int64_t ij = T.xf_index[(size_t)j];
-            const float* ib = &T.xf_inner_box[6 * (size_t)j];
-            v3 imn = ld3(ib), imx = ld3(ib + 3), bmn, bmx;
-            if (ik == kShapeSphere && ij >= 0 && ij < T.num_spheres)
-                shape_sphere_bounds(&T.sphere_center[3 * (size_t)ij], T.sphere_radius[(size_t)ij], imn, imx);
-            else if (ik == kShapeCube && ij >= 0 && ij < T.num_cubes) {
-                imn = ld3(&T.cube_min[3 * (size_t)ij]);
-                imx = ld3(&T.cube_max[3 * (size_t)ij]);
-            }
-            float lo[3], hi[3];
-            shape_xform_boxes(&T.xf_matrix[16 * (size_t)j], ik, imn, imx, lo, hi, bmn, bmx);
-            const float mn[3] = {bmn.x, bmn.y, bmn.z}, mx[3] = {bmx.x, bmx.y, bmx.z};
-            box_light_sphere(mn, mx, lights[i]);
-        } else {
-            continue;
-        }
-        any = true;
-    }
+    for (size_t i = 0; i < lights.size() && i < T.light_kind.size(); i++)
+        any = shape_light_sphere(T, T.light_kind[i], T.light_index[i], lights[i]) || any;
     return any;
+}
+
+void pack_material(const pt_material& m, DevMaterial& o) {
+    for (int k = 0; k < 3; k++) o.color[k] = m.color[k];
+    o.emittance = m.emittance;
+    o.tint = m.tint;
+    o.transparent = m.transparent;
+    o.index = m.index;
+    o.gloss = m.gloss;
+    o.reflectivity = m.reflectivity;
+    o.tex = m.texture - 1; o.ntex = m.normal_texture - 1; o.btex = m.bump_texture - 1; o.gtex = m.gloss_texture - 1;
+    o.bump_multiplier = m.bump_multiplier;
+}
+
+// Scene.Add order (Scene.cs:29-38): MaterialAt(new Vector()).Emittance > 0
+void look_lights(const LookTables& K, const ShapeRefitTables& T, const std::vector<DevMaterial>& mats, LookLights& out) {
+    out = LookLights{};
+    const int32_t num_materials = mats.empty() ? 0 : (int32_t)mats.size() - 1;   // the last is `new Material()`
+    for (size_t i = 0; i < K.slots.size(); i++) {
+        const LookSlot& s = K.slots[i];
+        const int k = s.kind, j = s.index, mat = s.mat;
+        const bool lit = !(mat < 0 || mat >= num_materials || !(mats[(size_t)mat].emittance > 0));
+        // what a later pt_update_volumes tests again with its new windows (VolumeTables)
+        if (s.volume >= 0) out.vol_slots.push_back(VolLightSlot{s.volume, lit ? (int32_t)out.lights.size() : -1});
+        if (!lit) continue;
+        DevLight L{};
+        L.kind = k; L.mat = mat; L.phantom = 0; L.index = s.pos;
+        if (k == PT_SHAPE_SPHERE) {   // Sampler.cs:218-223
+            shape_light_sphere(T, k, j, L);
+        } else if (k == PT_SHAPE_PLANE) {
+            light_sphere_of_box(mk(-1e9, -1e9, -1e9), mk(1e9, 1e9, 1e9), L);  // Plane.BoundingBox
+        } else if (k == PT_SHAPE_TRIANGLE) {  // a directly-added struct Triangle: never passes the identity test
+            L.index = -1; L.phantom = 1;
+            const float* v = &K.tri_verts[(size_t)s.vert];
+            tri_light_sphere(v, v + 3, v + 6, L);
+        } else {   // Cube, SDFShape, Volume: class shapes; TransformedShape: a struct, never identical
+            L.kind = k == PT_SHAPE_CUBE ? KIND_CUBE : k == PT_SHAPE_SDF ? KIND_SDF : k == PT_SHAPE_VOLUME ? KIND_VOLUME : KIND_XFORM;
+            L.phantom = k == PT_SHAPE_TRANSFORMED;
+            if (k == PT_SHAPE_SDF || k == PT_SHAPE_VOLUME) box_light_sphere(&K.fixed_box[6 * i], &K.fixed_box[6 * i + 3], L);   // light.BoundingBox()
+            else shape_light_sphere(T, k, j, L);
+        }
+        out.lights.push_back(L);
+        out.light_slot.push_back((int32_t)i);
+        out.light_tri.push_back(k == PT_SHAPE_TRIANGLE ? j : -1);
+        const bool moves = k == PT_SHAPE_SPHERE || k == PT_SHAPE_CUBE || k == PT_SHAPE_TRANSFORMED;
+        out.light_kind.push_back(moves ? k : -1);
+        out.light_index.push_back(moves ? j : -1);
+    }
+    out.emittance.resize((size_t)num_materials);
+    for (size_t i = 0; i < out.emittance.size(); i++) out.emittance[i] = mats[i].emittance;
+}
+
+void look_flags(const LookTables& K, const std::vector<DevLight>& lights, const std::vector<DevMaterial>& mats,
+                int32_t tri_num_nodes, DevScene& S) {
+    S.lights_lean = 1;
+    for (const DevLight& L : lights)
+        if (!L.phantom && (L.kind == KIND_SDF || L.kind == KIND_VOLUME || L.kind == KIND_XFORM)) S.lights_lean = 0;
+    S.route = (K.route_geom && S.lights_lean && tri_num_nodes > 64) ? 1 : 0;
+    bool mat_tex = false;
+    for (const auto& m : mats) mat_tex = mat_tex || m.tex >= 0 || m.ntex >= 0 || m.btex >= 0 || m.gtex >= 0;
+    S.shade_route = (K.shade_full && !mat_tex && S.lights_lean) ? 1 : 0;   // (a Volume light's colour is FULL work)
 }
 
 void shape_levels(const uint32_t* nodes, int64_t num_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {

@@ -130,6 +130,41 @@ struct VolumeTables {
     std::vector<double> emittance;     // per material of the scene (pt_scene_desc order)
 };
 
+// What pt_update_materials needs beside the device arrays: Scene.Add's light test (Scene.cs:29-38)
+// over tables instead of a pt_scene_desc, so that the upload and a later material edit run one derivation.
+struct LookSlot {
+    int32_t kind, index;   // Scene.Shapes slot: pt_shape_kind and the index of that kind
+    int32_t mat;           // MaterialAt(new Vector()) as an index (a Mesh: -1, `default`; a Volume's follows its windows)
+    int32_t pos;           // DevLight::index if the slot is a light: its position in ana_recs or planes; else -1
+    int32_t vert;          // a loose triangle: its first float in LookTables::tri_verts; else -1
+    int32_t volume;        // a Volume, or a TransformedShape over one: that volume; else -1
+};
+struct LookTables {
+    std::vector<LookSlot> slots;    // Scene.Shapes order
+    std::vector<float> fixed_box;   // per slot 6 floats: BoundingBox of an SDF shape or a Volume (no update moves it)
+    std::vector<float> tri_verts;   // 9 floats per PT_SHAPE_TRIANGLE slot: v1, v2, v3 as the device holds them now
+    std::vector<int32_t> light_slot;   // per entry of the current lights: its slot (LookLights::light_slot, kept here)
+    // the parts of DevScene::route and ::shade_route that no material decides (pt_scene_compile.cpp look_flags)
+    bool route_geom = false, shade_full = false;
+};
+void pack_material(const pt_material& m, DevMaterial& o);
+// The lights of the scene whose materials are `mats` (the scene's own, then `new Material()`), in Scene.Shapes order,
+// with the tables that name each light's source: RefitTables::light_tri, ShapeRefitTables::light_kind and
+// ::light_index, VolumeTables::slots and ::emittance.  A light's sphere comes from where its shape is now: T's current
+// parameters, K.tri_verts, K.fixed_box.
+struct LookLights {
+    std::vector<DevLight> lights;
+    std::vector<int32_t> light_tri, light_kind, light_index;
+    std::vector<int32_t> light_slot;   // per light: the Scene.Shapes slot that registered it
+    std::vector<VolLightSlot> vol_slots;
+    std::vector<double> emittance;
+};
+void look_lights(const LookTables& K, const ShapeRefitTables& T, const std::vector<DevMaterial>& mats, LookLights& out);
+// DevScene::lights_lean, ::route and ::shade_route from those lights and materials; tri_num_nodes: the triangle
+// BVH's node count now.
+void look_flags(const LookTables& K, const std::vector<DevLight>& lights, const std::vector<DevMaterial>& mats,
+                int32_t tri_num_nodes, DevScene& S);
+
 // A compiled scene on the host: every array pt_upload_scene uploads, and the DevScene with every
 // non-pointer field filled.
 struct HostScene {
@@ -162,6 +197,7 @@ struct HostScene {
     BlasRefitTables blas_refit;
     QueryTables query;
     VolumeTables volume_update;
+    LookTables look;
 };
 
 // Validates and compiles.  PT_OK, or an error code with its message in err (H is then partly filled; its

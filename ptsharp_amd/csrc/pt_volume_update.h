@@ -154,7 +154,7 @@ inline bool vol_origin_material(const DevVolume& hdr, const DevWindow* win, int3
     return true;
 }
 // A Scene.Shapes slot that is a Volume or a TransformedShape over one: its volume, and the lights entry the upload
-// registered for it (-1: not a light).
+// (or the last pt_update_materials) registered for it (-1: not a light).
 struct VolLightSlot {
     int32_t volume, light;
 };
@@ -163,7 +163,7 @@ inline bool vol_emissive(int32_t mat, const double* emittance, int32_t num_mater
 }
 // The light test of every slot with the windows an update would leave (win[i]: volume i's rows).  PT_OK and
 // mats[s] = the slot's MaterialAt(origin), or PT_ERR_UNSUPPORTED when a slot's membership would differ from the
-// upload's.  emittance: [num_materials], the scene's own materials (`new Material()`, default_mat = num_materials,
+// current set's (the upload's, or the one the last pt_update_materials left).  emittance: [num_materials], the scene's own materials (`new Material()`, default_mat = num_materials,
 // does not emit).
 inline int vol_update_lights(const VolLightSlot* slots, size_t num_slots, const DevVolume* hdrs, const DevWindow* const* win,
                              const double* emittance, int32_t num_materials, int32_t* mats, const char** why) {
@@ -177,8 +177,8 @@ inline int vol_update_lights(const VolLightSlot* slots, size_t num_slots, const 
         if (mats) mats[s] = m;
         const bool lit = vol_emissive(m, emittance, num_materials);
         if (lit != (slots[s].light >= 0)) {
-            *why = lit ? "a Volume that was no light at the upload would become one: upload the scene again"
-                       : "a Volume registered as a light at the upload would stop being one: upload the scene again";
+            *why = lit ? "a Volume that is no light now would become one: pt_update_materials or an upload changes the lights"
+                       : "a Volume that is a light now would stop being one: pt_update_materials or an upload changes the lights";
             return (int)PT_ERR_UNSUPPORTED;
         }
     }

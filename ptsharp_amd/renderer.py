@@ -660,6 +660,188 @@ class Renderer:
                 "windows": np.array([[wins[k].lo, wins[k].hi] for k in range(nwin)], np.float64).reshape(nwin, 2),
                 "materials": np.array([wins[k].material for k in range(nwin)], np.int32), "runs": runs, "cells": cells}
 
+    def UpdateMaterials(self, updates, env=None, mirror=True) -> float:
+        """New materials and a new environment for the uploaded scene (pt_update_materials).  `updates` is a sequence of
+        (old, new) pairs, or a dict keyed by index: old is a Material of the scene (matched by value, as the scene's
+        materials are; a Material holds a Colour and does not hash, hence the pairs) or its index in the compiled
+        scene's table, new the Material that takes its row.  A texture a new Material names must be one of the
+        uploaded scene's.  `env` is None (the environment stays) or a dict with any of "Color" (a Colour), "Texture" (a
+        ColorTexture of the uploaded scene, or None) and "TextureAngle"; the keys left out keep their values.  The
+        lights and the routing flags follow on the device as at an upload; no geometry is re-sent.  With `mirror` the
+        uploaded FlatScene, the Scene's Color, Texture and TextureAngle, every shape's Material and Scene.Lights are
+        updated, so a later OracleScene(scene) sees the same scene.  Returns the device time of the call's kernels in
+        ms: 0, it launches none."""
+        from .scene import Material
+        self._ensure_scene()
+        flat = self._uploaded
+        nm = len(flat.material_list)
+        new = list(flat.material_list)
+        updates = list(updates.items()) if isinstance(updates, dict) else list(updates or [])
+        for key, val in updates:
+            if isinstance(key, (int, np.integer)):
+                idx = [int(key)]
+            else:
+                idx = [i for i, m in enumerate(flat.material_list) if m.key() == key.key()]
+            if not idx or min(idx) < 0 or max(idx) >= nm:
+                raise ValueError(f"{key!r} is not a material of the uploaded scene")
+            if not isinstance(val, Material):
+                raise ValueError("a material is replaced by a Material")
+            for i in idx:
+                new[i] = val
+
+        def tid(t) -> int:
+            if t is None:
+                return 0
+            for i, o in enumerate(flat.texture_list):
+                if o is t:
+                    return i + 1
+            raise ValueError("a texture that is not in the uploaded scene needs an upload")
+
+        rows = (_abi.pt_material * nm)()
+        for i, m in enumerate(new):
+            rows[i] = _abi.pt_material((C.c_double * 3)(m.Color.r, m.Color.g, m.Color.b), m.Emittance, m.Index, m.Gloss,
+                                       m.Tint, m.Reflectivity, int(bool(m.Transparent)), tid(m.Texture),
+                                       tid(m.NormalTexture), tid(m.BumpTexture), tid(m.GlossTexture), 0, m.BumpMultiplier)
+        u = _abi.pt_material_update()
+        u.num_materials = nm
+        if updates:
+            u.materials = C.cast(rows, C.POINTER(_abi.pt_material))
+        color, tex, angle = self.Scene.Color, self.Scene.Texture, self.Scene.TextureAngle
+        if env is not None:
+            color, tex, angle = env.get("Color", color), env.get("Texture", tex), float(env.get("TextureAngle", angle))
+            u.flags = _abi.LOOK_ENV
+            u.env_color = (C.c_double * 3)(*color.tuple())
+            u.env_texture, u.env_texture_angle = tid(tex), angle
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_update_materials(self._ctx, C.byref(u), C.byref(ms)), "pt_update_materials")
+        if mirror:
+            if updates:
+                swap = {old.key(): m for old, m in zip(flat.material_list, new)}
+                for i in range(nm):
+                    flat.materials[i] = rows[i]
+                flat.material_list[:] = new
+                self._mirror_materials(swap)
+            if env is not None:
+                self.Scene.Color, self.Scene.Texture, self.Scene.TextureAngle = color, tex, angle
+                flat.env, flat.env_texture, flat.env_texture_angle = color.tuple(), tid(tex), angle
+                flat.desc.env_color = (C.c_double * 3)(*flat.env)
+                flat.desc.env_texture, flat.desc.env_texture_angle = flat.env_texture, angle
+        return float(ms.value)
+
+    def _mirror_materials(self, swap) -> None:
+        """Every shape of the Scene takes the Material `swap` maps its own to (by value); Scene.Lights follows."""
+        from .scene import Mesh, SDFShape, TransformedShape, Volume
+        sc = self.Scene
+        seen = set()
+
+        def visit(s):
+            if id(s) in seen:
+                return
+            seen.add(id(s))
+            if isinstance(s, TransformedShape):
+                visit(s.Shape)
+            elif isinstance(s, Mesh):
+                s.materials = [swap.get(m.key(), m) for m in s.materials]
+            elif isinstance(s, Volume):
+                for w in s.Windows:
+                    w.VolumeWindowMaterial = swap.get(w.VolumeWindowMaterial.key(), w.VolumeWindowMaterial)
+            elif hasattr(s, "Material"):
+                s.Material = swap.get(s.Material.key(), s.Material)
+
+        for s in sc.Shapes:
+            visit(s)
+        sc.Lights = [s for s in sc.Shapes if s.MaterialAt().Emittance > 0]
+
+    def ReadMaterials(self) -> dict:
+        """What the device holds of the look (pt_read_materials): a dict with `info` (the pt_look_info), `materials`
+        (the pt_material rows as a ctypes array), `light_rows` [L, 4] int32 (kind, index, material, phantom) and
+        `light_spheres` [L, 4] float64 (centre, radius)."""
+        self._ensure_scene()
+        info = _abi.pt_look_info()
+        _abi.check(self._lib.pt_read_materials(self._ctx, C.byref(info), None, None, None), "pt_read_materials")
+        mats = (_abi.pt_material * max(1, info.num_materials))()
+        rows = np.zeros((info.num_lights, 4), np.int32)
+        spheres = np.zeros((info.num_lights, 4), np.float64)
+        _abi.check(self._lib.pt_read_materials(self._ctx, C.byref(info), C.cast(mats, C.POINTER(_abi.pt_material)),
+                                               rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               spheres.ctypes.data_as(C.POINTER(C.c_double))), "pt_read_materials")
+        return {"info": info, "materials": mats, "light_rows": rows, "light_spheres": spheres}
+
+    def UpdateTextures(self, updates, mirror=True) -> float:
+        """New texels for textures of the uploaded scene (pt_update_textures).  `updates` maps a ColorTexture of the
+        scene, or its index among the compiled scene's textures, to the new image of the same size: a ColorTexture
+        (one that kept its 8-bit source, as NewTexture's do, sends its bytes and its 256-entry Table() and is decoded
+        on the device; any other sends its Data), an [H, W, 3] float64 array, or a pair (uint8 [H, W, 3 or 4], table of
+        256 float64).  With `mirror` the texture's Data is overwritten in place with the new texels, so a later
+        OracleScene(scene) sees the same scene.  Returns the device time of the decode kernels in ms."""
+        from .scene import ColorTexture
+        self._ensure_scene()
+        flat = self._uploaded
+        nt = len(flat.texture_list)
+        imgs = (C.POINTER(_abi.pt_texture_image) * max(1, nt))()
+        keep, decoded, source = [], {}, {}
+        for key, val in dict(updates or {}).items():
+            if isinstance(key, (int, np.integer)):
+                idx = [int(key)]
+            else:
+                idx = [i for i, o in enumerate(flat.texture_list) if o is key]
+            if not idx or min(idx) < 0 or max(idx) >= nt:
+                raise ValueError(f"{key!r} is not a texture of the uploaded scene")
+            src8 = lut = data = None
+            kept = (val.Source8, list(val._ops)) if isinstance(val, ColorTexture) else (None, [])
+            if isinstance(val, ColorTexture):
+                if val.Source8 is not None:
+                    src8, lut = val.Source8, val.Table()
+                else:
+                    data = val.Data
+            elif isinstance(val, tuple):
+                src8, lut = np.ascontiguousarray(val[0], np.uint8), np.ascontiguousarray(val[1], np.float64).reshape(-1)
+            else:
+                data = val
+            for i in idx:
+                t = flat.texture_list[i]
+                im = _abi.pt_texture_image()
+                if src8 is not None:
+                    if src8.ndim != 3 or src8.shape[2] not in (3, 4) or len(lut) != 256:
+                        raise ValueError("an 8-bit image is [H, W, 3 or 4] uint8 with a table of 256 doubles")
+                    im.height, im.width = src8.shape[:2]
+                    im.format = _abi.TEXELS_RGB8 if src8.shape[2] == 3 else _abi.TEXELS_RGBA8
+                    im.data, im.lut = src8.ctypes.data_as(C.c_void_p), lut.ctypes.data_as(C.POINTER(C.c_double))
+                    keep += [src8, lut]
+                    decoded[i] = lambda s=src8, l=lut: l[s[:, :, :3]].reshape(-1, 3)
+                else:
+                    a = np.ascontiguousarray(data, np.float64)
+                    if a.size != 3 * t.Width * t.Height:
+                        raise ValueError(f"texture {i} is {t.Width}x{t.Height}")
+                    im.width, im.height, im.format = t.Width, t.Height, _abi.TEXELS_F64
+                    im.data = a.ctypes.data_as(C.c_void_p)
+                    keep.append(a)
+                    decoded[i] = lambda a=a: a.reshape(-1, 3)
+                keep.append(im)
+                source[i] = kept
+                imgs[i] = C.pointer(im)
+        u = _abi.pt_texture_update()
+        u.num_textures = nt
+        u.images = C.cast(imgs, C.POINTER(C.POINTER(_abi.pt_texture_image)))
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_update_textures(self._ctx, C.byref(u), C.byref(ms)), "pt_update_textures")
+        if mirror:
+            for i, f in decoded.items():
+                t = flat.texture_list[i]
+                t.Data[...] = f()   # the array the FlatScene's pt_texture points at
+                t.Source8, t._ops = source[i][0], list(source[i][1])   # a ColorTexture's 8-bit source and table come along
+        return float(ms.value)
+
+    def ReadTexture(self, i: int) -> np.ndarray:
+        """The texels the device holds for texture i (pt_read_texture): [H, W, 3] float64."""
+        self._ensure_scene()
+        info = (C.c_int32 * 4)()
+        _abi.check(self._lib.pt_read_texture(self._ctx, int(i), info, None), "pt_read_texture")
+        out = np.zeros((int(info[1]), int(info[0]), 3), np.float64)
+        _abi.check(self._lib.pt_read_texture(self._ctx, int(i), info, out.ctypes.data_as(C.POINTER(C.c_double))),
+                   "pt_read_texture")
+        return out
+
     def UpdateMeshes(self, v1, v2, v3, n1=None, n2=None, n3=None, normals=None) -> float:
         """UpdateTriangles for a scene that may hold instanced meshes (pt_update_meshes; UpdateTriangles refuses
         such a scene): new vertex positions for every triangle of the scene, instanced meshes' included, with the

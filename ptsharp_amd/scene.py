@@ -99,6 +99,10 @@ class ColorTexture:
     def __init__(self, width: int, height: int, data):
         self.Width, self.Height = int(width), int(height)
         self.Data = np.ascontiguousarray(np.asarray(data, np.float64).reshape(self.Height * self.Width, 3))
+        # a texture made from an 8-bit image keeps it: every texel channel is then Table()[byte] (Renderer.UpdateTextures
+        # sends the bytes and the table instead of Data)
+        self.Source8 = None   # uint8 [Height, Width, 3 or 4], or None for a texture made from doubles
+        self._ops = []        # the ("pow" | "mul", a) applied since NewTexture, in order
 
     @staticmethod
     def NewTexture(rgb8) -> "ColorTexture":
@@ -106,7 +110,21 @@ class ColorTexture:
         a = np.asarray(rgb8)
         h, w = a.shape[:2]
         gamma = float(np.float32(2.2))   # Pow(2.2F): the float literal widened to double
-        return ColorTexture(w, h, (a[:, :, :3].astype(np.float64) / 255) ** gamma)
+        t = ColorTexture(w, h, (a[:, :, :3].astype(np.float64) / 255) ** gamma)
+        if a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] in (3, 4):
+            t.Source8 = np.ascontiguousarray(a)
+        return t
+
+    def Table(self):
+        """The 256 doubles t with Data[y * Width + x, c] == t[Source8[y, x, c]]: NewTexture's (byte / 255) ** 2.2F, then
+        every Pow and MulScalar since, each applied to the table as it was applied to Data.  None for a texture that
+        has no 8-bit source."""
+        if self.Source8 is None:
+            return None
+        t = (np.arange(256).astype(np.float64) / 255) ** float(np.float32(2.2))
+        for op, a in self._ops:
+            t = t ** a if op == "pow" else t * a
+        return np.ascontiguousarray(t)
 
     @staticmethod
     def LoadTexture(path: str) -> "ColorTexture":
@@ -122,10 +140,12 @@ class ColorTexture:
 
     def Pow(self, a: float) -> "ColorTexture":   # ITexture.Pow (Texture.cs:170-177), in place
         self.Data = self.Data ** float(a)
+        self._ops.append(("pow", float(a)))
         return self
 
     def MulScalar(self, a: float) -> "ColorTexture":   # ITexture.MulScalar (Texture.cs:179-186), in place
         self.Data = self.Data * float(a)
+        self._ops.append(("mul", float(a)))
         return self
 
 
