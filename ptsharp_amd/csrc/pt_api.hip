@@ -771,6 +771,7 @@ static pt::PassKnobs read_pass_knobs() {
     if (const char* f = std::getenv("PT_LINEAR")) k.linear = !std::strcmp(f, "0") ? 0 : -1;
     if (const char* f = std::getenv("PT_SIDE_STREAM")) k.side_stream = !std::strcmp(f, "1") ? 1 : !std::strcmp(f, "0") ? 0 : -1;
     if (const char* f = std::getenv("PT_SHADOW_TAIL")) k.tail_early = !std::strcmp(f, "early") ? 1 : 0;
+    if (const char* f = std::getenv("PT_ESCAPE_DROP")) k.escape_drop = !std::strcmp(f, "0") ? 0 : !std::strcmp(f, "all") ? 2 : 1;
     if (const char* f = std::getenv("PT_BATCH_MAX_PASSES")) k.batch_max_passes = std::max(1LL, std::atoll(f));
     if (const char* f = std::getenv("PT_WF_MAX_CAP")) {
         k.wf_max_cap_set = true;

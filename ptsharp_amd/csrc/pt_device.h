@@ -1440,6 +1440,12 @@ __device__ __forceinline__ void bounce_dir(const DevMaterial& m, const Shade& sh
     }
 }
 
+// The origin alone of bounce_dir's ray (the same expressions): the vertex, or past it along the refracted direction.
+__device__ __forceinline__ v3 bounce_origin(const DevMaterial& m, const Shade& sh, v3 indir, bool refl, double n1, double n2) {
+    if (refl || !m.transparent) return sh.pos;
+    return add(sh.pos, muls(refract(sh.nrm, indir, n1, n2), 1e-4));
+}
+
 // Sampler.sampleLight (Sampler.cs:212-296) up to the shadow query: the sampled
 // direction and the colour the light contributes if it is the nearest hit
 // (coverage depends only on the light centre/radius, so it is computed here).

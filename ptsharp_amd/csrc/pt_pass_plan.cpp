@@ -192,6 +192,10 @@ WfChoice choose_kernels(const WfChoiceInput& in) {
     c.sdf_hits = queue(split && in.num_sdf > 0, in.sdf_lds);
     c.vol_shadow = queue(split_sh && in.volq_sh && in.num_vol > 0, in.vol_lds);
     c.sdf_shadow = queue(split_sh && in.num_sdf > 0, in.sdf_lds);
+    // The dropping shade: only where k_wf_trace_head decides the child rays (so the analytic shapes are linear or
+    // absent, no row-4 kind, no split), the shade is the lean one, and a miss adds nothing (the head's env_black).
+    const bool drop = k.escape_drop != 0 && c.trace == WF_HEAD && c.shade == WF_SHADE_LEAN && in.env_black && in.env_tex < 0;
+    c.escape_drop_depths = !drop ? 0 : k.escape_drop == 2 ? kEscapeDropEveryDepth : kEscapeDropDepths;
     return c;
 }
 

@@ -77,6 +77,8 @@ struct PassKnobs {
     int32_t linear = -1;        // PT_LINEAR=0: no linear kernels; else -1, where they apply
     int32_t side_stream = -1;   // PT_SIDE_STREAM=0|1: one stream / the side stream; else -1, by the chunk's rays
     int32_t tail_early = 0;     // PT_SHADOW_TAIL=early: 1 (WfQueues::tail_early)
+    int32_t escape_drop = 1;    // PT_ESCAPE_DROP=0: shade queues every child; all: 2, the dropping shade at every depth;
+                                // else 1, where choose_kernels finds it applies (WfChoice::escape_drop)
     int64_t batch_max_passes = 0;          // PT_BATCH_MAX_PASSES: its value, at least 1; 0: not set
     bool wf_max_cap_set = false;           // PT_WF_MAX_CAP is set, to
     unsigned long long wf_max_cap = 0;     // this many entries (read once per context: wf_max_cap() in pt_api.hip)
@@ -164,7 +166,8 @@ struct WfChoiceInput {
     int32_t full = 0, full_geom = 0, tri_num_nodes = 0, ana_num_nodes = 0, ana_count = 0, ana_linear = 0, num_planes = 0;
     int32_t num_sdf = 0, num_vol = 0, num_lights = 0, lights_lean = 0, shade_route = 0, env_tex = -1, sdf_lds = 0, vol_lds = 0;
     bool volq = false, volq_sh = false;   // WfQueues::volq / volq_sh are allocated (they outlive a scene without Volumes)
-    PassKnobs knobs;                      // lanes, head, linear, tail_early
+    bool env_black = false;               // DevScene::env is {0, 0, 0} (with env_tex < 0: a miss adds nothing)
+    PassKnobs knobs;                      // lanes, head, linear, tail_early, escape_drop
     bool counted = false;
 };
 
@@ -180,7 +183,16 @@ struct WfChoice {
     // what caps each launch's grid: [0] the step's first kernel, [1] its second (WF_HEAD: the list-fed kernel,
     // WF_SPLIT: the FULL half; otherwise as [0]).  The linear kernels launch exactly their member's blocks.
     WfGrid trace_grid[2] = {G_TRACE, G_TRACE}, shadow_grid[2] = {G_SHADOW, G_SHADOW};
+    // The dropping form of the lean shade (k_wf_shade<.., DROP>: a child ray that k_wf_trace_head would turn into a
+    // miss with nothing to shade is counted and not queued) runs at the depths below this one; 0: at none.
+    int32_t escape_drop_depths = 0;
+    bool escape_drop(int depth) const { return depth < escape_drop_depths; }
 };
+// Depths of the dropping shade under the default rule (PassKnobs::escape_drop 1): the camera hits only.  Their
+// children are the first bounce, where most rays leave the scene; deeper, the head lists 84-94 % of the rays
+// (DESIGN.md §8 has both rules measured).
+constexpr int32_t kEscapeDropDepths = 1;
+constexpr int32_t kEscapeDropEveryDepth = 1 << 30;
 
 WfChoice choose_kernels(const WfChoiceInput& in);
 

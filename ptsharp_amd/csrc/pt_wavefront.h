@@ -127,7 +127,7 @@ struct WfGrids {
 
 // One pass on the wavefront engine, as its launches take it: the context's grids, the host's plan (chunk,
 // chunk_extra, the children per sample) and the switches that choose kernels (shade_form, lanes, head, head_stats,
-// linear: choose_kernels), all by value (pt_pass_plan.h), and the side stream's handles.
+// linear, escape_drop: choose_kernels), all by value (pt_pass_plan.h), and the side stream's handles.
 struct WfPlan : WfGrids, PassPlan, PassKnobs {
     // Optional second stream (PassPlan::use_side): each depth's shadow pass runs there, beside the next depth's
     // closest-hit pass (independent queues), so one fills the other's ramp and tail.

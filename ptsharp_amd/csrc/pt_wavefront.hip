@@ -936,8 +936,11 @@ __global__ __launch_bounds__(kTB, PT_LANES_WAVES) __attribute__((amdgpu_num_vgpr
 // that reaches it gets its provisional hit in Q.hits and its slot in the partition's list, in slot order
 // inside the block's claim of kHeadRows rows of 256 slots (the child-major order of 64-ray batches survives
 // within a claim), reserved with one atomic per claim.
+// STATS (PT_HEAD_STATS=1, never a timed run): the rays decided here as a miss with nothing to shade, added to
+// counters[kEscapeStatCounter].
 constexpr uint32_t kHeadRows = 4;
-template <bool COUNT>
+constexpr int kEscapeStatCounter = 16;   // DevBuffer::counters word (no other kernel's; not read back by the pass)
+template <bool COUNT, bool STATS = false>
 __global__ __launch_bounds__(256) void k_wf_trace_head(DevScene S, WfQueues Q, int qi, unsigned long long* counters) {
     const Group G = xcd_group();
     const uint32_t n = min(*ray_count(Q, qi, G.g), Q.pcap), base = G.g * Q.pcap;
@@ -946,6 +949,7 @@ __global__ __launch_bounds__(256) void k_wf_trace_head(DevScene S, WfQueues Q, i
     const bool env_black = (!FULL_SHADE_ENV(S)) && S.env[0] == 0.f && S.env[1] == 0.f && S.env[2] == 0.f;
     Counters ctr{0, 0, 0, 0};
     uint32_t kept = 0;
+    uint32_t escaped = 0;   // STATS
     __shared__ uint32_t s_wcnt[kHeadRows * 4];
     __shared__ uint32_t s_at;
     for (uint32_t k0 = G.lb * (256u * kHeadRows); k0 < n; k0 += G.nb * (256u * kHeadRows)) {   // block-uniform
@@ -984,6 +988,7 @@ __global__ __launch_bounds__(256) void k_wf_trace_head(DevScene S, WfQueues Q, i
             hit_store(&Q.hits[i], make_uint4((uint32_t)tb, (uint32_t)(tb >> 32), (uint32_t)bkind, (uint32_t)bidx));
             if (reach) listed |= 1u << j;
             else kept += (bkind >= 0 || !env_black) ? 1u : 0u;
+            if (STATS && !reach && bkind < 0 && env_black) escaped++;
         }
         uint64_t bal[kHeadRows];
 #pragma unroll
@@ -1016,6 +1021,29 @@ __global__ __launch_bounds__(256) void k_wf_trace_head(DevScene S, WfQueues Q, i
         uint32_t prims = wave_sum(ctr.prims);
         if (lane == 0 && prims) atomicAdd(&counters[2], (unsigned long long)prims);
     }
+    if (STATS) {
+        escaped = wave_sum(escaped);
+        if (lane == 0 && escaped) atomicAdd(&counters[kEscapeStatCounter], (unsigned long long)escaped);
+    }
+}
+
+// Would k_wf_trace_head turn the ray (o, d), as ray_store is about to write it, into a miss and list nothing?  The
+// head's own operations in the head's order: no plane hit, no hit among the linear analytic records, and the
+// triangle BVH's root box not reached within tmax_bound(kHitInf) (nothing was hit).  True: the head would write
+// {kHitInf, -1, -1} to Q.hits; under a black, untextured environment no later kernel has work for that ray.
+__device__ __forceinline__ bool head_misses(const DevScene& S, v3 o, v3 d) {
+    const v3 invd{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    for (int p = 0; p < S.num_planes; p++) {
+        const float4 pa = S.planes[2 * p], pb = S.planes[2 * p + 1];
+        if (isect_plane(v3{pa.x, pa.y, pa.z}, v3{pb.x, pb.y, pb.z}, o, d) < kHitInf) return false;
+    }
+    if (S.ana_linear) {
+        for (int p = 0; p < S.ana_count; p++) {
+            int32_t kind;
+            if (prim_t<false, false>(S, S.ana_recs, (uint32_t)p, o, d, kind) < kHitInf) return false;
+        }
+    }
+    return !tri_reach(S, o, invd, tmax_bound(kHitInf));
 }
 
 // ---------------------------------------------------------------- shade / bounce
@@ -1032,12 +1060,12 @@ __global__ __launch_bounds__(256) void k_wf_trace_head(DevScene S, WfQueues Q, i
 // traversal kernel (ray + stack state only).
 // One queued vertex (slot i of partition G.g; `alive` false: the lane only takes part in
 // the block's reservation and ballots).  Block-uniform call.
-template <bool FULL>
+template <bool FULL, bool DROP, bool HOLD>
 __device__ __forceinline__ void shade_children(const DevScene& S, const DevSampler& smp, const WfQueues& Q, int qi,
                                                const Group& G, const Shade& sh, v3 d, int depth, uint64_t node,
                                                uint32_t pixel, const double (&t2)[3], double pv, double n1, double n2,
-                                               int nn, int nm, int nch);
-template <bool COUNT, bool FULL>
+                                               int nn, int nm, int nch, uint32_t& dropped);
+template <bool COUNT, bool FULL, bool DROP, bool HOLD = false>
 __device__ __forceinline__ void shade_vertex(const DevScene& S, const DevSampler& smp, const WfQueues& Q, int qi,
                                              const Group& G, uint32_t i, bool alive, Counters& ctr,
                                              const uint4* hl = nullptr) {   // hl: the hit record, already in LDS
@@ -1100,16 +1128,39 @@ __device__ __forceinline__ void shade_vertex(const DevScene& S, const DevSampler
         pv = vertex_p(m, sh, d, n1, n2);
     }
     fix_add_wave(Q.acc, pixel, has_c, cc[0], cc[1], cc[2]);
-    shade_children<FULL>(S, smp, Q, qi, G, sh, d, depth, node, pixel, t2, pv, n1, n2, nn, nm, nch);
+    shade_children<FULL, DROP, HOLD>(S, smp, Q, qi, G, sh, d, depth, node, pixel, t2, pv, n1, n2, nn, nm, nch, ctr.rays);
 }
 // The children of a shaded vertex (Sampler.cs:96-131): mode, reflect decision and liveness, the block's
 // child-major reservation of extension rays and NEE requests, sampleLights up to the shadow query, Ray.Bounce.
 // nch 0: the lane only takes part in the block's reservation and ballots.  Block-uniform call.
-template <bool FULL>
+// DROP (lean only; choose_kernels says where: WfChoice::escape_drop): the slots are reserved before any bounce is
+// computed, so the first sweep also computes each extension child's ray and asks head_misses of it.  A child it
+// answers for is one Scene.Intersect call (added to `dropped`; the kernel adds them to the pass' counters) and
+// nothing else: it is in no count, so the reservation, the child-major order and every store see the survivors
+// only.  The second sweep computes a survivor's ray again (keyed draws: the same bits), except in a wave of one
+// child per vertex (every depth >= 1), which keeps the first sweep's ray.  A dropped diffuse child's NEE requests
+// are made as ever.
+// HOLD (the direct form, whose block has the LDS for it): the first sweep leaves the directions of a lane's first
+// kDropHold children in LDS and the second sweep takes a survivor's from there (its origin is the vertex, or
+// bounce_origin's offset one): no ray is computed twice.  Each lane reads its own words only.
+constexpr int kDropHold = 8;
+template <bool HOLD>
+__device__ __forceinline__ float* drop_hold() {
+    if constexpr (HOLD) {
+        __shared__ float s_nd[3 * kDropHold * 256];
+        return s_nd;
+    } else {
+        return nullptr;
+    }
+}
+template <bool FULL, bool DROP, bool HOLD>
 __device__ __forceinline__ void shade_children(const DevScene& S, const DevSampler& smp, const WfQueues& Q, int qi,
                                                const Group& G, const Shade& sh, v3 d, int depth, uint64_t node,
                                                uint32_t pixel, const double (&t2)[3], double pv, double n1, double n2,
-                                               int nn, int nm, int nch) {
+                                               int nn, int nm, int nch, uint32_t& dropped) {
+    static_assert(!(FULL && DROP), "the dropping form is a lean shade");
+    static_assert(DROP || !HOLD, "only the dropping form holds directions");
+    float* const hold = drop_hold<HOLD>();
     const int qo = 1 - qi;
     const bool nee_on = smp.dl && S.num_lights > 0;
     const int nl = S.num_lights;
@@ -1131,12 +1182,35 @@ __device__ __forceinline__ void shade_children(const DevScene& S, const DevSampl
     const bool block_major = smp.fh <= kBlockMajorFH;   // kernel-uniform: every depth's children fit s_cc
     uint32_t n_ext = 0, n_nee = 0;
     uint64_t rbits = 0;   // the reflect decisions of children 0..63, kept for the second loop (one draw each)
+    uint64_t dbits = 0;   // DROP: the children 0..63 whose extension ray is dropped
+    v3 no1 = zero3(), nd1 = zero3();   // DROP: the first sweep's last ray (the second sweep's, when cmax is 1)
+    // child c's extension ray (Ray.Bounce with the stratum's jittered u, v)
+    auto child_ray = [&](int c, uint64_t E, bool refl, v3& no, v3& nd) {
+        const int stratum = nm == 2 ? c >> 1 : c;
+        const int u = rn != 0.0 ? stratum >> lg : stratum / nn, v = rn != 0.0 ? stratum & (nn - 1) : stratum % nn;
+        const double fu = div_strata((double)u + draw(E, D_STRATUM_U), nn, rn);
+        const double fv = div_strata((double)(float)v + draw(E, D_STRATUM_V), nn, rn);
+        bounce_dir(m, sh, d, fu, fv, refl, n1, n2, E, no, nd);
+    };
     for (int c = 0; c < cmax; c++) {   // wave-uniform trip count: the ballots need every lane
         const int mode = ma + (nm == 2 ? c & 1 : 0);   // nm is 1 or 2
         const bool refl = mode == 2 || (mode == 0 && c < nch && draw(child_key(node, (uint32_t)c), D_REFLECT) < pv);
         rbits |= refl && c < 64 ? 1ull << c : 0ull;
         const bool live = c < nch && (mode == 0 || (refl ? pv > 0 : (1 - pv) > 0));
-        const bool ee = live && ext_on, en = live && !refl && !m.transparent && nee_on;
+        bool ee = live && ext_on;
+        const bool en = live && !refl && !m.transparent && nee_on;
+        if (DROP && ee) {
+            child_ray(c, child_key(node, (uint32_t)c), refl, no1, nd1);
+            if (head_misses(S, no1, nd1)) {
+                ee = false;
+                dbits |= c < 64 ? 1ull << c : 0ull;
+                dropped++;
+            } else if (HOLD && c < kDropHold) {
+                hold[(3 * c + 0) * 256 + threadIdx.x] = nd1.x;
+                hold[(3 * c + 1) * 256 + threadIdx.x] = nd1.y;
+                hold[(3 * c + 2) * 256 + threadIdx.x] = nd1.z;
+            }
+        }
         n_ext += ee ? 1u : 0u;
         n_nee += en ? rays_per_nee : 0u;
         if (block_major) {
@@ -1165,7 +1239,18 @@ __device__ __forceinline__ void shade_children(const DevScene& S, const DevSampl
         const bool live = c < nch && (mode == 0 || (refl ? pv > 0 : (1 - pv) > 0));
         const bool reflected = refl || m.transparent;                 // specular branch (Sampler.cs:109-115)
         const bool emit_nee = live && !reflected && nee_on;
-        const bool emit_ext = live && ext_on;
+        bool emit_ext = live && ext_on;
+        v3 no, nd;
+        bool have_ray = false;   // DROP, children >= 64: the ray, computed here for the decision
+        if (DROP && emit_ext) {
+            if (c < 64) {
+                emit_ext = !((dbits >> c) & 1ull);
+            } else {
+                child_ray(c, E, refl, no, nd);
+                have_ray = true;
+                emit_ext = !head_misses(S, no, nd);
+            }
+        }
         const uint64_t bn = __ballot(emit_nee), be = __ballot(emit_ext);
         uint32_t pe = 0, pn = 0, te = (uint32_t)__popcll(be), tn = (uint32_t)__popcll(bn);
         if (block_major) {   // waves before this one, and the whole block's total, at child c
@@ -1213,13 +1298,15 @@ __device__ __forceinline__ void shade_children(const DevScene& S, const DevSampl
                 }
             }
         }
-        if (!ext_on) continue;
-        const int stratum = nm == 2 ? c >> 1 : c;
-        const int u = rn != 0.0 ? stratum >> lg : stratum / nn, v = rn != 0.0 ? stratum & (nn - 1) : stratum % nn;
-        const double fu = div_strata((double)u + draw(E, D_STRATUM_U), nn, rn);
-        const double fv = div_strata((double)(float)v + draw(E, D_STRATUM_V), nn, rn);
-        v3 no, nd;
-        bounce_dir(m, sh, d, fu, fv, refl, n1, n2, E, no, nd);
+        if (DROP ? !emit_ext : !ext_on) continue;
+        if (HOLD && c < kDropHold) {
+            no = bounce_origin(m, sh, d, refl, n1, n2);
+            nd = v3{hold[(3 * c + 0) * 256 + threadIdx.x], hold[(3 * c + 1) * 256 + threadIdx.x], hold[(3 * c + 2) * 256 + threadIdx.x]};
+        } else if (DROP && cmax == 1) {   // (wave-uniform)
+            no = no1; nd = nd1;
+        } else if (!(DROP && have_ray)) {
+            child_ray(c, E, refl, no, nd);
+        }
         if (my_e < Q.pcap) {
             const double nthr[3] = {t2[0] * w[0], t2[1] * w[1], t2[2] * w[2]};
             ray_store(Q, qo, G.g * Q.pcap + my_e, no, nd, nthr, pixel, (uint32_t)(depth + 1) | ((reflected ? 1u : 0u) << 8),
@@ -1269,7 +1356,7 @@ __device__ __forceinline__ DevScene stage_shading(const DevScene& S0) {
     return S;
 }
 
-template <bool COUNT, bool FULL, bool SCAN>
+template <bool COUNT, bool FULL, bool SCAN, bool DROP = false>
 __global__ __launch_bounds__(256, FULL ? PT_FULL_SHADE_WAVES : PT_SHADE_WAVES) void k_wf_shade(DevScene S0, DevSampler smp, WfQueues Q, int qi,
                                                                   unsigned long long* counters, int form) {
     const DevScene& S = S0;   // the kernel argument until the block knows it runs (stage_shading below)
@@ -1283,7 +1370,9 @@ __global__ __launch_bounds__(256, FULL ? PT_FULL_SHADE_WAVES : PT_SHADE_WAVES) v
     const bool routed = S.shade_route != 0;
     const bool scan = routed ? true
                     : form ? form == 2
-                           : FULL ? 2ull * kept < (unsigned long long)queued
+                           // (the dropping form: its direct kernel holds the children's directions in LDS, which the
+                           // SCAN kernel's lists leave no room for, so it stays direct down to half kept)
+                           : FULL || DROP ? 2ull * kept < (unsigned long long)queued
                                                      : 32ull * kept < 31ull * (unsigned long long)queued;
     if (scan != SCAN) return;
     const DevScene Sv = PT_SHADE_LDS ? stage_shading(S0) : S0;
@@ -1313,7 +1402,7 @@ __global__ __launch_bounds__(256, FULL ? PT_FULL_SHADE_WAVES : PT_SHADE_WAVES) v
             __syncthreads();
             const uint32_t k0 = s_k0;  // thread 0 rewrites it only after block_reserve2's barriers
             if (k0 >= n) break;
-            shade_vertex<COUNT, FULL>(Sv, smp, Q, qi, G, base + k0 + threadIdx.x, k0 + threadIdx.x < n, ctr);
+            shade_vertex<COUNT, FULL, DROP, DROP>(Sv, smp, Q, qi, G, base + k0 + threadIdx.x, k0 + threadIdx.x < n, ctr);
         }
     } else {
         const bool env_black = (!FULL || S.env_tex < 0) && S.env[0] == 0.f && S.env[1] == 0.f && S.env[2] == 0.f;
@@ -1378,7 +1467,7 @@ __global__ __launch_bounds__(256, FULL ? PT_FULL_SHADE_WAVES : PT_SHADE_WAVES) v
             const uint32_t full = last ? total : total & ~255u;
             for (uint32_t r = 0; r < full; r += 256u) {   // block-uniform
                 const bool listed = r + threadIdx.x < full;
-                shade_vertex<COUNT, FULL>(Sv, smp, Q, qi, G, base + (listed ? s_list[r + threadIdx.x] : 0u), listed, ctr,
+                shade_vertex<COUNT, FULL, DROP>(Sv, smp, Q, qi, G, base + (listed ? s_list[r + threadIdx.x] : 0u), listed, ctr,
                                           &s_hit[r + threadIdx.x]);
                 __syncthreads();   // the next round rewrites shade_vertex's LDS child counts
             }
@@ -1394,6 +1483,13 @@ __global__ __launch_bounds__(256, FULL ? PT_FULL_SHADE_WAVES : PT_SHADE_WAVES) v
     if (COUNT) {
         uint32_t shades = wave_sum(ctr.shades);
         if ((threadIdx.x & 63) == 0) atomicAdd(&counters[3], (unsigned long long)shades);
+    }
+    if (DROP) {   // the dropped children: Scene.Intersect calls, each with the head's analytic tests
+        const uint32_t rays = wave_sum(ctr.rays);
+        if ((threadIdx.x & 63) == 0 && rays) {
+            atomicAdd(&counters[0], (unsigned long long)rays);
+            if (COUNT && S.ana_linear) atomicAdd(&counters[2], (unsigned long long)rays * (unsigned long long)S.ana_count);
+        }
     }
 }
 
@@ -2236,6 +2332,7 @@ static WfChoiceInput choice_input(const DevScene& S, const WfQueues& Q, const Wf
     in.num_vol = S.num_vol; in.num_lights = S.num_lights; in.lights_lean = S.lights_lean; in.shade_route = S.shade_route;
     in.env_tex = S.env_tex; in.sdf_lds = S.sdf_lds; in.vol_lds = S.vol_lds;
     in.volq = Q.volq != nullptr; in.volq_sh = Q.volq_sh != nullptr;
+    in.env_black = S.env[0] == 0.f && S.env[1] == 0.f && S.env[2] == 0.f;
     in.knobs = plan;
     in.knobs.tail_early = Q.tail_early;
     in.counted = count;
@@ -2253,19 +2350,32 @@ static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const Dev
     const bool head = ch.trace == WF_HEAD;   // (then the shadow family is WF_HEAD too)
     const hipStream_t side = plan.side ? plan.side : stream;
     // PT_HEAD_STATS=1 (a diagnostic, not for timed runs: it waits for both streams at every depth): the listed
-    // share of each depth's closest-hit and shadow rays, from the list counts, to stderr
+    // share of each depth's closest-hit and shadow rays, from the list counts, to stderr; of the closest-hit rays,
+    // those the head decided as a miss with nothing to shade (k_wf_trace_head<.., STATS>); and the child rays the
+    // dropping shade of that depth's vertices did not queue (what it added to the rays counted since the head)
+    unsigned long long stat_escaped = 0, stat_rays = 0;   // counters[kEscapeStatCounter] and [0] at the last closest hit
     auto list_stats = [&](int depth, int q, bool shadow) {   // after the closest hit of queue q / the shadow pass of set q
         if (!head || !plan.head_stats) return;
         (void)hipStreamSynchronize(stream);
         (void)hipStreamSynchronize(side);
         std::vector<uint32_t> w(kCountWords);
         if (hipMemcpy(w.data(), Q.counts, kCountWords * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return;
+        unsigned long long c[kEscapeStatCounter + 1];
+        if (hipMemcpy(c, B.counters, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return;
         unsigned long long rays = 0, listed = 0;
         for (int g = 0; g < kParts; g++) {
             rays += shadow ? std::min(w[count_word(q * kParts + g) + 1], Q.spcap) : std::min(w[count_word(q * kParts + g)], Q.pcap);
             listed += shadow ? w[list_sh_word(q, g)] : w[list_word(g)];
         }
         std::fprintf(stderr, "head depth %d: %s %llu listed of %llu\n", depth, shadow ? "shadow" : "closest hit", listed, rays);
+        if (shadow) {
+            std::fprintf(stderr, "head depth %d: shade dropped %llu child rays\n", depth, c[0] - stat_rays);
+        } else {
+            std::fprintf(stderr, "head depth %d: closest hit %llu of %llu missed with nothing to shade\n", depth,
+                         c[kEscapeStatCounter] - stat_escaped, rays);
+            stat_escaped = c[kEscapeStatCounter];
+            stat_rays = c[0];
+        }
     };
     using RayKernel = void (*)(DevScene, WfQueues, int, unsigned long long*);
     using QueueKernel = void (*)(DevScene, WfQueues, int);
@@ -2297,7 +2407,7 @@ static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const Dev
             queue(ch.sdf_hits, k_wf_sdf_hits<false>, k_wf_sdf_hits<true>, n, 8192, S.sdf_lds, stream, qi);
             break;
         case WF_HEAD:
-            head_pass(k_wf_trace_head<COUNT>, n, g0, stream, qi);
+            head_pass(plan.head_stats ? k_wf_trace_head<COUNT, true> : k_wf_trace_head<COUNT, false>, n, g0, stream, qi);
             traverse(k_wf_trace_lanes<COUNT, false, true>, n, g1, stream, qi);
             break;
         case WF_FULL: traverse(k_wf_trace<COUNT, true>, n, g0, stream, qi); break;
@@ -2334,6 +2444,11 @@ static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const Dev
         end_k(3, side);
     };
     int qi = 0;
+    if (head && plan.head_stats) {   // (a pass' later chunks: the head's count so far)
+        (void)hipStreamSynchronize(stream);
+        (void)hipStreamSynchronize(side);
+        (void)hipMemcpy(&stat_escaped, B.counters + kEscapeStatCounter, sizeof stat_escaped, hipMemcpyDeviceToHost);
+    }
     trace(qi, bound);
     list_stats(0, qi, false);
     for (int depth = 0; depth <= smp.mb; depth++) {
@@ -2347,7 +2462,10 @@ static hipError_t depth_loop(const DevScene& S, const DevSampler& smp, const Dev
         switch (ch.shade) {
         case WF_SHADE_ROUTED: shade(k_wf_shade<COUNT, false, true>); shade(k_wf_shade<COUNT, true, true>); break;
         case WF_SHADE_FULL: shade(k_wf_shade<COUNT, true, false>); shade(k_wf_shade<COUNT, true, true>); break;
-        case WF_SHADE_LEAN: shade(k_wf_shade<COUNT, false, false>); shade(k_wf_shade<COUNT, false, true>); break;
+        case WF_SHADE_LEAN:
+            if (ch.escape_drop(depth)) { shade(k_wf_shade<COUNT, false, false, true>); shade(k_wf_shade<COUNT, false, true, true>); }
+            else { shade(k_wf_shade<COUNT, false, false>); shade(k_wf_shade<COUNT, false, true>); }
+            break;
         }
         if (ch.shade_miss)   // a routed shade's misses of a textured environment
             hipLaunchKernelGGL(k_wf_shade_miss, dim3(grid_for(bound, 256, 8192)), dim3(256), 0, stream, S, Q, qi);
