@@ -232,6 +232,25 @@ namespace PTSharpCore
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_skin_desc
+        {
+            public int num_triangles;      // must equal the uploaded scene's num_triangles
+            public int num_bones;          // 1..PT_SKIN_MAX_BONES
+            public fixed int reserved[2];  // 0
+            public IntPtr bone1, bone2, bone3;        // [num_triangles][4] int each: the bones of corner 1, 2, 3, every one in [0, num_bones)
+            public IntPtr weight1, weight2, weight3;  // [num_triangles][4] float each: their weights; +-0: the influence is dead
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_mesh_skin
+        {
+            public int num_bones;          // must equal the installed skin's num_bones
+            public int normals_mode;       // 0: the blend of MulDirection of the rest normals; PT_NORMALS_FACE; PT_NORMALS_SMOOTH
+            public fixed int reserved[2];  // 0
+            public IntPtr matrices;        // [num_bones][16] double, row-major, required
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         public unsafe struct pt_volume_update
         {
             public int num_volumes;        // must equal the uploaded scene's
@@ -322,7 +341,12 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_set_rest_pose(IntPtr ctx, int numTriangles, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_pose_meshes(IntPtr ctx, ref pt_mesh_pose u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_pose(IntPtr ctx, float[] v1, float[] v2, float[] v3, float[] n1, float[] n2, float[] n3);
-        // pt_update_meshes that also re-sorts the world triangle BVH on the device (u = IntPtr.Zero: the staged pose), and the tree's cost
+        // Blend skinning on the device: four bones and weights per corner sent once, one matrix per bone per call, then pt_update_meshes' refits
+        public const int PT_SKIN_INFLUENCES = 4, PT_SKIN_MAX_BONES = 65536;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_set_skin(IntPtr ctx, ref pt_skin_desc desc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_skin_meshes(IntPtr ctx, ref pt_mesh_skin u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_skin(IntPtr ctx, int[] bone1, int[] bone2, int[] bone3, float[] weight1, float[] weight2, float[] weight3);
+        // pt_update_meshes that also re-sorts the world triangle BVH on the device (u = IntPtr.Zero: the staged pose or skin), and the tree's cost
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, ref pt_mesh_update u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, IntPtr u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_tri_bvh_cost(IntPtr ctx, double[] out3);
@@ -888,7 +912,52 @@ namespace PTSharpCore
             }
         }
 
-        /// <summary>The six arrays the last PoseMeshes left on the device (pt_read_pose), 3 floats per triangle each:
+        /// <summary>Installs the skin SkinMeshes blends with (pt_set_skin): bones[c] and weights[c] hold four bone
+        /// indices and four weights per triangle for corner c + 1 of every triangle of the uploaded scene; a weight of
+        /// 0 makes its influence dead.  Kept on the device until the next upload.</summary>
+        public void SetSkin(int[][] bones, float[][] weights, int numBones)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            try
+            {
+                IntPtr Pin(object a) { var h = GCHandle.Alloc(a, GCHandleType.Pinned); held.Add(h); return h.AddrOfPinnedObject(); }
+                var d = new PtHip.pt_skin_desc
+                {
+                    num_triangles = bones[0].Length / PtHip.PT_SKIN_INFLUENCES, num_bones = numBones,
+                    bone1 = Pin(bones[0]), bone2 = Pin(bones[1]), bone3 = Pin(bones[2]),
+                    weight1 = Pin(weights[0]), weight2 = Pin(weights[1]), weight3 = Pin(weights[2]),
+                };
+                PtHip.Check(PtHip.pt_set_skin(ctx, ref d), "pt_set_skin");
+            }
+            finally
+            {
+                foreach (var h in held) h.Free();
+            }
+        }
+
+        /// <summary>Linear blend skinning of every mesh of the uploaded scene on the device, from the rest pose
+        /// SetRestPose installed and the skin SetSkin installed (pt_skin_meshes): matrices holds 16 doubles per bone,
+        /// row-major.  normalsMode 0 blends the transformed rest normals, PtHip.PT_NORMALS_FACE or PT_NORMALS_SMOOTH
+        /// derives them from the skinned positions.  The BVHs, the instances' boxes and the lights follow as in
+        /// UpdateMeshes; ReadPose returns the skinned arrays.  Returns the device time of the kernels in ms.</summary>
+        public double SkinMeshes(double[] matrices, int normalsMode = 0)
+        {
+            if (!uploaded) Upload();
+            var hm = GCHandle.Alloc(matrices, GCHandleType.Pinned);
+            try
+            {
+                var u = new PtHip.pt_mesh_skin { num_bones = matrices.Length / 16, normals_mode = normalsMode, matrices = hm.AddrOfPinnedObject() };
+                PtHip.Check(PtHip.pt_skin_meshes(ctx, ref u, out double ms), "pt_skin_meshes");
+                return ms;
+            }
+            finally
+            {
+                hm.Free();
+            }
+        }
+
+        /// <summary>The six arrays the last PoseMeshes or SkinMeshes left on the device (pt_read_pose), 3 floats per triangle each:
         /// v1, v2, v3, n1, n2, n3, derived normals included.</summary>
         public float[][] ReadPose(int numTriangles)
         {
@@ -929,7 +998,7 @@ namespace PTSharpCore
             }
         }
 
-        /// <summary>RebuildMeshes from the pose the last PoseMeshes left staged on the device: nothing is copied.</summary>
+        /// <summary>RebuildMeshes from the pose or skin the last PoseMeshes or SkinMeshes left staged on the device: nothing is copied.</summary>
         public double RebuildMeshes()
         {
             PtHip.Check(PtHip.pt_rebuild_meshes(ctx, IntPtr.Zero, out double ms), "pt_rebuild_meshes");
@@ -968,7 +1037,7 @@ namespace PTSharpCore
             }
         }
 
-        /// <summary>RebuildBlas from the pose the last PoseMeshes left staged on the device: nothing is copied.</summary>
+        /// <summary>RebuildBlas from the pose or skin the last PoseMeshes or SkinMeshes left staged on the device: nothing is copied.</summary>
         public double RebuildBlas(int what = 0)
         {
             PtHip.Check(PtHip.pt_rebuild_blas(ctx, IntPtr.Zero, what, out double ms), "pt_rebuild_blas");

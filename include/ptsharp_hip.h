@@ -26,6 +26,9 @@
  *   pt_set_rest_pose   (new) Mesh.Transform(matrix) of every mesh of the      Mesh.cs:254-274 (Mesh.Transform; MoveTo
  *   / pt_pose_meshes   uploaded scene on the device, from a rest pose kept    and FitInside, Mesh.cs:237-252, end in it),
  *   / pt_read_pose     there: one matrix per mesh per call, then the refits   Matrix.cs:134-150
+ *   pt_set_skin        (new) linear blend skinning of that rest pose on the   Matrix.MulPosition / MulDirection,
+ *   / pt_skin_meshes   device: four bone indices and weights per corner sent  Matrix.cs:134-150 (the reference has no
+ *   / pt_read_skin     once, one matrix per bone per call, then the refits    skinning)
  *   pt_rebuild_meshes  (new) pt_update_meshes that also re-sorts the world    Tree.NewTree, Tree.cs:22-29 (the reference
  *   / pt_tri_bvh_cost  triangle BVH into a balanced median tree on the device  builds a new tree for every frame's scene)
  *                      for the new positions; the SAH cost of the tree as it
@@ -762,10 +765,68 @@ typedef struct pt_mesh_pose {
     const int32_t* mesh_mask;  /* [num_meshes] or NULL (= all); 0: the mesh takes its rest values verbatim */
 } pt_mesh_pose;
 int pt_pose_meshes(void* ctx, const pt_mesh_pose* u, double* out_kernel_ms);
-/* The six arrays the last pt_pose_meshes left staged on the device (derived normals included), [n][3] each in
+/* The six arrays the last pt_pose_meshes or pt_skin_meshes left staged on the device (derived normals included), [n][3] each in
  * pt_scene_desc order; any pointer may be NULL.  They stay until a pt_update_* or pt_read_tri_normals reuses the
- * staged arrays.  A NULL ctx, or no pose staged: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+ * staged arrays.  A NULL ctx, or no pose or skin staged: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n2, float* n3);
+
+/* Blend skinning on the device: a mesh that bends.  The host sends four bone indices and four weights
+ * per corner once (pt_set_skin) and one 4x4 matrix per bone per frame (pt_skin_meshes); the device blends the rest pose
+ * pt_set_rest_pose installed, derives or transforms the normals, and refits, as pt_pose_meshes does.
+ *
+ * pt_set_skin installs the skin: for each of the three corners of every triangle, pt_scene_desc order,
+ * PT_SKIN_INFLUENCES (bone index, weight) pairs.  The data is copied to a device workspace of its own (72 B per
+ * triangle: the indices are kept in 16 bits; plus 128 B per bone for the matrices) kept until the next pt_upload_scene;
+ * a later pt_set_skin replaces it, a later pt_set_rest_pose keeps it.  It needs a scene, not a rest pose, and changes
+ * nothing a ray sees.  Weights are not normalised and their values are not checked.  Synchronises before returning.
+ * Errors (nothing copied, a previous skin kept): a NULL ctx, desc or array, reserved != 0, num_triangles different from
+ * the uploaded scene's, num_bones outside [1, PT_SKIN_MAX_BONES], any of the 12 num_triangles indices outside
+ * [0, num_bones), whatever its weight: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; the workspace not allocated:
+ * PT_ERR_OUT_OF_MEMORY. */
+#define PT_SKIN_INFLUENCES 4     /* (bone, weight) pairs per corner */
+#define PT_SKIN_MAX_BONES 65536
+typedef struct pt_skin_desc {
+    int32_t num_triangles;     /* must equal the uploaded scene's num_triangles */
+    int32_t num_bones;         /* 1..PT_SKIN_MAX_BONES */
+    int32_t reserved[2];       /* 0 */
+    const int32_t *bone1, *bone2, *bone3;     /* [num_triangles][4] each: the bones of corner 1, 2, 3; every one in [0, num_bones) */
+    const float *weight1, *weight2, *weight3; /* [num_triangles][4] each: their weights; +-0: the influence is dead */
+} pt_skin_desc;
+int pt_set_skin(void* ctx, const pt_skin_desc* desc);
+/* pt_skin_meshes skins the rest pose and refits.  A source triangle belongs to a mesh as for pt_pose_meshes; a loose
+ * triangle takes its rest values bit for bit, whatever its weights (a light that is a loose emissive triangle returns
+ * to its rest vertices).  For a corner V of a mesh triangle an influence k is live when weight[k] != 0 (false only for
+ * +-0; a NaN weight is live).  With no live influence the position, and with normals_mode 0 the normal, take their rest
+ * values bit for bit.  Otherwise, over the live k in ascending order, the term is (double)weight[k] * P_k per
+ * component, P_k the three fp64 sums Matrix.MulPosition(matrices[bone[k]], V_rest) forms (m[0] x + m[1] y + m[2] z +
+ * m[3], left to right) before any conversion; the accumulator is the first live term, each further live term is added
+ * to it (it does not start from 0: -0 survives, and a dead influence's matrix is never read); the position is one
+ * conversion of the accumulator to fp32.  With normals_mode 0 the normal is blended the same way from
+ * Matrix.MulDirection's three fp64 sums (no translation), converted once, then normalised in fp32 as MulDirection ends;
+ * with PT_NORMALS_FACE or PT_NORMALS_SMOOTH the normals of every triangle are derived from the skinned positions as
+ * pt_update_meshes derives them.  The fourth row of a matrix is not read.  So one live influence of weight 1 gives
+ * exactly pt_pose_meshes' result for that bone's matrix.  A skin is always applied to the rest pose, never to the
+ * current state: repeated skins do not drift, a later pt_update_* or pt_pose_meshes overwrites the skin and the skin
+ * overwrites them.  An instanced mesh is skinned in its object space.  The skinned arrays then go through what
+ * pt_update_meshes runs, so everything on the device is, word for word, what pt_update_meshes with the same arrays
+ * computed on the host leaves; pt_read_pose returns them, and pt_rebuild_meshes / pt_rebuild_blas with u == NULL take
+ * them.  Stream order, the synchronisation, the Buffer, pass state, counters and non-finite values are as for
+ * pt_pose_meshes; out_kernel_ms (may be NULL) covers the skin kernel, the normals kernels and the refits.
+ * Errors (nothing launched, the scene untouched): a NULL ctx, u or matrices, reserved != 0, a normals_mode outside
+ * {0, 1, 2}, num_bones different from the installed skin's, no skin installed, no rest pose installed:
+ * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; a workspace not allocated: PT_ERR_OUT_OF_MEMORY; PT_NORMALS_SMOOTH with
+ * 3 * num_triangles >= 2^31: PT_ERR_UNSUPPORTED.  A scene with no triangle in any BVH: PT_OK, nothing launched. */
+typedef struct pt_mesh_skin {
+    int32_t num_bones;         /* must equal the installed skin's num_bones */
+    int32_t normals_mode;      /* 0: the blend of MulDirection of the rest normals; PT_NORMALS_FACE; PT_NORMALS_SMOOTH */
+    int32_t reserved[2];       /* 0 */
+    const double* matrices;    /* [num_bones][16] row-major, required */
+} pt_mesh_skin;
+int pt_skin_meshes(void* ctx, const pt_mesh_skin* u, double* out_kernel_ms);
+/* The installed skin in pt_skin_desc's form, indices and weight bits as given, [num_triangles][4] each; any pointer may
+ * be NULL.  Synchronises and changes nothing.  A NULL ctx, or no skin installed: PT_ERR_INVALID_ARG; no scene:
+ * PT_ERR_NO_SCENE. */
+int pt_read_skin(void* ctx, int32_t* bone1, int32_t* bone2, int32_t* bone3, float* weight1, float* weight2, float* weight3);
 
 /* Re-sorting the world triangle BVH on the device.  The updates above refit: they keep the topology
  * of the pose the tree was built for, and a mesh deformed far from it traces an ever worse tree.  pt_rebuild_meshes
@@ -776,8 +837,8 @@ int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n
  * numbered level by level from the root; the order comes from 3 h rounds of stable sorts of ever halved position
  * segments by the key min + max of the triangle's vertices on the segment's widest axis (pt_rebuild.h states it
  * exactly).  The tree's shape depends on P alone, the order is computed on the device, and every box, record and chunk
- * line then comes from the refit.  With u == NULL the arrays the last pt_pose_meshes left staged are taken: nothing is
- * copied, the staged normals are used and the pose stays readable.
+ * line then comes from the refit.  With u == NULL the arrays the last pt_pose_meshes or pt_skin_meshes left staged are taken: nothing is
+ * copied, the staged normals are used and the pose or skin stays readable.
  * Afterwards every ray query, feature pass and render pass sees what a fresh pt_upload_scene with these arrays would
  * see, up to the exact-t tie order of DESIGN.md §5, and every later pt_update_triangles, _normals, pt_update_meshes,
  * pt_pose_meshes, pt_read_tri_normals and pt_read_tri_bvh works on the new topology (pt_read_tri_bvh's counts follow;
@@ -786,7 +847,7 @@ int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n
  * untouched: other contexts keep their trees.  Runs on the context's stream after every pass issued before it and
  * synchronises before returning; out_kernel_ms (may be NULL) covers every kernel of the call.  Non-finite positions:
  * the order is unspecified, still a permutation; no access leaves its array.
- * Errors (nothing launched, the scene untouched): those of pt_update_meshes (u == NULL without a staged pose:
+ * Errors (nothing launched, the scene untouched): those of pt_update_meshes (u == NULL without a staged pose or skin:
  * PT_ERR_INVALID_ARG); a scene with an instanced mesh, whose BLAS is not rebuilt: PT_ERR_UNSUPPORTED (pt_rebuild_blas
  * below serves such a scene); more than 9 levels, or more node and chunk lines together than the upload allocated
  * (nodes and chunks share one run of lines,
@@ -802,7 +863,7 @@ int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms)
 int pt_tri_bvh_cost(void* ctx, double out[3]);
 
 /* Re-sorting instanced meshes' BLASes on the device.  pt_rebuild_blas takes pt_update_meshes' struct and
- * does everything that call does (positions; normals given, kept or derived; u == NULL: the staged pose, as
+ * does everything that call does (positions; normals given, kept or derived; u == NULL: the staged pose or skin, as
  * pt_rebuild_meshes takes it), and re-sorts what `what` names: PT_REBUILD_WORLD the world triangle BVH, exactly as
  * pt_rebuild_meshes does (its refusals for too many levels or lines included; on a scene without an instanced mesh the
  * device then holds, word for word, what pt_rebuild_meshes leaves), PT_REBUILD_BLAS every BLAS, 0 both.  A BLAS of n
@@ -821,7 +882,7 @@ int pt_tri_bvh_cost(void* ctx, double out[3]);
  * pt_rebuild_meshes.  PT_BLAS_TAIL in the environment, read at each call, sizes the segments one workgroup finishes in
  * LDS (0: none, every round a device sort; else the largest 4 * 4^k in [64, 1024] it holds); the words left on the
  * device do not depend on it.
- * Errors (nothing launched, the scene untouched): those of pt_update_meshes (u == NULL without a staged pose:
+ * Errors (nothing launched, the scene untouched): those of pt_update_meshes (u == NULL without a staged pose or skin:
  * PT_ERR_INVALID_ARG); `what` outside 0..3: PT_ERR_INVALID_ARG; a BLAS of more than 10 levels: PT_ERR_UNSUPPORTED; a
  * workspace (about 100 B per BLAS triangle, kept until the next upload) not allocated: PT_ERR_OUT_OF_MEMORY. */
 #define PT_REBUILD_WORLD 1 /* what pt_rebuild_meshes re-sorts */

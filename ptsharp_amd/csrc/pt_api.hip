@@ -34,6 +34,7 @@
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
 #include "pt_shape_refit.h"
+#include "pt_skin.h"
 #include "pt_texture.h"
 #include "pt_update_layout.h"
 #include "pt_volume_update.h"
@@ -148,6 +149,10 @@ hipError_t launch_blas_cost(int64_t num_blas, int64_t total_nodes, int64_t max_n
 // pt_pose.hip
 hipError_t launch_pose(int64_t n, int32_t num_meshes, const int32_t* group, const int32_t* mask, const double* matrices,
                        bool normals, const float* const rest[6], float* const out[6], hipStream_t stream);
+// pt_skin.hip
+hipError_t launch_skin(int64_t n, int32_t num_bones, const int32_t* group, const double* matrices, bool normals,
+                       const uint16_t* const bone[3], const float* const weight[3], const float* const rest[6], float* const out[6],
+                       hipStream_t stream);
 // pt_volume.hip
 hipError_t launch_vol_rebuild(const DevVolume& v, bool new_data, hipStream_t stream);
 // pt_texture.hip
@@ -245,6 +250,8 @@ struct SceneDyn {
     Workspace<pt::ShapesDev> shapes_ws;     // first pt_update_shapes, or pt_update_meshes on instanced meshes
     Workspace<pt::BlasDev> blas_ws;         // first pt_update_meshes on instanced meshes
     Workspace<pt::PoseDev> pose_ws;         // pt_set_rest_pose
+    Workspace<pt::SkinDev> skin_ws;         // pt_set_skin
+    int32_t skin_bones = 0;                 // the installed skin's num_bones (0: none)
     Workspace<RebuildDev> rebuild_ws;       // first pt_rebuild_meshes
     Workspace<pt::QueryDev> query_ws;       // first pt_intersect_hits: its own copies of the identity tables
     bool query_src_stale = false;           // a pt_rebuild_meshes permuted refit.src_of_pos after query_ws took its copy
@@ -268,7 +275,7 @@ struct SceneDyn {
     size_t lights_cap = 0;
     std::vector<pt::DevTexture> texs;
     DeviceArray tex_stage;
-    bool pose_staged = false;            // refit_ws' staged arrays hold the last pt_pose_meshes' (pt_read_pose)
+    bool pose_staged = false;            // refit_ws' staged arrays hold the last pt_pose_meshes' or pt_skin_meshes' (pt_read_pose)
     bool blas_boxes_on_device = false;   // blas_ws holds the meshes' boxes (after the first pt_update_meshes)
     void release_device() {
         refit_ws.release();
@@ -276,6 +283,7 @@ struct SceneDyn {
         shapes_ws.release();
         blas_ws.release();
         pose_ws.release();
+        skin_ws.release();
         rebuild_ws.release();
         blas_rebuild_ws.release();
         query_ws.release();
@@ -1743,7 +1751,8 @@ int update_run(Ctx* c, const UpdateCall& U, double* out_kernel_ms) {
     return kernel_ms(c, out_kernel_ms);
 }
 
-// An update from host arrays: src staged (NULL: the pose pt_pose_meshes left staged is used and stays readable), then run
+// An update from host arrays: src staged (NULL: the pose pt_pose_meshes or pt_skin_meshes left staged is used and stays
+// readable), then run
 int update_stage_and_run(Ctx* c, const UpdateCall& U, const float* const src[6], double* out_kernel_ms) {
     if (src) {
         c->dyn.pose_staged = false;   // the staged arrays are this update's from here on
@@ -1907,13 +1916,127 @@ int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (!c->dyn.pose_staged || !c->dyn.refit_ws.mem.ptr)
-        return fail(PT_ERR_INVALID_ARG, "read pose: the staged arrays hold no pose (none made since the upload, or a later "
+        return fail(PT_ERR_INVALID_ARG, "read pose: the staged arrays hold no pose or skin (none made since the upload, or a later "
                                         "pt_update_* or pt_read_tri_normals reused them)");
     PT_HIP(hipSetDevice(c->device));
     const size_t arr = (size_t)c->dyn.refit.num_triangles * 3 * sizeof(float);
     float* out[6] = {v1, v2, v3, n1, n2, n3};
     for (int k = 0; k < 6; k++) PT_HIP(read_back(c, out[k], c->dyn.refit_ws.at.in[k], arr));
     PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// ---- blend skinning on the device
+static_assert(pt::kSkinInfluences == PT_SKIN_INFLUENCES, "pt_skin.h and the ABI agree on the influences per corner");
+
+int pt_set_skin(void* ctx, const pt_skin_desc* d) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!d) return fail(PT_ERR_INVALID_ARG, "set skin: desc is NULL");
+    if (d->reserved[0] != 0 || d->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "set skin: reserved must be 0");
+    const int32_t* const bones[3] = {d->bone1, d->bone2, d->bone3};
+    const float* const weights[3] = {d->weight1, d->weight2, d->weight3};
+    for (int k = 0; k < 3; k++)
+        if (!bones[k] || !weights[k])
+            return fail(PT_ERR_INVALID_ARG, "set skin: bone1, bone2, bone3, weight1, weight2 and weight3 are required");
+    if (d->num_bones < 1 || d->num_bones > PT_SKIN_MAX_BONES)
+        return fail(PT_ERR_INVALID_ARG, "set skin: num_bones is " + std::to_string(d->num_bones) + ", outside [1, " +
+                                            std::to_string(PT_SKIN_MAX_BONES) + "]");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const int32_t n = Y.refit.num_triangles;
+    if (d->num_triangles != n)
+        return fail(PT_ERR_INVALID_ARG, "set skin: num_triangles is " + std::to_string(d->num_triangles) + ", the uploaded scene has " +
+                                            std::to_string(n));
+    // every index, whatever its weight, before the first copy: the kernel's gathers stay inside the matrix array
+    const size_t row = (size_t)n * PT_SKIN_INFLUENCES;
+    std::vector<uint16_t> packed[3];
+    for (int k = 0; k < 3; k++) {
+        packed[k].resize(row);
+        for (size_t i = 0; i < row; i++) {
+            const int32_t b = bones[k][i];
+            if (b < 0 || b >= d->num_bones)
+                return fail(PT_ERR_INVALID_ARG, "set skin: bone" + std::to_string(k + 1) + "[" + std::to_string(i / PT_SKIN_INFLUENCES) + "][" +
+                                                    std::to_string(i % PT_SKIN_INFLUENCES) + "] is " + std::to_string(b) +
+                                                    ", outside [0, " + std::to_string(d->num_bones) + ")");
+            packed[k][i] = (uint16_t)b;
+        }
+    }
+    PT_HIP(hipSetDevice(c->device));
+    // a workspace with room for the matrices: the installed one, or a new one that replaces it once it is filled
+    const auto upload = [&](const pt::SkinDev& S, Uploader& up) {
+        for (int k = 0; k < 3; k++) {
+            up(S.bone[k], packed[k]);
+            up.copy(S.weight[k], weights[k], row * sizeof(float));
+        }
+    };
+    if (Y.skin_ws.mem.ptr && d->num_bones <= Y.skin_ws.at.bone_cap) {
+        Uploader up{c->stream};
+        upload(Y.skin_ws.at, up);
+        if (const int rc = check_hip(up.err, "staging the skin")) return rc;
+    } else {
+        Workspace<pt::SkinDev> fresh;
+        if (const int rc = ensure_workspace(c, fresh, "skin", [&](void* base) { return pt::skin_layout(n, d->num_bones, base); }, upload))
+            return rc;
+        Y.skin_ws.release();
+        Y.skin_ws = fresh;
+    }
+    PT_HIP(hipStreamSynchronize(c->stream));
+    Y.skin_bones = d->num_bones;
+    return PT_OK;
+}
+
+int pt_skin_meshes(void* ctx, const pt_mesh_skin* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!u) return fail(PT_ERR_INVALID_ARG, "skin meshes: u is NULL");
+    if (u->reserved[0] != 0 || u->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "skin meshes: reserved must be 0");
+    if (const int rc = check_normals_mode("skin meshes", u->normals_mode)) return rc;
+    if (!u->matrices) return fail(PT_ERR_INVALID_ARG, "skin meshes: matrices is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const pt::RefitTables& T = Y.refit;
+    if (!Y.skin_ws.mem.ptr || Y.skin_bones == 0) return fail(PT_ERR_INVALID_ARG, "skin meshes: no skin (pt_set_skin)");
+    if (u->num_bones != Y.skin_bones)
+        return fail(PT_ERR_INVALID_ARG, "skin meshes: num_bones is " + std::to_string(u->num_bones) + ", the installed skin has " +
+                                            std::to_string(Y.skin_bones));
+    if (!Y.pose_ws.mem.ptr) return fail(PT_ERR_INVALID_ARG, "skin meshes: no rest pose (pt_set_rest_pose)");
+    // the skinned normals are staged unless a mode derives them; the lights return to their rest vertices
+    const UpdateCall U{T.num_triangles, normals_of(u->normals_mode, true), {nullptr, nullptr, nullptr}, nullptr};
+    bool launch = false;
+    if (const int rc = update_prepare(c, U, true, out_kernel_ms, &launch)) return rc;
+    if (!launch) return PT_OK;
+    const pt::PoseDev& P = Y.pose_ws.at;
+    const pt::SkinDev& S = Y.skin_ws.at;
+    PT_HIP(hipMemcpyAsync(S.matrices, u->matrices, (size_t)u->num_bones * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_skin(T.num_triangles, u->num_bones, P.group, S.matrices, U.normals == Normals::Given, S.bone, S.weight, P.rest,
+                           Y.refit_ws.at.in, c->stream));
+    Y.pose_staged = true;
+    return update_run(c, U, out_kernel_ms);
+}
+
+int pt_read_skin(void* ctx, int32_t* bone1, int32_t* bone2, int32_t* bone3, float* weight1, float* weight2, float* weight3) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    if (!Y.skin_ws.mem.ptr || Y.skin_bones == 0) return fail(PT_ERR_INVALID_ARG, "read skin: no skin (pt_set_skin)");
+    PT_HIP(hipSetDevice(c->device));
+    const size_t row = (size_t)Y.refit.num_triangles * PT_SKIN_INFLUENCES;
+    int32_t* const bones[3] = {bone1, bone2, bone3};
+    float* const weights[3] = {weight1, weight2, weight3};
+    std::vector<uint16_t> packed[3];
+    for (int k = 0; k < 3; k++) {
+        if (bones[k]) {
+            packed[k].resize(row);
+            PT_HIP(read_back(c, packed[k].data(), Y.skin_ws.at.bone[k], row * sizeof(uint16_t)));
+        }
+        PT_HIP(read_back(c, weights[k], Y.skin_ws.at.weight[k], row * sizeof(float)));
+    }
+    PT_HIP(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; k++)
+        if (bones[k]) for (size_t i = 0; i < row; i++) bones[k][i] = packed[k][i];
     return PT_OK;
 }
 
@@ -1946,7 +2069,7 @@ int rebuild_world_prepare(Ctx* c, const std::string& who, RebuildRun& run) {
 // pt_rebuild_meshes and pt_rebuild_blas after their own argument checks: world / blas say which trees are re-sorted
 int rebuild_call(Ctx* c, const std::string& who, const pt_mesh_update* u, bool world, bool blas, double* out_kernel_ms) {
     SceneDyn& Y = c->dyn;
-    // u NULL: the staged pose with its normals, the lights at their rest vertices
+    // u NULL: the staged pose or skin with its normals, the lights at their rest vertices
     RebuildRun run{};
     UpdateCall U{Y.refit.num_triangles, Normals::Given, {nullptr, nullptr, nullptr}, nullptr};
     if (u) U = UpdateCall{u->num_triangles, normals_of(u->normals_mode, u->n1), {u->v1, u->v2, u->v3}, nullptr};
@@ -1977,7 +2100,7 @@ int pt_rebuild_meshes(void* ctx, const pt_mesh_update* u, double* out_kernel_ms)
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
     SceneDyn& Y = c->dyn;
     if (!u && (!Y.pose_staged || !Y.refit_ws.mem.ptr))
-        return fail(PT_ERR_INVALID_ARG, "rebuild meshes: u is NULL and the staged arrays hold no pose (pt_pose_meshes)");
+        return fail(PT_ERR_INVALID_ARG, "rebuild meshes: u is NULL and the staged arrays hold no pose or skin (pt_pose_meshes, pt_skin_meshes)");
     if (Y.has_blas)
         return fail(PT_ERR_UNSUPPORTED, "rebuild meshes: the scene holds an instanced mesh (a transformed shape over PT_SHAPE_MESH); "
                                         "BLASes are not rebuilt");
@@ -1993,7 +2116,7 @@ int pt_rebuild_blas(void* ctx, const pt_mesh_update* u, int32_t what, double* ou
     if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
     SceneDyn& Y = c->dyn;
     if (!u && (!Y.pose_staged || !Y.refit_ws.mem.ptr))
-        return fail(PT_ERR_INVALID_ARG, "rebuild blas: u is NULL and the staged arrays hold no pose (pt_pose_meshes)");
+        return fail(PT_ERR_INVALID_ARG, "rebuild blas: u is NULL and the staged arrays hold no pose or skin (pt_pose_meshes, pt_skin_meshes)");
     if (what == 0) what = PT_REBUILD_WORLD | PT_REBUILD_BLAS;
     return rebuild_call(c, "rebuild blas", u, (what & PT_REBUILD_WORLD) != 0, (what & PT_REBUILD_BLAS) != 0, out_kernel_ms);
 }

@@ -268,6 +268,26 @@ inline PoseDev pose_layout(const RefitTables& T, void* base) {
     return r;
 }
 
+// pt_set_skin: [bone1 bone2 bone3 | weight1 weight2 weight3 | matrices]: per corner four 16-bit bone indices and four
+// fp32 weights per triangle (3 * (8 + 16) = 72 B per triangle), then room for bone_cap matrices of 16 doubles
+struct SkinDev {
+    uint16_t* bone[3];
+    float* weight[3];
+    double* matrices;
+    int32_t bone_cap;
+    size_t bytes;
+};
+inline SkinDev skin_layout(int32_t num_triangles, int32_t bone_cap, void* base) {
+    Carver c(base);
+    SkinDev r{};
+    for (uint16_t*& a : r.bone) a = c.take<uint16_t>((size_t)num_triangles * 4);
+    for (float*& a : r.weight) a = c.take<float>((size_t)num_triangles * 4);
+    r.matrices = c.take<double>((size_t)bone_cap * 16);
+    r.bone_cap = bone_cap;
+    r.bytes = c.bytes();
+    return r;
+}
+
 // pt_intersect_hits' identity tables (pt_query.h): [tri_src | blas_src | tri_slot | ana_slot | plane_slot]
 struct QueryDev {
     int32_t* tri_src;

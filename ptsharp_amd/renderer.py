@@ -882,8 +882,8 @@ class Renderer:
     def RebuildMeshes(self, v1=None, v2=None, v3=None, n1=None, n2=None, n3=None, normals=None) -> float:
         """UpdateMeshes that also re-sorts the world triangle BVH on the device (pt_rebuild_meshes): the topology is
         replaced by a balanced object-median tree for the new positions, for a mesh deformed far from the pose its tree
-        was built for (TriBvhCost tells when).  RebuildMeshes() with no arrays takes the pose the last PoseMeshes left
-        staged on the device; nothing is copied.  A scene with an instanced mesh is refused.  The uploaded FlatScene
+        was built for (TriBvhCost tells when).  RebuildMeshes() with no arrays takes the pose the last PoseMeshes or
+        SkinMeshes left staged on the device; nothing is copied.  A scene with an instanced mesh is refused.  The uploaded FlatScene
         is kept as UpdateMeshes keeps it.  Returns the device time of the kernels in ms."""
         self._ensure_scene()
         ms = C.c_double(0.0)
@@ -925,7 +925,7 @@ class Renderer:
         balanced object-median tree for the new positions (BlasCost tells when that pays); one whose balanced tree
         needs more nodes than the upload gave it is refitted instead.  `what` is _abi.REBUILD_WORLD (the world
         triangle BVH, as RebuildMeshes re-sorts it), _abi.REBUILD_BLAS, or both (0).  RebuildBlas() with no arrays
-        takes the pose the last PoseMeshes left staged on the device.  The uploaded FlatScene is kept as UpdateMeshes
+        takes the pose the last PoseMeshes or SkinMeshes left staged on the device.  The uploaded FlatScene is kept as UpdateMeshes
         keeps it.  Returns the device time of the kernels in ms."""
         self._ensure_scene()
         ms = C.c_double(0.0)
@@ -1062,8 +1062,66 @@ class Renderer:
             self._refresh_mirror()
         return float(ms.value)
 
+    def SetSkin(self, bones, weights, num_bones) -> None:
+        """Installs the skin SkinMeshes blends with (pt_set_skin): for every corner of every triangle of the compiled
+        scene four bone indices and four weights.  `bones` is an [n, 3, 4] integer array or three [n, 4] arrays (corner
+        1, 2, 3), `weights` the same in float32; a weight of 0 makes its influence dead.  Kept on the device until the
+        next upload; an index outside [0, num_bones) is refused."""
+        self._ensure_scene()
+        n = len(self._uploaded.tri_material)
+
+        def corners(a, dtype):
+            if isinstance(a, np.ndarray) and a.ndim == 3:
+                a = [a[:, k] for k in range(3)]
+            a = [np.ascontiguousarray(x, dtype).reshape(-1, 4) for x in a]
+            if len(a) != 3 or any(len(x) != n for x in a):
+                raise ValueError(f"the scene has {n} triangles: three [n, 4] arrays, or one [n, 3, 4]")
+            return a
+        b, w = corners(bones, np.int32), corners(weights, np.float32)
+        d = _abi.pt_skin_desc()
+        d.num_triangles, d.num_bones = n, int(num_bones)
+        d.bone1, d.bone2, d.bone3 = (x.ctypes.data_as(C.POINTER(C.c_int32)) for x in b)
+        d.weight1, d.weight2, d.weight3 = (x.ctypes.data_as(C.POINTER(C.c_float)) for x in w)
+        _abi.check(self._lib.pt_set_skin(self._ctx, C.byref(d)), "pt_set_skin")
+
+    def SkinMeshes(self, matrices, normals=None, mirror=True) -> float:
+        """Linear blend skinning of every mesh of the scene on the device, from the rest pose and the skin SetSkin
+        installed (pt_skin_meshes): `matrices` is a sequence of Matrix or a [B, 16] (or [B, 4, 4]) float64 array, one
+        per bone.  normals=None blends the transformed rest normals, "face" or "smooth" derives them from the skinned
+        positions.  Loose triangles take their rest values.  The BVHs, the instances' boxes and the lights are refitted
+        as UpdateMeshes refits them.  The rest pose is installed on first use (SetRestPose()); mirror is PoseMeshes'.
+        Returns the device time of the kernels in ms."""
+        self._ensure_scene()
+        flat = self._uploaded
+        if normals not in (None, "face", "smooth"):
+            raise ValueError('normals is None, "face" or "smooth"')
+        if self._rest_of is not flat:
+            self.SetRestPose()
+        m = np.ascontiguousarray([getattr(k, "m", k) for k in matrices], np.float64).reshape(-1, 16)
+        u = _abi.pt_mesh_skin()
+        u.num_bones = len(m)
+        u.normals_mode = 0 if normals is None else _abi.NORMALS_FACE if normals == "face" else _abi.NORMALS_SMOOTH
+        u.matrices = m.ctypes.data_as(C.POINTER(C.c_double))
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_skin_meshes(self._ctx, C.byref(u), C.byref(ms)), "pt_skin_meshes")
+        # a device time of exactly 0: nothing was launched (no triangle of the scene is in a BVH), nothing to mirror
+        self._mirror_stale = ms.value != 0.0
+        if mirror:
+            self._refresh_mirror()
+        return float(ms.value)
+
+    def ReadSkin(self):
+        """The installed skin as SetSkin took it (pt_read_skin): (bones [n, 3, 4] int32, weights [n, 3, 4] float32)."""
+        self._ensure_scene()
+        n = len(self._uploaded.tri_material)
+        b = [np.zeros((n, 4), np.int32) for _ in range(3)]
+        w = [np.zeros((n, 4), np.float32) for _ in range(3)]
+        _abi.check(self._lib.pt_read_skin(self._ctx, *[x.ctypes.data_as(C.POINTER(C.c_int32)) for x in b],
+                                          *[x.ctypes.data_as(C.POINTER(C.c_float)) for x in w]), "pt_read_skin")
+        return np.stack(b, axis=1), np.stack(w, axis=1)
+
     def ReadPose(self):
-        """The six arrays the last PoseMeshes left on the device (pt_read_pose): v1, v2, v3, n1, n2, n3, [n, 3]
+        """The six arrays the last PoseMeshes or SkinMeshes left on the device (pt_read_pose): v1, v2, v3, n1, n2, n3, [n, 3]
         float32 each, derived normals included.  Also brings a FlatScene left stale by mirror=False up to date."""
         self._ensure_scene()
         n = len(self._uploaded.tri_material)
