@@ -251,6 +251,29 @@ namespace PTSharpCore
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct pt_morph_desc
+        {
+            public int num_triangles;      // must equal the uploaded scene's num_triangles
+            public int num_targets;        // 1..PT_MORPH_MAX_TARGETS
+            public fixed int reserved[2];  // 0
+            public IntPtr target_first;    // [num_targets + 1] long, target_first[0] = 0, non-decreasing; the last = number of deltas
+            public IntPtr corner;          // [deltas] int: 3 * triangle + c, strictly ascending within a target
+            public IntPtr dpos;            // [deltas][3] float
+            public IntPtr dnrm;            // [deltas][3] float or null: the morph carries no normal deltas
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        public struct pt_mesh_morph
+        {
+            public int num_targets;        // must equal the installed morph's
+            public int normals_mode;       // 0, PT_NORMALS_FACE, PT_NORMALS_SMOOTH
+            public int num_bones;          // 0 when skin_matrices is null, else the installed skin's
+            public int reserved;           // 0
+            public IntPtr weights;         // [num_targets] float, required
+            public IntPtr skin_matrices;   // null: morph only; else [num_bones][16] double: morph, then the skin of the morphed pose
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         public unsafe struct pt_volume_update
         {
             public int num_volumes;        // must equal the uploaded scene's
@@ -346,7 +369,12 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_set_skin(IntPtr ctx, ref pt_skin_desc desc);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_skin_meshes(IntPtr ctx, ref pt_mesh_skin u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_skin(IntPtr ctx, int[] bone1, int[] bone2, int[] bone3, float[] weight1, float[] weight2, float[] weight3);
-        // pt_update_meshes that also re-sorts the world triangle BVH on the device (u = IntPtr.Zero: the staged pose or skin), and the tree's cost
+        // Morph targets on the device: sparse per-corner deltas sent once, one weight per target per call (and optionally the skin's matrices), then pt_update_meshes' refits
+        public const int PT_MORPH_MAX_TARGETS = 65535;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_set_morph(IntPtr ctx, ref pt_morph_desc desc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_morph_meshes(IntPtr ctx, ref pt_mesh_morph u, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_morph(IntPtr ctx, long[] counts3, long[] targetFirst, int[] corner, float[] dpos, float[] dnrm);
+        // pt_update_meshes that also re-sorts the world triangle BVH on the device (u = IntPtr.Zero: the staged pose, skin or morph), and the tree's cost
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, ref pt_mesh_update u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_rebuild_meshes(IntPtr ctx, IntPtr u, out double kernelMs);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_tri_bvh_cost(IntPtr ctx, double[] out3);
@@ -957,7 +985,60 @@ namespace PTSharpCore
             }
         }
 
-        /// <summary>The six arrays the last PoseMeshes or SkinMeshes left on the device (pt_read_pose), 3 floats per triangle each:
+        /// <summary>Installs the morph targets MorphMeshes adds to the rest pose (pt_set_morph): target t owns the
+        /// deltas targetFirst[t] .. targetFirst[t + 1] - 1; delta i moves corner corner[i] = 3 * triangle + c by
+        /// dpos[3 i ..] and, when dnrm is not null, its normal by dnrm[3 i ..].  Kept on the device until the next
+        /// upload.</summary>
+        public void SetMorph(int numTriangles, long[] targetFirst, int[] corner, float[] dpos, float[] dnrm = null)
+        {
+            if (!uploaded) Upload();
+            var held = new List<GCHandle>();
+            try
+            {
+                IntPtr Pin(object a) { var h = GCHandle.Alloc(a, GCHandleType.Pinned); held.Add(h); return h.AddrOfPinnedObject(); }
+                var d = new PtHip.pt_morph_desc
+                {
+                    num_triangles = numTriangles, num_targets = targetFirst.Length - 1,
+                    target_first = Pin(targetFirst), corner = Pin(corner), dpos = Pin(dpos),
+                    dnrm = dnrm == null ? IntPtr.Zero : Pin(dnrm),
+                };
+                PtHip.Check(PtHip.pt_set_morph(ctx, ref d), "pt_set_morph");
+            }
+            finally
+            {
+                foreach (var h in held) h.Free();
+            }
+        }
+
+        /// <summary>Morphs every mesh of the uploaded scene on the device, from the rest pose SetRestPose installed and
+        /// the targets SetMorph installed (pt_morph_meshes): weights holds one float per target, 0 makes it dead.
+        /// normalsMode 0 adds the normal deltas to the rest normals, PtHip.PT_NORMALS_FACE or PT_NORMALS_SMOOTH derives
+        /// them from the morphed positions.  skinMatrices (16 doubles per bone of the skin SetSkin installed, or null)
+        /// skins the morphed pose as SkinMeshes skins the rest pose.  ReadPose returns the arrays.  Returns the device
+        /// time of the kernels in ms.</summary>
+        public double MorphMeshes(float[] weights, int normalsMode = 0, double[] skinMatrices = null)
+        {
+            if (!uploaded) Upload();
+            var hw = GCHandle.Alloc(weights, GCHandleType.Pinned);
+            var hm = skinMatrices == null ? default(GCHandle) : GCHandle.Alloc(skinMatrices, GCHandleType.Pinned);
+            try
+            {
+                var u = new PtHip.pt_mesh_morph
+                {
+                    num_targets = weights.Length, normals_mode = normalsMode, num_bones = skinMatrices == null ? 0 : skinMatrices.Length / 16,
+                    weights = hw.AddrOfPinnedObject(), skin_matrices = skinMatrices == null ? IntPtr.Zero : hm.AddrOfPinnedObject(),
+                };
+                PtHip.Check(PtHip.pt_morph_meshes(ctx, ref u, out double ms), "pt_morph_meshes");
+                return ms;
+            }
+            finally
+            {
+                hw.Free();
+                if (skinMatrices != null) hm.Free();
+            }
+        }
+
+        /// <summary>The six arrays the last PoseMeshes, SkinMeshes or MorphMeshes left on the device (pt_read_pose), 3 floats per triangle each:
         /// v1, v2, v3, n1, n2, n3, derived normals included.</summary>
         public float[][] ReadPose(int numTriangles)
         {

@@ -29,6 +29,10 @@
  *   pt_set_skin        (new) linear blend skinning of that rest pose on the   Matrix.MulPosition / MulDirection,
  *   / pt_skin_meshes   device: four bone indices and weights per corner sent  Matrix.cs:134-150 (the reference has no
  *   / pt_read_skin     once, one matrix per bone per call, then the refits    skinning)
+ *   pt_set_morph       (new) morph targets (blend shapes) over that rest pose   (the reference has no morphing; the
+ *   / pt_morph_meshes  on the device: sparse per-corner deltas sent once, one   arithmetic is fixed below)
+ *   / pt_read_morph    weight per target per call, optionally the skin on top,
+ *                      then the refits
  *   pt_rebuild_meshes  (new) pt_update_meshes that also re-sorts the world    Tree.NewTree, Tree.cs:22-29 (the reference
  *   / pt_tri_bvh_cost  triangle BVH into a balanced median tree on the device  builds a new tree for every frame's scene)
  *                      for the new positions; the SAH cost of the tree as it
@@ -765,9 +769,9 @@ typedef struct pt_mesh_pose {
     const int32_t* mesh_mask;  /* [num_meshes] or NULL (= all); 0: the mesh takes its rest values verbatim */
 } pt_mesh_pose;
 int pt_pose_meshes(void* ctx, const pt_mesh_pose* u, double* out_kernel_ms);
-/* The six arrays the last pt_pose_meshes or pt_skin_meshes left staged on the device (derived normals included), [n][3] each in
+/* The six arrays the last pt_pose_meshes, pt_skin_meshes or pt_morph_meshes left staged on the device (derived normals included), [n][3] each in
  * pt_scene_desc order; any pointer may be NULL.  They stay until a pt_update_* or pt_read_tri_normals reuses the
- * staged arrays.  A NULL ctx, or no pose or skin staged: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+ * staged arrays.  A NULL ctx, or no pose, skin or morph staged: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_read_pose(void* ctx, float* v1, float* v2, float* v3, float* n1, float* n2, float* n3);
 
 /* Blend skinning on the device: a mesh that bends.  The host sends four bone indices and four weights
@@ -827,6 +831,86 @@ int pt_skin_meshes(void* ctx, const pt_mesh_skin* u, double* out_kernel_ms);
  * be NULL.  Synchronises and changes nothing.  A NULL ctx, or no skin installed: PT_ERR_INVALID_ARG; no scene:
  * PT_ERR_NO_SCENE. */
 int pt_read_skin(void* ctx, int32_t* bone1, int32_t* bone2, int32_t* bone3, float* weight1, float* weight2, float* weight3);
+
+/* Morph targets on the device: faces, muscle bulges and corrective shapes.  A morph target (blend
+ * shape) is a sparse set of per-corner offsets; a frame scales each target by one weight and adds it to the rest pose
+ * pt_set_rest_pose installed, before the skin.  The host sends the deltas once (pt_set_morph) and 4 bytes per target
+ * per frame (pt_morph_meshes), plus 128 bytes per bone when the call also skins.
+ *
+ * pt_set_morph installs the morph.  Target t owns the deltas target_first[t] .. target_first[t + 1] - 1; delta i moves
+ * corner corner[i] = 3 * triangle + c (c = 0, 1, 2 for v1, v2, v3; pt_scene_desc order) by dpos[i] and, when dnrm is
+ * given, its normal by dnrm[i].  Within a target the corners ascend strictly (no corner twice); a target may be empty.
+ * target_first, corner and dpos are required even when there is no delta.  The data is packed on the host into a
+ * sliced ELL format whose slice is one wave (64 consecutive triangles of one corner array; a slice is as long as its
+ * busiest corner, the rest is padding) and copied to a device workspace of its own: per step of a slice 128 B of
+ * 16-bit target indices and 768 B of position deltas, 768 B more with normal deltas, 12 B per slice, 4 B per target;
+ * pt_read_morph's counts[2] is the padded entry count (64 per step), what a sparsity pattern costs.  It is kept
+ * until the next pt_upload_scene; a later pt_set_morph replaces it (the new workspace is allocated and filled first,
+ * the old one released afterwards), a later pt_set_rest_pose or pt_set_skin keeps it.  It needs a scene, not a rest
+ * pose, and changes nothing a ray sees.  Values of deltas are not checked.  Synchronises before returning.
+ * Errors (nothing copied, a previous morph kept): a NULL ctx, desc, target_first, corner or dpos, reserved != 0,
+ * num_triangles different from the uploaded scene's, num_targets outside [1, PT_MORPH_MAX_TARGETS], target_first[0]
+ * != 0 or target_first decreasing, a corner outside [0, 3 * num_triangles) or not above its predecessor in the same
+ * target: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; the workspace not allocated: PT_ERR_OUT_OF_MEMORY. */
+#define PT_MORPH_MAX_TARGETS 65535
+typedef struct pt_morph_desc {
+    int32_t num_triangles;        /* must equal the uploaded scene's num_triangles */
+    int32_t num_targets;          /* 1..PT_MORPH_MAX_TARGETS */
+    int32_t reserved[2];          /* 0 */
+    const int64_t* target_first;  /* [num_targets + 1], target_first[0] = 0, non-decreasing; the last = number of deltas */
+    const int32_t* corner;        /* [deltas]: 3 * triangle + c, c = 0, 1, 2 (pt_scene_desc order); strictly ascending within a target */
+    const float*   dpos;          /* [deltas][3] */
+    const float*   dnrm;          /* [deltas][3] or NULL: the morph carries no normal deltas */
+} pt_morph_desc;
+int pt_set_morph(void* ctx, const pt_morph_desc* desc);
+/* pt_morph_meshes morphs the rest pose and refits.  A source triangle belongs to a mesh as for pt_pose_meshes; a loose
+ * triangle takes its rest values bit for bit whatever deltas name it (a light that is a loose emissive triangle
+ * returns to its rest vertices, as after a pose or a skin).  A delta of target t is live when weights[t] != 0 (false
+ * only for +-0; a NaN weight is live); a dead delta is skipped by a branch, not multiplied by zero, so a non-finite
+ * delta of a dead target changes nothing.  A corner of a mesh triangle with no live delta is copied bit for bit,
+ * position and normal.  Otherwise, per component, a = (double)p, the rest value, then over the corner's live deltas in
+ * ascending target order a = a + (double)weights[t] * (double)d; the position is one conversion of a to fp32.  The
+ * product of two widened floats is exact in fp64, so the result does not depend on whether the multiply and the add
+ * are contracted (the build keeps -ffp-contract=off anyway).  Normals: with normals_mode 0 and a morph that carries
+ * dnrm, the normal is accumulated the same way from the rest normal and dnrm, converted once, then normalised by the
+ * fp32 Normalize Matrix.MulDirection ends in (a zero-length result is NaN, as Normalize gives); with normals_mode 0
+ * and no dnrm the rest normals are copied; with PT_NORMALS_FACE or PT_NORMALS_SMOOTH the normals of every triangle
+ * are derived from the morphed positions as pt_update_meshes derives them.  A morph is always made from the rest pose,
+ * never from the current state: repeated morphs do not drift, a later pt_update_*, pt_pose_meshes or pt_skin_meshes
+ * overwrites the morph and the morph overwrites them.  An instanced mesh is morphed in its object space.
+ * With skin_matrices the call composes the two deformers: the morphed six arrays (normals as normals_mode 0 gives them
+ * above; with PT_NORMALS_FACE or PT_NORMALS_SMOOTH the rest normals are carried) go to an intermediate device buffer
+ * (72 B per triangle, allocated by the first such call and kept until the next pt_upload_scene), and pt_skin_meshes'
+ * kernel blends that buffer in place of the rest pose, with the same normals_mode: the result is skin(morph(rest))
+ * exactly.  It needs a skin installed (pt_set_skin) and num_bones equal to the installed skin's; without
+ * skin_matrices num_bones is 0.
+ * The arrays then go through what pt_update_meshes runs, so everything on the device is, word for word, what
+ * pt_update_meshes with the same arrays computed on the host leaves; pt_read_pose returns them, and pt_rebuild_meshes /
+ * pt_rebuild_blas with u == NULL take them.  Stream order, the synchronisation, the Buffer, pass state, counters and
+ * non-finite values are as for pt_pose_meshes; out_kernel_ms (may be NULL) covers the morph kernel, the skin kernel,
+ * the normals kernels and the refits.
+ * Errors (nothing launched or copied, the scene untouched): a NULL ctx, u or weights, reserved != 0, a normals_mode
+ * outside {0, 1, 2}, no morph installed, num_targets different from the installed morph's, num_bones != 0 without
+ * skin_matrices, skin_matrices with no skin installed or num_bones different from the installed skin's, no rest pose
+ * installed: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; a workspace not allocated: PT_ERR_OUT_OF_MEMORY;
+ * PT_NORMALS_SMOOTH with 3 * num_triangles >= 2^31: PT_ERR_UNSUPPORTED.  A scene with no triangle in any BVH: PT_OK,
+ * nothing launched. */
+typedef struct pt_mesh_morph {
+    int32_t num_targets;          /* must equal the installed morph's */
+    int32_t normals_mode;         /* 0, PT_NORMALS_FACE, PT_NORMALS_SMOOTH */
+    int32_t num_bones;            /* 0 when skin_matrices is NULL, else the installed skin's */
+    int32_t reserved;             /* 0 */
+    const float*  weights;        /* [num_targets], required */
+    const double* skin_matrices;  /* NULL: morph only; else [num_bones][16]: morph, then pt_skin_meshes' blend of the morphed pose */
+} pt_mesh_morph;
+int pt_morph_meshes(void* ctx, const pt_mesh_morph* u, double* out_kernel_ms);
+/* The installed morph in pt_morph_desc's form, bit for bit: counts receives the targets, the deltas and the padded
+ * entries held on the device; target_first [targets + 1], corner [deltas], dpos and dnrm [deltas][3].  The packed
+ * device data is read back and unpacked on the host, so this is what the device holds.  Any pointer but ctx may be
+ * NULL (call once for counts, then with arrays); dnrm is written only when the morph carries normal deltas.
+ * Synchronises and changes nothing.  A NULL ctx, or no morph installed: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
+int pt_read_morph(void* ctx, int64_t counts[3] /* targets, deltas, padded entries held on the device */,
+                  int64_t* target_first, int32_t* corner, float* dpos, float* dnrm);
 
 /* Re-sorting the world triangle BVH on the device.  The updates above refit: they keep the topology
  * of the pose the tree was built for, and a mesh deformed far from it traces an ever worse tree.  pt_rebuild_meshes

@@ -37,6 +37,7 @@ SHAPE_SDF, SHAPE_VOLUME, SHAPE_TRANSFORMED = 5, 6, 7
 MARCH_LANE, MARCH_WAVE = 1, 2   # pt_intersect / pt_occluded flags (PT_MARCH_*)
 NORMALS_FACE, NORMALS_SMOOTH = 1, 2   # pt_normals_mode (pt_update_triangles_normals)
 SKIN_INFLUENCES, SKIN_MAX_BONES = 4, 65536   # PT_SKIN_INFLUENCES, PT_SKIN_MAX_BONES (pt_set_skin)
+MORPH_MAX_TARGETS = 65535                    # PT_MORPH_MAX_TARGETS (pt_set_morph)
 REBUILD_WORLD, REBUILD_BLAS = 1, 2    # pt_rebuild_blas' `what`
 LOOK_ENV = 1                          # pt_material_update.flags (PT_LOOK_ENV)
 TEXELS_F64, TEXELS_RGB8, TEXELS_RGBA8 = 0, 1, 2   # pt_texel_format
@@ -166,6 +167,16 @@ class pt_mesh_skin(C.Structure):
                 ("matrices", _d)]
 
 
+class pt_morph_desc(C.Structure):
+    _fields_ = [("num_triangles", C.c_int32), ("num_targets", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("target_first", C.POINTER(C.c_int64)), ("corner", _i), ("dpos", _f), ("dnrm", _f)]
+
+
+class pt_mesh_morph(C.Structure):
+    _fields_ = [("num_targets", C.c_int32), ("normals_mode", C.c_int32), ("num_bones", C.c_int32), ("reserved", C.c_int32),
+                ("weights", _f), ("skin_matrices", _d)]
+
+
 class pt_volume_update(C.Structure):
     _fields_ = [("num_volumes", C.c_int32), ("reserved", C.c_int32 * 3), ("data", C.POINTER(_d)),
                 ("windows", C.POINTER(C.POINTER(pt_volume_window)))]
@@ -243,6 +254,9 @@ SIGNATURES = {
     "pt_set_skin": (C.c_int, [C.c_void_p, C.POINTER(pt_skin_desc)]),
     "pt_skin_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_skin), _d]),
     "pt_read_skin": (C.c_int, [C.c_void_p, _i, _i, _i, _f, _f, _f]),
+    "pt_set_morph": (C.c_int, [C.c_void_p, C.POINTER(pt_morph_desc)]),
+    "pt_morph_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_morph), _d]),
+    "pt_read_morph": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i, _f, _f]),
     "pt_rebuild_meshes": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_update), _d]),
     "pt_tri_bvh_cost": (C.c_int, [C.c_void_p, _d]),
     "pt_rebuild_blas": (C.c_int, [C.c_void_p, C.POINTER(pt_mesh_update), C.c_int32, _d]),

@@ -34,6 +34,7 @@
 #include "pt_scene.h"
 #include "pt_scene_compile.h"
 #include "pt_shape_refit.h"
+#include "pt_morph.h"
 #include "pt_skin.h"
 #include "pt_texture.h"
 #include "pt_update_layout.h"
@@ -153,6 +154,10 @@ hipError_t launch_pose(int64_t n, int32_t num_meshes, const int32_t* group, cons
 hipError_t launch_skin(int64_t n, int32_t num_bones, const int32_t* group, const double* matrices, bool normals,
                        const uint16_t* const bone[3], const float* const weight[3], const float* const rest[6], float* const out[6],
                        hipStream_t stream);
+// pt_morph.hip
+hipError_t launch_morph(int64_t n, int32_t num_targets, const int32_t* group, const float* weights, int normals, const int32_t* len,
+                        const int64_t* first, const uint16_t* target, const float* dpos, const float* dnrm, const float* const rest[6],
+                        float* const out[6], hipStream_t stream);
 // pt_volume.hip
 hipError_t launch_vol_rebuild(const DevVolume& v, bool new_data, hipStream_t stream);
 // pt_texture.hip
@@ -252,6 +257,10 @@ struct SceneDyn {
     Workspace<pt::PoseDev> pose_ws;         // pt_set_rest_pose
     Workspace<pt::SkinDev> skin_ws;         // pt_set_skin
     int32_t skin_bones = 0;                 // the installed skin's num_bones (0: none)
+    Workspace<pt::MorphDev> morph_ws;       // pt_set_morph: the packed planes (pt_morph.h)
+    Workspace<pt::MorphTmpDev> morph_tmp_ws;   // first pt_morph_meshes with skin_matrices: the morphed arrays the skin reads
+    int32_t morph_targets = 0;              // the installed morph's num_targets (0: none), its deltas, slices and steps
+    int64_t morph_deltas = 0, morph_slices = 0, morph_steps = 0;
     Workspace<RebuildDev> rebuild_ws;       // first pt_rebuild_meshes
     Workspace<pt::QueryDev> query_ws;       // first pt_intersect_hits: its own copies of the identity tables
     bool query_src_stale = false;           // a pt_rebuild_meshes permuted refit.src_of_pos after query_ws took its copy
@@ -275,7 +284,7 @@ struct SceneDyn {
     size_t lights_cap = 0;
     std::vector<pt::DevTexture> texs;
     DeviceArray tex_stage;
-    bool pose_staged = false;            // refit_ws' staged arrays hold the last pt_pose_meshes' or pt_skin_meshes' (pt_read_pose)
+    bool pose_staged = false;            // refit_ws' staged arrays hold the last pose, skin or morph (pt_read_pose)
     bool blas_boxes_on_device = false;   // blas_ws holds the meshes' boxes (after the first pt_update_meshes)
     void release_device() {
         refit_ws.release();
@@ -284,6 +293,8 @@ struct SceneDyn {
         blas_ws.release();
         pose_ws.release();
         skin_ws.release();
+        morph_ws.release();
+        morph_tmp_ws.release();
         rebuild_ws.release();
         blas_rebuild_ws.release();
         query_ws.release();
@@ -1751,7 +1762,7 @@ int update_run(Ctx* c, const UpdateCall& U, double* out_kernel_ms) {
     return kernel_ms(c, out_kernel_ms);
 }
 
-// An update from host arrays: src staged (NULL: the pose pt_pose_meshes or pt_skin_meshes left staged is used and stays
+// An update from host arrays: src staged (NULL: the pose, skin or morph left staged is used and stays
 // readable), then run
 int update_stage_and_run(Ctx* c, const UpdateCall& U, const float* const src[6], double* out_kernel_ms) {
     if (src) {
@@ -2040,6 +2051,150 @@ int pt_read_skin(void* ctx, int32_t* bone1, int32_t* bone2, int32_t* bone3, floa
     return PT_OK;
 }
 
+// ---- morph targets on the device
+static_assert(pt::kMorphMaxTargets == PT_MORPH_MAX_TARGETS, "pt_morph.h and the ABI agree on the number of targets");
+
+int pt_set_morph(void* ctx, const pt_morph_desc* d) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!d) return fail(PT_ERR_INVALID_ARG, "set morph: desc is NULL");
+    if (d->reserved[0] != 0 || d->reserved[1] != 0) return fail(PT_ERR_INVALID_ARG, "set morph: reserved must be 0");
+    if (!d->target_first || !d->corner || !d->dpos) return fail(PT_ERR_INVALID_ARG, "set morph: target_first, corner and dpos are required");
+    if (d->num_targets < 1 || d->num_targets > PT_MORPH_MAX_TARGETS)
+        return fail(PT_ERR_INVALID_ARG, "set morph: num_targets is " + std::to_string(d->num_targets) + ", outside [1, " +
+                                            std::to_string(PT_MORPH_MAX_TARGETS) + "]");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const int32_t n = Y.refit.num_triangles;
+    if (d->num_triangles != n)
+        return fail(PT_ERR_INVALID_ARG, "set morph: num_triangles is " + std::to_string(d->num_triangles) + ", the uploaded scene has " +
+                                            std::to_string(n));
+    // every delta before the first copy: the packer and the kernel index with what this accepts
+    std::string why;
+    if (!pt::morph_check(n, d->num_targets, d->target_first, d->corner, &why)) return fail(PT_ERR_INVALID_ARG, "set morph: " + why);
+    pt::MorphPacked P;
+    pt::morph_pack(n, d->num_targets, d->target_first, d->corner, d->dpos, d->dnrm, P);
+    PT_HIP(hipSetDevice(c->device));
+    // the planes' sizes follow the sparsity pattern: always a new workspace, which replaces the installed one once it is filled
+    Workspace<pt::MorphDev> fresh;
+    if (const int rc = ensure_workspace(c, fresh, "morph",
+                                        [&](void* base) { return pt::morph_layout(P.slices, P.steps, P.has_dnrm, P.num_targets, base); },
+                                        [&](const pt::MorphDev& M, Uploader& up) {
+                                            up(M.len, P.len);
+                                            up(M.first, P.first);
+                                            up(M.target, P.target);
+                                            up(M.dpos, P.dpos);
+                                            if (M.dnrm) up(M.dnrm, P.dnrm);
+                                        }))
+        return rc;
+    const hipError_t e = hipStreamSynchronize(c->stream);   // P's arrays live until here
+    if (e != hipSuccess) {
+        fresh.release();
+        return check_hip(e, "staging the morph");
+    }
+    Y.morph_ws.release();
+    Y.morph_ws = fresh;
+    Y.morph_targets = P.num_targets;
+    Y.morph_deltas = P.deltas;
+    Y.morph_slices = P.slices;
+    Y.morph_steps = P.steps;
+    return PT_OK;
+}
+
+int pt_morph_meshes(void* ctx, const pt_mesh_morph* u, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!u) return fail(PT_ERR_INVALID_ARG, "morph meshes: u is NULL");
+    if (u->reserved != 0) return fail(PT_ERR_INVALID_ARG, "morph meshes: reserved must be 0");
+    if (const int rc = check_normals_mode("morph meshes", u->normals_mode)) return rc;
+    if (!u->weights) return fail(PT_ERR_INVALID_ARG, "morph meshes: weights is NULL");
+    const bool skin = u->skin_matrices != nullptr;
+    if (!skin && u->num_bones != 0) return fail(PT_ERR_INVALID_ARG, "morph meshes: num_bones is not 0 and skin_matrices is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    const pt::RefitTables& T = Y.refit;
+    if (!Y.morph_ws.mem.ptr || Y.morph_targets == 0) return fail(PT_ERR_INVALID_ARG, "morph meshes: no morph (pt_set_morph)");
+    if (u->num_targets != Y.morph_targets)
+        return fail(PT_ERR_INVALID_ARG, "morph meshes: num_targets is " + std::to_string(u->num_targets) + ", the installed morph has " +
+                                            std::to_string(Y.morph_targets));
+    if (skin) {
+        if (!Y.skin_ws.mem.ptr || Y.skin_bones == 0) return fail(PT_ERR_INVALID_ARG, "morph meshes: skin_matrices given and no skin (pt_set_skin)");
+        if (u->num_bones != Y.skin_bones)
+            return fail(PT_ERR_INVALID_ARG, "morph meshes: num_bones is " + std::to_string(u->num_bones) + ", the installed skin has " +
+                                                std::to_string(Y.skin_bones));
+    }
+    if (!Y.pose_ws.mem.ptr) return fail(PT_ERR_INVALID_ARG, "morph meshes: no rest pose (pt_set_rest_pose)");
+    // the morphed (and skinned) normals are staged unless a mode derives them; the lights return to their rest vertices
+    const UpdateCall U{T.num_triangles, normals_of(u->normals_mode, true), {nullptr, nullptr, nullptr}, nullptr};
+    bool launch = false;
+    if (const int rc = update_prepare(c, U, true, out_kernel_ms, &launch)) return rc;
+    if (!launch) return PT_OK;
+    if (skin)
+        if (const int rc = ensure_workspace(c, Y.morph_tmp_ws, "morph intermediate",
+                                            [&](void* base) { return pt::morph_tmp_layout(T.num_triangles, base); },
+                                            [](const pt::MorphTmpDev&, Uploader&) {}))
+            return rc;
+    const pt::PoseDev& P = Y.pose_ws.at;
+    const pt::MorphDev& M = Y.morph_ws.at;
+    PT_HIP(hipMemcpyAsync(M.weights, u->weights, (size_t)u->num_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (skin)
+        PT_HIP(hipMemcpyAsync(Y.skin_ws.at.matrices, u->skin_matrices, (size_t)u->num_bones * 16 * sizeof(double), hipMemcpyHostToDevice,
+                              c->stream));
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    // given normals: blended with dnrm, or copied when the morph has none; derived ones: not written, or carried to the skin
+    const bool given = U.normals == Normals::Given;
+    const int normals = given ? (M.dnrm ? 2 : 1) : skin ? 1 : 0;
+    float* const* out = skin ? Y.morph_tmp_ws.at.out : Y.refit_ws.at.in;
+    PT_HIP(pt::launch_morph(T.num_triangles, u->num_targets, P.group, M.weights, normals, M.len, M.first, M.target, M.dpos, M.dnrm,
+                            P.rest, out, c->stream));
+    if (skin) {
+        const pt::SkinDev& S = Y.skin_ws.at;
+        PT_HIP(pt::launch_skin(T.num_triangles, u->num_bones, P.group, S.matrices, given, S.bone, S.weight, Y.morph_tmp_ws.at.out,
+                               Y.refit_ws.at.in, c->stream));
+    }
+    Y.pose_staged = true;
+    return update_run(c, U, out_kernel_ms);
+}
+
+int pt_read_morph(void* ctx, int64_t counts[3], int64_t* target_first, int32_t* corner, float* dpos, float* dnrm) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    SceneDyn& Y = c->dyn;
+    if (!Y.morph_ws.mem.ptr || Y.morph_targets == 0) return fail(PT_ERR_INVALID_ARG, "read morph: no morph (pt_set_morph)");
+    if (counts) { counts[0] = Y.morph_targets; counts[1] = Y.morph_deltas; counts[2] = Y.morph_steps * pt::kMorphSlice; }
+    if (!target_first && !corner && !dpos && !dnrm) return PT_OK;
+    PT_HIP(hipSetDevice(c->device));
+    const pt::MorphDev& M = Y.morph_ws.at;
+    pt::MorphPacked P;
+    P.n = Y.refit.num_triangles;
+    P.slices = Y.morph_slices;
+    P.steps = Y.morph_steps;
+    P.deltas = Y.morph_deltas;
+    P.num_targets = Y.morph_targets;
+    P.has_dnrm = M.dnrm != nullptr;
+    P.len.resize((size_t)P.slices);
+    P.first.resize((size_t)P.slices);
+    P.target.resize((size_t)P.padded());
+    P.dpos.resize((size_t)P.padded() * 3);
+    if (P.has_dnrm) P.dnrm.resize((size_t)P.padded() * 3);
+    PT_HIP(read_back(c, P.len.data(), M.len, P.len.size() * sizeof(int32_t)));
+    PT_HIP(read_back(c, P.first.data(), M.first, P.first.size() * sizeof(int64_t)));
+    PT_HIP(read_back(c, P.target.data(), M.target, P.target.size() * sizeof(uint16_t)));
+    PT_HIP(read_back(c, P.dpos.data(), M.dpos, P.dpos.size() * sizeof(float)));
+    if (P.has_dnrm) PT_HIP(read_back(c, P.dnrm.data(), M.dnrm, P.dnrm.size() * sizeof(float)));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    // the device's own len and first are what the unpacker walks: checked against the sizes the planes were read with
+    int64_t steps = 0;
+    for (size_t s = 0; s < P.len.size(); s++) {
+        if (P.len[s] < 0 || P.first[s] != steps) return fail(PT_ERR_HIP, "read morph: the device's slice table is not the installed morph's");
+        steps += P.len[s];
+    }
+    if (steps != P.steps || !pt::morph_unpack(P, target_first, corner, dpos, dnrm))
+        return fail(PT_ERR_HIP, "read morph: the device's planes are not the installed morph's");
+    return PT_OK;
+}
+
 }  // extern "C"
 
 // ---- re-sorting the triangle BVH on the device, and the BLASes (§4j)
@@ -2069,7 +2224,7 @@ int rebuild_world_prepare(Ctx* c, const std::string& who, RebuildRun& run) {
 // pt_rebuild_meshes and pt_rebuild_blas after their own argument checks: world / blas say which trees are re-sorted
 int rebuild_call(Ctx* c, const std::string& who, const pt_mesh_update* u, bool world, bool blas, double* out_kernel_ms) {
     SceneDyn& Y = c->dyn;
-    // u NULL: the staged pose or skin with its normals, the lights at their rest vertices
+    // u NULL: the staged pose, skin or morph with its normals, the lights at their rest vertices
     RebuildRun run{};
     UpdateCall U{Y.refit.num_triangles, Normals::Given, {nullptr, nullptr, nullptr}, nullptr};
     if (u) U = UpdateCall{u->num_triangles, normals_of(u->normals_mode, u->n1), {u->v1, u->v2, u->v3}, nullptr};

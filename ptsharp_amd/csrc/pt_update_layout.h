@@ -1,8 +1,8 @@
 // pt_update_layout.h — how the moving-geometry entry points (pt_api.hip) carve their per-scene
 // device workspaces: one allocation each, its parts 256-B aligned and in the order listed; and pt_rebuild_blas' host
 // tables (its plans, level lists and tail workgroups).  Host code only: no HIP call, compiles with g++
-// (tests/native/rebuild_check.cpp, blas_check.cpp, shapes_check.cpp and blas_rebuild_check.cpp check the layouts and
-// tables against what the kernels index).  With a null base the pointers are the parts' offsets.
+// (tests/native/rebuild_check.cpp, blas_check.cpp, shapes_check.cpp, blas_rebuild_check.cpp and morph_check.cpp check
+// the layouts and tables against what the kernels index).  With a null base the pointers are the parts' offsets.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -284,6 +284,46 @@ inline SkinDev skin_layout(int32_t num_triangles, int32_t bone_cap, void* base) 
     for (float*& a : r.weight) a = c.take<float>((size_t)num_triangles * 4);
     r.matrices = c.take<double>((size_t)bone_cap * 16);
     r.bone_cap = bone_cap;
+    r.bytes = c.bytes();
+    return r;
+}
+
+// pt_set_morph: [len | first | target | dpos | dnrm | weights]: pt_morph.h's packed planes (per step of a slice 128 B
+// of 16-bit targets and 768 B of position deltas, 768 B more with normal deltas; 12 B per slice), then room for one
+// fp32 weight per target.  Every part starts on a 256-B boundary and a step is a whole number of 128-B lines, so every
+// step of every plane starts on a line.
+struct MorphDev {
+    int32_t* len;
+    int64_t* first;
+    uint16_t* target;
+    float* dpos;
+    float* dnrm;      // NULL: the morph carries no normal deltas
+    float* weights;
+    size_t bytes;
+};
+inline MorphDev morph_layout(int64_t slices, int64_t steps, bool has_dnrm, int32_t num_targets, void* base) {
+    Carver c(base);
+    MorphDev r{};
+    r.len = c.take<int32_t>((size_t)slices);
+    r.first = c.take<int64_t>((size_t)slices);
+    r.target = c.take<uint16_t>((size_t)steps * 64);
+    r.dpos = c.take<float>((size_t)steps * 64 * 3);
+    float* const dnrm = c.take<float>(has_dnrm ? (size_t)steps * 64 * 3 : 0);
+    r.dnrm = has_dnrm ? dnrm : nullptr;
+    r.weights = c.take<float>((size_t)num_targets);
+    r.bytes = c.bytes();
+    return r;
+}
+// pt_morph_meshes with skin_matrices: the morphed v1 v2 v3 n1 n2 n3 between the two kernels (72 B per triangle), made
+// by the first such call
+struct MorphTmpDev {
+    float* out[6];
+    size_t bytes;
+};
+inline MorphTmpDev morph_tmp_layout(int64_t num_triangles, void* base) {
+    Carver c(base);
+    MorphTmpDev r{};
+    for (float*& a : r.out) a = c.take<float>((size_t)num_triangles * 3);
     r.bytes = c.bytes();
     return r;
 }

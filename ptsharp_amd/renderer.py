@@ -155,6 +155,7 @@ class Renderer:
         self._lib = None
         self._uploaded = None
         self._rest_of = None         # the FlatScene whose rest pose the device holds (SetRestPose)
+        self._morph_of = None        # (the FlatScene whose morph the device holds, whether it carries normal deltas) (SetMorph)
         self._mirror_stale = False   # PoseMeshes(mirror=False) left the uploaded FlatScene's triangle arrays behind
         self._pass = 0
         self.iterations = 0
@@ -190,6 +191,7 @@ class Renderer:
             _abi.check(self._lib.pt_upload_scene(self._ctx, C.byref(flat.desc)), "pt_upload_scene")
             self._uploaded = flat
             self._rest_of = None
+            self._morph_of = None
             self._mirror_stale = False
 
     def _pass_params(self, spp=None, pass_index=None):
@@ -1120,8 +1122,103 @@ class Renderer:
                                           *[x.ctypes.data_as(C.POINTER(C.c_float)) for x in w]), "pt_read_skin")
         return np.stack(b, axis=1), np.stack(w, axis=1)
 
+    def SetMorph(self, targets, normal_deltas=None) -> None:
+        """Installs the morph targets MorphMeshes adds to the rest pose (pt_set_morph).  `targets` is a list with one
+        (corners, dpos[, dnrm]) per target: corners [k] integers 3 * triangle + c (c = 0, 1, 2 for v1, v2, v3), strictly
+        ascending, dpos and dnrm [k, 3] float32; or the packed arrays as a dict with target_first [T + 1], corner [D],
+        dpos [D, 3] and optionally dnrm [D, 3].  normal_deltas=True requires every target to carry dnrm, False drops
+        them, None takes them when every target of the list has them.  Kept on the device until the next upload."""
+        self._ensure_scene()
+        n = len(self._uploaded.tri_material)
+        if isinstance(targets, dict):
+            first = np.ascontiguousarray(targets["target_first"], np.int64).reshape(-1)
+            corner = np.ascontiguousarray(targets["corner"], np.int32).reshape(-1)
+            dpos = np.ascontiguousarray(targets["dpos"], np.float32).reshape(-1, 3)
+            dnrm = targets.get("dnrm")
+            if normal_deltas and dnrm is None:
+                raise ValueError("normal_deltas=True and the packed arrays have no dnrm")
+            dnrm = None if dnrm is None or normal_deltas is False else np.ascontiguousarray(dnrm, np.float32).reshape(-1, 3)
+        else:
+            targets = list(targets)
+            have = [len(t) > 2 and t[2] is not None for t in targets]
+            if normal_deltas and not all(have):
+                raise ValueError("normal_deltas=True and a target has no dnrm")
+            with_n = bool(targets) and all(have) if normal_deltas is None else bool(normal_deltas)
+            first = np.zeros(len(targets) + 1, np.int64)
+            first[1:] = np.cumsum([len(np.asarray(t[0]).reshape(-1)) for t in targets])
+            cat = lambda k, dtype, shape: (np.concatenate([np.asarray(t[k], dtype).reshape(shape) for t in targets])
+                                           if targets else np.zeros(shape, dtype).reshape(shape)[:0])
+            corner = np.ascontiguousarray(cat(0, np.int32, (-1,)))
+            dpos = np.ascontiguousarray(cat(1, np.float32, (-1, 3)))
+            dnrm = np.ascontiguousarray(cat(2, np.float32, (-1, 3))) if with_n else None
+        if len(dpos) != len(corner) or (dnrm is not None and len(dnrm) != len(corner)) or (len(first) and first[-1] != len(corner)):
+            raise ValueError("corner, dpos and dnrm hold one entry per delta, target_first[-1] of them")
+        # (room for one entry past the end, so that a morph with no delta still passes non-NULL arrays)
+        room = lambda x: None if x is None else np.ascontiguousarray(np.concatenate([x.reshape(-1), np.zeros(3, x.dtype)]))
+        corner_a, dpos_a, dnrm_a = room(corner), room(dpos), room(dnrm)
+        d = _abi.pt_morph_desc()
+        d.num_triangles, d.num_targets = n, len(first) - 1
+        d.target_first = first.ctypes.data_as(C.POINTER(C.c_int64))
+        d.corner = corner_a.ctypes.data_as(C.POINTER(C.c_int32))
+        d.dpos = dpos_a.ctypes.data_as(C.POINTER(C.c_float))
+        d.dnrm = None if dnrm_a is None else dnrm_a.ctypes.data_as(C.POINTER(C.c_float))
+        _abi.check(self._lib.pt_set_morph(self._ctx, C.byref(d)), "pt_set_morph")
+        self._morph_of = (self._uploaded, dnrm is not None)
+
+    def MorphMeshes(self, weights, normals=None, skin=None, mirror=True) -> float:
+        """Morphs every mesh of the scene on the device, from the rest pose and the targets SetMorph installed
+        (pt_morph_meshes): `weights` holds one float32 per target; a weight of 0 makes its target dead.  normals=None
+        adds the targets' normal deltas to the rest normals and normalises (the rest normals stay when the morph has
+        none), "face" or "smooth" derives them from the morphed positions.  `skin` (a sequence of Matrix or a [B, 16]
+        float64 array, one per bone of the skin SetSkin installed) skins the morphed pose as SkinMeshes skins the rest
+        pose.  Loose triangles take their rest values.  The BVHs, the instances' boxes and the lights are refitted as
+        UpdateMeshes refits them.  The rest pose is installed on first use (SetRestPose()); mirror is PoseMeshes'.
+        Returns the device time of the kernels in ms."""
+        self._ensure_scene()
+        flat = self._uploaded
+        if normals not in (None, "face", "smooth"):
+            raise ValueError('normals is None, "face" or "smooth"')
+        if self._rest_of is not flat:
+            self.SetRestPose()
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        u = _abi.pt_mesh_morph()
+        u.num_targets = len(w)
+        u.normals_mode = 0 if normals is None else _abi.NORMALS_FACE if normals == "face" else _abi.NORMALS_SMOOTH
+        u.weights = w.ctypes.data_as(C.POINTER(C.c_float))
+        if skin is not None:
+            m = np.ascontiguousarray([getattr(k, "m", k) for k in skin], np.float64).reshape(-1, 16)
+            u.num_bones = len(m)
+            u.skin_matrices = m.ctypes.data_as(C.POINTER(C.c_double))
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_morph_meshes(self._ctx, C.byref(u), C.byref(ms)), "pt_morph_meshes")
+        # a device time of exactly 0: nothing was launched (no triangle of the scene is in a BVH), nothing to mirror
+        self._mirror_stale = ms.value != 0.0
+        if mirror:
+            self._refresh_mirror()
+        return float(ms.value)
+
+    def ReadMorph(self):
+        """The installed morph as the device holds it, unpacked (pt_read_morph): a dict with target_first [T + 1] int64,
+        corner [D] int32, dpos [D, 3] float32, dnrm [D, 3] float32 or None when the morph carries no normal deltas, and
+        padded: the entries the packed format holds on the device, padding included.  (Whether to ask for dnrm is what this
+        Renderer's SetMorph installed.)"""
+        self._ensure_scene()
+        counts = (C.c_int64 * 3)()
+        _abi.check(self._lib.pt_read_morph(self._ctx, counts, None, None, None, None), "pt_read_morph")
+        t, k = int(counts[0]), int(counts[1])
+        first = np.zeros(t + 1, np.int64)
+        corner = np.zeros(k + 1, np.int32)
+        dpos = np.zeros((k + 1, 3), np.float32)
+        with_n = self._morph_of is not None and self._morph_of[0] is self._uploaded and self._morph_of[1]
+        dnrm = np.zeros((k + 1, 3), np.float32) if with_n else None
+        _abi.check(self._lib.pt_read_morph(self._ctx, counts, first.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           corner.ctypes.data_as(C.POINTER(C.c_int32)), dpos.ctypes.data_as(C.POINTER(C.c_float)),
+                                           None if dnrm is None else dnrm.ctypes.data_as(C.POINTER(C.c_float))), "pt_read_morph")
+        return dict(target_first=first, corner=corner[:k].copy(), dpos=dpos[:k].copy(), dnrm=None if dnrm is None else dnrm[:k].copy(),
+                    padded=int(counts[2]))
+
     def ReadPose(self):
-        """The six arrays the last PoseMeshes or SkinMeshes left on the device (pt_read_pose): v1, v2, v3, n1, n2, n3, [n, 3]
+        """The six arrays the last PoseMeshes, SkinMeshes or MorphMeshes left on the device (pt_read_pose): v1, v2, v3, n1, n2, n3, [n, 3]
         float32 each, derived normals included.  Also brings a FlatScene left stale by mirror=False up to date."""
         self._ensure_scene()
         n = len(self._uploaded.tri_material)
