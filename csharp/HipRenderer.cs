@@ -175,6 +175,14 @@ namespace PTSharpCore
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        public struct pt_temporal_params
+        {
+            public int max_history;      // 0..2^20
+            public int reserved;         // 0
+            public double sigma_depth;   // >= 0, finite; 0 = depth test off
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         public struct pt_mesh_data
         {
             public int num_triangles;
@@ -343,6 +351,17 @@ namespace PTSharpCore
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_features(IntPtr ctx, int feature, IntPtr dst);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_features(IntPtr ctx, double[] albedo, float[] normal, double[] depth, int[] kind);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_denoise_guided(IntPtr ctx, ref pt_denoise_guided_params p, out double kernelMs);
+        // motion vectors and temporal accumulation across animated frames (pt_motion_array: PT_MOTION_*)
+        public const int PT_MOTION_SHAPE_I32 = 0, PT_MOTION_PRIM_I32 = 1, PT_MOTION_DEPTH_F64 = 2, PT_MOTION_PREV_XY_F64 = 3,
+                         PT_MOTION_PREV_DEPTH_F64 = 4, PT_MOTION_PREV_PIXEL_I32 = 5, PT_MOTION_STATUS_I32 = 6;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_motion_snapshot(IntPtr ctx, ref pt_camera cam);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_render_motion(IntPtr ctx, ref pt_camera cam, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_motion(IntPtr ctx, int what, IntPtr dst);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_accumulate_temporal(IntPtr ctx, ref pt_temporal_params p, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_temporal(IntPtr ctx, double[] m, double[] v, int[] n, int[] status);
+        // plain: a pt_denoise_params*, or guided: a pt_denoise_guided_params*; the other IntPtr.Zero
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_denoise_temporal(IntPtr ctx, IntPtr plain, IntPtr guided, out double kernelMs);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_reset_temporal(IntPtr ctx);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_read_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_write_tiles(IntPtr ctx, int[] tiles, int num_tiles, double[] m, double[] v, int[] n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pt_reset_buffer(IntPtr ctx);
@@ -782,6 +801,84 @@ namespace PTSharpCore
             var p = new PtHip.pt_denoise_params { iterations = DenoiseIterations, reserved = 0, sigma_colour = DenoiseSigmaColour };
             PtHip.Check(PtHip.pt_denoise(ctx, ref p, out double ms), "pt_denoise");
             return ms;
+        }
+
+        /// <summary>AccumulateTemporal's parameters: the samples the history may weigh at most (0..2^20) and the relative
+        /// depth tolerance (0 = off).  Design defaults, not tuned values.</summary>
+        public int TemporalMaxHistory = 32;
+        public double TemporalSigmaDepth = 0.1;
+
+        /// <summary>Record the camera and the geometry as the device holds it as "the previous frame" (pt_motion_snapshot).</summary>
+        public void MotionSnapshot()
+        {
+            var cam = Cam();
+            PtHip.Check(PtHip.pt_motion_snapshot(ctx, ref cam), "pt_motion_snapshot");
+        }
+
+        /// <summary>One ray through each pixel's centre and where its hit point was in the snapshot's frame
+        /// (pt_render_motion).  Returns the device time of the kernel in ms.</summary>
+        public double RenderMotion()
+        {
+            var cam = Cam();
+            PtHip.Check(PtHip.pt_render_motion(ctx, ref cam, out double ms), "pt_render_motion");
+            return ms;
+        }
+
+        /// <summary>One array of the last RenderMotion (pt_read_motion; what: PtHip.PT_MOTION_*): int[W*H] for the _I32
+        /// arrays, double[W*H] for the _F64 ones, double[W*H*2] for PT_MOTION_PREV_XY_F64.</summary>
+        public Array Motion(int what)
+        {
+            bool f64 = what == PtHip.PT_MOTION_DEPTH_F64 || what == PtHip.PT_MOTION_PREV_XY_F64 || what == PtHip.PT_MOTION_PREV_DEPTH_F64;
+            int n = W * H * (what == PtHip.PT_MOTION_PREV_XY_F64 ? 2 : 1);
+            Array a = f64 ? new double[n] : new int[n];
+            var pin = GCHandle.Alloc(a, GCHandleType.Pinned);
+            try { PtHip.Check(PtHip.pt_read_motion(ctx, what, pin.AddrOfPinnedObject()), "pt_read_motion"); }
+            finally { pin.Free(); }
+            return a;
+        }
+
+        /// <summary>Merge the history into the Buffer's statistics through the last RenderMotion
+        /// (pt_accumulate_temporal); the Buffer is unchanged.  Returns the device time of the kernel in ms.</summary>
+        public double AccumulateTemporal()
+        {
+            var p = new PtHip.pt_temporal_params { max_history = TemporalMaxHistory, reserved = 0, sigma_depth = TemporalSigmaDepth };
+            PtHip.Check(PtHip.pt_accumulate_temporal(ctx, ref p, out double ms), "pt_accumulate_temporal");
+            return ms;
+        }
+
+        /// <summary>The last AccumulateTemporal's result (pt_read_temporal): M, V [W*H*3], N, status [W*H].</summary>
+        public void Temporal(double[] m, double[] v, int[] n, int[] status)
+        {
+            PtHip.Check(PtHip.pt_read_temporal(ctx, m, v, n, status), "pt_read_temporal");
+        }
+
+        /// <summary>DenoiseBuffer on the temporal result instead of the Buffer (pt_denoise_temporal).</summary>
+        public unsafe double DenoiseTemporal()
+        {
+            double ms;
+            if (DenoiseGuided)
+            {
+                if (!haveFeatures) RenderFeatures();
+                var g = new PtHip.pt_denoise_guided_params { iterations = DenoiseIterations, reserved = 0, sigma_colour = DenoiseSigmaColour,
+                    sigma_normal = DenoiseSigmaNormal, sigma_albedo = DenoiseSigmaAlbedo, sigma_depth = DenoiseSigmaDepth };
+                PtHip.Check(PtHip.pt_denoise_temporal(ctx, IntPtr.Zero, (IntPtr)(&g), out ms), "pt_denoise_temporal");
+                return ms;
+            }
+            var p = new PtHip.pt_denoise_params { iterations = DenoiseIterations, reserved = 0, sigma_colour = DenoiseSigmaColour };
+            PtHip.Check(PtHip.pt_denoise_temporal(ctx, (IntPtr)(&p), IntPtr.Zero, out ms), "pt_denoise_temporal");
+            return ms;
+        }
+
+        /// <summary>Drop the history and the temporal and motion results, keep the snapshot (pt_reset_temporal): after a
+        /// cut, or after a change of materials or lights, which nothing detects.</summary>
+        public void ResetTemporal() { PtHip.Check(PtHip.pt_reset_temporal(ctx), "pt_reset_temporal"); }
+
+        /// <summary>The temporal half of one animated frame, after its passes.</summary>
+        public void TemporalFrame()
+        {
+            RenderMotion();
+            AccumulateTemporal();
+            MotionSnapshot();
         }
 
         /// <summary>New vertex positions (and optionally normals, all three or none) for every triangle of the

@@ -1116,6 +1116,75 @@ int pt_update_textures(void* ctx, const pt_texture_update* u, double* out_kernel
  * PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE. */
 int pt_read_texture(void* ctx, int32_t index, int32_t info[4], double* data);
 
+/* ---- Motion vectors and temporal accumulation across animated frames.
+ * One animated frame on the host: apply the frame's updates; pt_reset_buffer and render passes (pass numbers keep
+ * counting across frames); pt_render_motion(cam); pt_accumulate_temporal; pt_denoise_temporal and pt_read_denoised;
+ * pt_motion_snapshot(cam).  The first frame runs the same sequence.
+ *
+ * pt_motion_snapshot records "the previous frame": the camera, and device-to-device copies of the geometry as the
+ * device holds it now: every world and BLAS triangle record {v1, e1, e2} stored at its source triangle (so a later
+ * rebuild's re-sort does not matter), the analytic records, the instance matrices and the instances' inner records
+ * (those three by record position: nothing re-sorts them).  The storage is context-owned, allocated on first use
+ * and dropped by the next pt_upload_scene together with the motion result and the history.  It ensures the identity
+ * tables as the scene's first pt_intersect_hits does, and changes no Buffer, pass state, features or counters.
+ * A NULL ctx or camera: PT_ERR_INVALID_ARG; no scene: PT_ERR_NO_SCENE; the storage not allocated:
+ * PT_ERR_OUT_OF_MEMORY, the previous snapshot kept. */
+int pt_motion_snapshot(void* ctx, const pt_camera* camera);
+
+/* One primary ray per pixel as pt_render_features casts it (Camera.CastRay(x, y, W, H, 0.5, 0.5), the lens ignored),
+ * and per pixel what pt_read_motion returns.  The previous position of the hit point is defined per kind of shape in
+ * ptsharp_amd/csrc/pt_motion.h, in fp64.  Without a snapshot on the context (status 2) shape, prim and depth are still
+ * written, so frame 0 runs the same sequence.  Errors as pt_motion_snapshot. */
+int pt_render_motion(void* ctx, const pt_camera* camera, double* out_kernel_ms);
+
+typedef enum pt_motion_array {
+    PT_MOTION_SHAPE_I32 = 0,      /* [H][W] int32: pt_intersect_hits' `shape` for the pixel's ray; -1 on a miss */
+    PT_MOTION_PRIM_I32 = 1,       /* [H][W] int32: its `prim`; -1 on a miss */
+    PT_MOTION_DEPTH_F64 = 2,      /* [H][W] double: the hit's t, or 1e9 on a miss */
+    PT_MOTION_PREV_XY_F64 = 3,    /* [H][W][2] double: the previous frame's continuous pixel coordinates of the same
+                                     surface point; (-1, -1) behind the previous camera, not finite, or without snapshot */
+    PT_MOTION_PREV_DEPTH_F64 = 4, /* [H][W] double: that point's distance from the previous camera; 1e9 for a miss */
+    PT_MOTION_PREV_PIXEL_I32 = 5, /* [H][W] int32: the nearest previous pixel floor(x' + 0.5) + W·floor(y' + 0.5), or -1 */
+    PT_MOTION_STATUS_I32 = 6      /* [H][W] int32: 0 ok; 1 outside the previous image, behind the previous camera or not
+                                     finite; 2 no snapshot on the context */
+} pt_motion_array;
+/* One array of the last pt_render_motion, row-major, into the caller's `out`.  A NULL ctx or out, `what` outside the
+ * enum, or no motion result on the context: PT_ERR_INVALID_ARG. */
+int pt_read_motion(void* ctx, int32_t what, void* out);
+
+/* max_history: the samples the history may weigh at most, 0..2^20; sigma_depth: the relative depth tolerance, finite
+ * and >= 0, 0 switches the depth test off.  NULL = 32 and 0.1: design defaults, not tuned values. */
+typedef struct pt_temporal_params {
+    int32_t max_history;
+    int32_t reserved;     /* 0 */
+    double sigma_depth;
+} pt_temporal_params;
+
+/* Merges the history into the current Buffer's statistics.  For pixel p with q = prev_pixel[p] the status is the first
+ * that applies: 7 the current pixel is invalid (pt_denoise's rule; a tile-sharded context's foreign pixels, N = 0);
+ * 1 no history; 2 the motion status is not 0; 3 the history at q is invalid; 4 (shape, prim) at p differs from the
+ * history's at q; 5 |prev_depth[p] − hist_depth[q]| > sigma_depth·prev_depth[p]; 0 merged.  On any status but 0 the
+ * temporal pixel is the Buffer's pixel as it stands; on 0 it is Chan's pairwise update in fp64 per channel with
+ * Nh' = min(Nh, max_history) (clamped so that Nc + Nh' fits int32; Nh' = 0 leaves the Buffer's pixel):
+ *   Vh' = Nh >= 2 ? Vh·((Nh' − 1)/(Nh − 1)) : Vh;  N = Nc + Nh';  δ = Mh − Mc;
+ *   M = Mc + δ·(Nh'/N);  V = Vc + Vh' + (δ·δ)·(Nc·Nh'/N).
+ * The result {M, V, N, status} is context-owned (pt_read_temporal); with this frame's (shape, prim, depth) it becomes
+ * the history, which is double-buffered: the merge reads one set and writes the other.  Changes neither the Buffer nor
+ * the pass state nor the features.  Lighting and material changes are not detected: call pt_reset_temporal after them.
+ * Needs a motion result rendered since the last pt_accumulate_temporal or pt_reset_temporal.  That missing, a NULL ctx,
+ * or a field out of range: PT_ERR_INVALID_ARG, nothing launched; the storage not allocated: PT_ERR_OUT_OF_MEMORY. */
+int pt_accumulate_temporal(void* ctx, const pt_temporal_params* params, double* out_kernel_ms);
+/* The last pt_accumulate_temporal's result: m, v [H][W][3] double, n, status [H][W] int32; each may be NULL.
+ * A NULL ctx or no temporal result on the context: PT_ERR_INVALID_ARG. */
+int pt_read_temporal(void* ctx, double* m, double* v, int32_t* n, int32_t* status);
+/* pt_denoise (`plain`, or both NULL for its defaults) or pt_denoise_guided (`guided`; the context needs features) on
+ * the temporal {M, V, N} instead of the Buffer.  The result goes where pt_denoise's goes.  Both params non-NULL, or no
+ * temporal result on the context: PT_ERR_INVALID_ARG; else the errors of the filter called. */
+int pt_denoise_temporal(void* ctx, const pt_denoise_params* plain, const pt_denoise_guided_params* guided, double* out_kernel_ms);
+/* Drops the history and the temporal and motion results and keeps the snapshot: after a cut, or after
+ * pt_update_materials or another change of the lighting.  A NULL ctx: PT_ERR_INVALID_ARG. */
+int pt_reset_temporal(void* ctx);
+
 /* Instrumentation (bench / roofline): last pass' traversal counters, summed. */
 typedef struct pt_trace_counters {
     uint64_t rays;            /* all Scene.Intersect calls                     */

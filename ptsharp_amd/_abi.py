@@ -31,6 +31,9 @@ K_IMAGE = 7   # PT_K_IMAGE: the last pt_read_image's kernels
 IMAGE_RGB8, IMAGE_RGBA8 = 0, 1   # pt_image_format (pt_channel is renderer.Channel)
 DENOISED_RGB8, DENOISED_RGBA8, DENOISED_COLOUR_F64, DENOISED_VARIANCE_F64 = 0, 1, 2, 3   # pt_denoised_format
 FEATURE_ALBEDO_F64, FEATURE_NORMAL_F32, FEATURE_DEPTH_F64, FEATURE_KIND_I32, FEATURE_MATERIAL_I32 = 0, 1, 2, 3, 4   # pt_feature
+# pt_motion_array
+(MOTION_SHAPE_I32, MOTION_PRIM_I32, MOTION_DEPTH_F64, MOTION_PREV_XY_F64, MOTION_PREV_DEPTH_F64, MOTION_PREV_PIXEL_I32,
+ MOTION_STATUS_I32) = range(7)
 
 SHAPE_SPHERE, SHAPE_CUBE, SHAPE_PLANE, SHAPE_TRIANGLE, SHAPE_MESH = 0, 1, 2, 3, 4
 SHAPE_SDF, SHAPE_VOLUME, SHAPE_TRANSFORMED = 5, 6, 7
@@ -139,6 +142,10 @@ class pt_denoise_params(C.Structure):
 class pt_denoise_guided_params(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("sigma_colour", C.c_double),
                 ("sigma_normal", C.c_double), ("sigma_albedo", C.c_double), ("sigma_depth", C.c_double)]
+
+
+class pt_temporal_params(C.Structure):
+    _fields_ = [("max_history", C.c_int32), ("reserved", C.c_int32), ("sigma_depth", C.c_double)]
 
 
 class pt_shape_update(C.Structure):
@@ -280,6 +287,13 @@ SIGNATURES = {
     "pt_read_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "pt_write_features": (C.c_int, [C.c_void_p, _d, _f, _d, _i]),
     "pt_denoise_guided": (C.c_int, [C.c_void_p, C.POINTER(pt_denoise_guided_params), _d]),
+    "pt_motion_snapshot": (C.c_int, [C.c_void_p, C.POINTER(pt_camera)]),
+    "pt_render_motion": (C.c_int, [C.c_void_p, C.POINTER(pt_camera), _d]),
+    "pt_read_motion": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "pt_accumulate_temporal": (C.c_int, [C.c_void_p, C.POINTER(pt_temporal_params), _d]),
+    "pt_read_temporal": (C.c_int, [C.c_void_p, _d, _d, _i, _i]),
+    "pt_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(pt_denoise_params), C.POINTER(pt_denoise_guided_params), _d]),
+    "pt_reset_temporal": (C.c_int, [C.c_void_p]),
     "pt_read_tiles": (C.c_int, [C.c_void_p, _i, C.c_int32, _d, _d, _i]),
     "pt_write_tiles": (C.c_int, [C.c_void_p, _i, C.c_int32, _d, _d, _i]),
     "pt_stats_get": (C.c_int, [C.c_void_p, C.POINTER(pt_stats)]),

@@ -35,6 +35,7 @@
 #include "pt_scene_compile.h"
 #include "pt_shape_refit.h"
 #include "pt_morph.h"
+#include "pt_motion_dev.h"
 #include "pt_skin.h"
 #include "pt_texture.h"
 #include "pt_update_layout.h"
@@ -284,6 +285,17 @@ struct SceneDyn {
     size_t lights_cap = 0;
     std::vector<pt::DevTexture> texs;
     DeviceArray tex_stage;
+    // motion vectors and temporal accumulation: pt_motion_snapshot's copies (pt_motion_dev.h MotionSnap,
+    // carved by motion_snap_layout) and its camera; the last pt_render_motion's arrays; the two history sets and the
+    // merge's status.  All of it goes with the scene.
+    int64_t num_xforms = 0, num_ext_recs = 0;   // entries of DevScene::xforms, records of DevScene::ext_recs
+    DeviceArray motion_snap, motion_out, temporal;
+    pt::MotionSnap snap{};
+    bool have_motion = false;            // motion_out holds a pt_render_motion's result
+    bool motion_fresh = false;           // ... rendered since the last pt_accumulate_temporal or pt_reset_temporal
+    bool have_history = false;           // temporal's set temporal_cur holds a history
+    bool have_temporal = false;          // ... which is the last pt_accumulate_temporal's result
+    int temporal_cur = 0;
     bool pose_staged = false;            // refit_ws' staged arrays hold the last pose, skin or morph (pt_read_pose)
     bool blas_boxes_on_device = false;   // blas_ws holds the meshes' boxes (after the first pt_update_meshes)
     void release_device() {
@@ -299,6 +311,9 @@ struct SceneDyn {
         blas_rebuild_ws.release();
         query_ws.release();
         tex_stage.release();
+        motion_snap.release();
+        motion_out.release();
+        temporal.release();
     }
 };
 
@@ -756,6 +771,8 @@ int pt_upload_scene(void* ctx, const pt_scene_desc* d) {
     c->dyn.h_mats = std::move(H.mats);
     c->dyn.texs = std::move(texs);
     c->dyn.has_blas = !H.blas.empty();
+    c->dyn.num_xforms = (int64_t)H.xforms.size();
+    c->dyn.num_ext_recs = (int64_t)H.ext_recs.size() / 3;
     c->dyn.h_blas = H.blas;
     for (const pt::DevBlas& b : H.blas) c->dyn.blas_node_cap.push_back(b.num_nodes);
     c->dyn.volume_update = std::move(H.volume_update);
@@ -1160,9 +1177,9 @@ int pt_read_image(void* ctx, int32_t channel, int32_t format, uint8_t* out) {
     return PT_OK;
 }
 
-int pt_denoise(void* ctx, const pt_denoise_params* params, double* out_kernel_ms) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+// pt_denoise on the Welford state {m, v, n}: the Buffer's, or the temporal result's (pt_denoise_temporal)
+static int denoise_on(Ctx* c, const pt_denoise_params* params, const double* m, const double* v, const int32_t* n,
+                      double* out_kernel_ms) {
     const int32_t iterations = params ? params->iterations : 5;
     const double sigma = params ? params->sigma_colour : 4.0;
     if (iterations < 1 || iterations > 8) return fail(PT_ERR_INVALID_ARG, "denoise: iterations must be 1..8");
@@ -1176,11 +1193,17 @@ int pt_denoise(void* ctx, const pt_denoise_params* params, double* out_kernel_ms
     }
     int pair = -1;
     PT_HIP(hipEventRecord(c->ev0, c->stream));
-    PT_HIP(pt::launch_denoise(c->d_m, c->d_v, c->d_n, c->d_denoise, c->width, c->height, iterations, sigma, &pair, c->stream));
+    PT_HIP(pt::launch_denoise(m, v, n, c->d_denoise, c->width, c->height, iterations, sigma, &pair, c->stream));
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     PT_HIP(hipStreamSynchronize(c->stream));
     c->denoise_pair = pair;
     return kernel_ms(c, out_kernel_ms);
+}
+
+int pt_denoise(void* ctx, const pt_denoise_params* params, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    return denoise_on(c, params, c->d_m, c->d_v, c->d_n, out_kernel_ms);
 }
 
 int pt_read_denoised(void* ctx, int32_t format, void* out) {
@@ -1283,9 +1306,9 @@ int pt_write_features(void* ctx, const double* albedo, const float* normal, cons
     return PT_OK;
 }
 
-int pt_denoise_guided(void* ctx, const pt_denoise_guided_params* params, double* out_kernel_ms) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+// pt_denoise_guided on the Welford state {m, v, n}, as denoise_on
+static int denoise_guided_on(Ctx* c, const pt_denoise_guided_params* params, const double* m, const double* v, const int32_t* n,
+                             double* out_kernel_ms) {
     const int32_t iterations = params ? params->iterations : 5;
     const double sigma = params ? params->sigma_colour : 4.0;
     const double guide[3] = {params ? params->sigma_albedo : PT_DENOISE_GUIDED_SIGMA_ALBEDO,
@@ -1307,12 +1330,18 @@ int pt_denoise_guided(void* ctx, const pt_denoise_guided_params* params, double*
     }
     int pair = -1;
     PT_HIP(hipEventRecord(c->ev0, c->stream));
-    PT_HIP(pt::launch_denoise_guided(c->d_m, c->d_v, c->d_n, c->d_denoise, pt::features_guide(c->d_features, c->width, c->height),
+    PT_HIP(pt::launch_denoise_guided(m, v, n, c->d_denoise, pt::features_guide(c->d_features, c->width, c->height),
                                      c->width, c->height, iterations, sigma, guide[0], guide[1], guide[2], &pair, c->stream));
     PT_HIP(hipEventRecord(c->ev1, c->stream));
     PT_HIP(hipStreamSynchronize(c->stream));
     c->denoise_pair = pair;
     return kernel_ms(c, out_kernel_ms);
+}
+
+int pt_denoise_guided(void* ctx, const pt_denoise_guided_params* params, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    return denoise_guided_on(c, params, c->d_m, c->d_v, c->d_n, out_kernel_ms);
 }
 
 static int tile_workspace(Ctx* c);
@@ -2786,6 +2815,22 @@ int ensure_query_ws(Ctx* c) {
     return PT_OK;
 }
 
+// The kernels' view of the identity tables, after ensure_query_ws
+pt::QueryDevTables query_dev_tables(const Ctx* c) {
+    const SceneDyn& Y = c->dyn;
+    const pt::QueryDev& D = Y.query_ws.at;
+    pt::QueryDevTables T{};
+    T.tri_src = D.tri_src; T.tri_src_n = (int64_t)Y.refit.src_of_pos.size();
+    T.blas_src = D.blas_src; T.blas_src_n = (int64_t)Y.blas_refit.src_of_pos.size();
+    T.tri_slot = D.tri_slot; T.tri_slot_n = (int64_t)Y.query.tri_slot.size();
+    T.ana_slot = D.ana_slot; T.ana_slot_n = (int64_t)Y.query.ana_slot.size();
+    T.plane_slot = D.plane_slot; T.plane_slot_n = (int64_t)Y.query.plane_slot.size();
+    std::memcpy(T.ana_off, Y.query.ana_off, sizeof T.ana_off);
+    std::memcpy(T.ana_cnt, Y.query.ana_cnt, sizeof T.ana_cnt);
+    T.num_blas = (int32_t)Y.blas_refit.num_blas();
+    return T;
+}
+
 // PT_QUERY_CHUNK, read at each call (tests set it): rays staged at a time
 int64_t query_chunk() {
     const char* e = std::getenv("PT_QUERY_CHUNK");
@@ -2843,17 +2888,7 @@ int pt_intersect_hits(void* ctx, int64_t n, const float* origins, const float* d
         return fail(PT_ERR_OUT_OF_MEMORY, who + ": staging allocation");
     }
     carve(staging);
-    const SceneDyn& Y = c->dyn;
-    const pt::QueryDev& D = Y.query_ws.at;
-    pt::QueryDevTables T{};
-    T.tri_src = D.tri_src; T.tri_src_n = (int64_t)Y.refit.src_of_pos.size();
-    T.blas_src = D.blas_src; T.blas_src_n = (int64_t)Y.blas_refit.src_of_pos.size();
-    T.tri_slot = D.tri_slot; T.tri_slot_n = (int64_t)Y.query.tri_slot.size();
-    T.ana_slot = D.ana_slot; T.ana_slot_n = (int64_t)Y.query.ana_slot.size();
-    T.plane_slot = D.plane_slot; T.plane_slot_n = (int64_t)Y.query.plane_slot.size();
-    std::memcpy(T.ana_off, Y.query.ana_off, sizeof T.ana_off);
-    std::memcpy(T.ana_cnt, Y.query.ana_cnt, sizeof T.ana_cnt);
-    T.num_blas = (int32_t)Y.blas_refit.num_blas();
+    const pt::QueryDevTables T = query_dev_tables(c);
     pt::DevScene S = c->S;
     S.march = nullptr;
     if (flags & PT_MARCH_LANE) S.coop_min_lanes = 65;   // as pt_intersect sets them
@@ -2886,6 +2921,216 @@ int pt_query_kernel_ms(void* ctx, double* out_ms) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !out_ms) return fail(PT_ERR_INVALID_ARG, "NULL argument");
     *out_ms = c->query_kernel_ms;
+    return PT_OK;
+}
+
+}  // extern "C"
+
+// ---- motion vectors and temporal accumulation
+namespace {
+// pt_motion_snapshot's storage: [world records by source | BLAS records by source | analytic records | xforms | ext_recs]
+struct MotionSnapDev {
+    float4 *tris, *blas, *ana, *ext;
+    pt::DevXform* xforms;
+    size_t bytes;
+};
+MotionSnapDev motion_snap_layout(const Ctx* c, void* base) {
+    const SceneDyn& Y = c->dyn;
+    const size_t num_src = (size_t)std::max(Y.refit.num_triangles, 0);
+    pt::Carver cv(base);
+    MotionSnapDev r{};
+    r.tris = cv.take<float4>(Y.refit.src_of_pos.empty() ? 0 : 3 * num_src);
+    r.blas = cv.take<float4>(Y.blas_refit.src_of_pos.empty() ? 0 : 3 * num_src);
+    r.ana = cv.take<float4>(3 * (size_t)std::max(c->S.ana_count, 0));
+    r.xforms = cv.take<pt::DevXform>((size_t)Y.num_xforms);
+    r.ext = cv.take<float4>(3 * (size_t)Y.num_ext_recs);
+    r.bytes = cv.bytes();
+    return r;
+}
+
+int device_storage(DeviceArray& a, size_t bytes, const char* name) {
+    if (a.ptr) return PT_OK;
+    if (hipMalloc(&a.ptr, bytes) != hipSuccess) {
+        a.ptr = nullptr;
+        (void)hipGetLastError();
+        return fail(PT_ERR_OUT_OF_MEMORY, std::string(name) + " allocation");
+    }
+    a.bytes = bytes;
+    return PT_OK;
+}
+
+pt::DevCamera features_camera(const pt_camera* camera) {
+    pt::DevCamera cam;
+    std::memcpy(cam.p, camera->p, sizeof cam.p); std::memcpy(cam.u, camera->u, sizeof cam.u);
+    std::memcpy(cam.v, camera->v, sizeof cam.v); std::memcpy(cam.w, camera->w, sizeof cam.w);
+    cam.m = camera->m; cam.focal_distance = camera->focal_distance;
+    cam.aperture_radius = 0.0;   // the lens is ignored: one deterministic ray through the pixel
+    return cam;
+}
+
+// The two history sets, then the merge's status
+size_t temporal_bytes(const Ctx* c) {
+    return 2 * pt::temporal_set_bytes(c->width, c->height) + (size_t)c->width * (size_t)c->height * sizeof(int32_t);
+}
+pt::TemporalSet temporal_set(const Ctx* c, int which) {
+    return pt::temporal_set_of((char*)c->dyn.temporal.ptr + (size_t)which * pt::temporal_set_bytes(c->width, c->height), c->width, c->height);
+}
+int32_t* temporal_status_array(const Ctx* c) {
+    return (int32_t*)((char*)c->dyn.temporal.ptr + 2 * pt::temporal_set_bytes(c->width, c->height));
+}
+}  // namespace
+
+extern "C" {
+
+int pt_motion_snapshot(void* ctx, const pt_camera* camera) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !camera) return fail(PT_ERR_INVALID_ARG, "pt_motion_snapshot: ctx or camera is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    PT_HIP(hipSetDevice(c->device));
+    if (const int rc = ensure_query_ws(c)) return rc;
+    SceneDyn& Y = c->dyn;
+    const bool first = !Y.motion_snap.ptr;
+    if (const int rc = device_storage(Y.motion_snap, motion_snap_layout(c, nullptr).bytes, "motion snapshot")) return rc;
+    const MotionSnapDev D = motion_snap_layout(c, Y.motion_snap.ptr);
+    if (first) PT_HIP(hipMemsetAsync(Y.motion_snap.ptr, 0, Y.motion_snap.bytes, c->stream));
+    const pt::DevScene& S = c->S;
+    const pt::QueryDev& Q = Y.query_ws.at;
+    const int64_t num_src = (int64_t)std::max(Y.refit.num_triangles, 0);
+    const int64_t world_pos = (int64_t)Y.refit.src_of_pos.size(), blas_pos = (int64_t)Y.blas_refit.src_of_pos.size();
+    if (world_pos > 0 && S.tri_recs)
+        PT_HIP(pt::launch_motion_snapshot_tris(world_pos, S.tri_recs, S.tri_rstride, Q.tri_src, num_src, D.tris, c->stream));
+    if (blas_pos > 0 && S.blas_recs)
+        PT_HIP(pt::launch_motion_snapshot_tris(blas_pos, S.blas_recs, 3, Q.blas_src, num_src, D.blas, c->stream));
+    const size_t ana_bytes = 3 * (size_t)std::max(S.ana_count, 0) * sizeof(float4);
+    if (ana_bytes && S.ana_recs) PT_HIP(hipMemcpyAsync(D.ana, S.ana_recs, ana_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (Y.num_xforms && S.xforms)
+        PT_HIP(hipMemcpyAsync(D.xforms, S.xforms, (size_t)Y.num_xforms * sizeof(pt::DevXform), hipMemcpyDeviceToDevice, c->stream));
+    if (Y.num_ext_recs && S.ext_recs)
+        PT_HIP(hipMemcpyAsync(D.ext, S.ext_recs, 3 * (size_t)Y.num_ext_recs * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    pt::MotionSnap N{};
+    N.tris = world_pos > 0 && S.tri_recs ? D.tris : nullptr;
+    N.blas = blas_pos > 0 && S.blas_recs ? D.blas : nullptr;
+    N.ana = ana_bytes && S.ana_recs ? D.ana : nullptr;
+    N.xforms = Y.num_xforms && S.xforms ? D.xforms : nullptr;
+    N.ext = Y.num_ext_recs && S.ext_recs ? D.ext : nullptr;
+    N.num_src = num_src;
+    N.num_ana = (int64_t)std::max(S.ana_count, 0);
+    N.num_xforms = Y.num_xforms;
+    N.num_ext = Y.num_ext_recs;
+    for (int k = 0; k < 3; k++) {
+        N.cam.p[k] = camera->p[k]; N.cam.u[k] = camera->u[k];
+        N.cam.v[k] = camera->v[k]; N.cam.w[k] = camera->w[k];
+    }
+    N.cam.m = camera->m;
+    N.have = 1;
+    Y.snap = N;
+    return PT_OK;
+}
+
+int pt_render_motion(void* ctx, const pt_camera* camera, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !camera) return fail(PT_ERR_INVALID_ARG, "pt_render_motion: ctx or camera is NULL");
+    if (!c->has_scene) return fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    PT_HIP(hipSetDevice(c->device));
+    if (const int rc = ensure_query_ws(c)) return rc;
+    SceneDyn& Y = c->dyn;
+    if (const int rc = device_storage(Y.motion_out, pt::motion_bytes(c->width, c->height), "motion result")) return rc;
+    const pt::QueryDevTables T = query_dev_tables(c);
+    pt::DevScene S = c->S;
+    S.march = nullptr;
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_motion(S, T, Y.snap, features_camera(camera), pt::motion_of(Y.motion_out.ptr, c->width, c->height), c->width,
+                             c->height, c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    Y.have_motion = true;
+    Y.motion_fresh = true;
+    return kernel_ms(c, out_kernel_ms);
+}
+
+int pt_read_motion(void* ctx, int32_t what, void* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return fail(PT_ERR_INVALID_ARG, "pt_read_motion: ctx or out is NULL");
+    if (what < PT_MOTION_SHAPE_I32 || what > PT_MOTION_STATUS_I32) return fail(PT_ERR_INVALID_ARG, "pt_read_motion: what is not a pt_motion_array");
+    if (!c->dyn.have_motion) return fail(PT_ERR_INVALID_ARG, "pt_read_motion before any pt_render_motion on this scene");
+    PT_HIP(hipSetDevice(c->device));
+    const size_t P = (size_t)c->width * (size_t)c->height;
+    const pt::MotionOut M = pt::motion_of(c->dyn.motion_out.ptr, c->width, c->height);
+    const void* src = nullptr;
+    size_t bytes = P * sizeof(int32_t);
+    switch (what) {
+        case PT_MOTION_SHAPE_I32: src = M.shape; break;
+        case PT_MOTION_PRIM_I32: src = M.prim; break;
+        case PT_MOTION_DEPTH_F64: src = M.depth; bytes = P * sizeof(double); break;
+        case PT_MOTION_PREV_XY_F64: src = M.prev_xy; bytes = 2 * P * sizeof(double); break;
+        case PT_MOTION_PREV_DEPTH_F64: src = M.prev_depth; bytes = P * sizeof(double); break;
+        case PT_MOTION_PREV_PIXEL_I32: src = M.prev_pixel; break;
+        default: src = M.status; break;
+    }
+    PT_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_accumulate_temporal(void* ctx, const pt_temporal_params* params, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    const int32_t max_history = params ? params->max_history : 32;
+    const double sigma_depth = params ? params->sigma_depth : 0.1;
+    if (max_history < 0 || max_history > (1 << 20)) return fail(PT_ERR_INVALID_ARG, "accumulate_temporal: max_history must be 0..2^20");
+    if (params && params->reserved != 0) return fail(PT_ERR_INVALID_ARG, "accumulate_temporal: reserved must be 0");
+    if (!(sigma_depth >= 0.0) || !std::isfinite(sigma_depth))
+        return fail(PT_ERR_INVALID_ARG, "accumulate_temporal: sigma_depth must be finite and >= 0");
+    SceneDyn& Y = c->dyn;
+    if (!Y.motion_fresh)
+        return fail(PT_ERR_INVALID_ARG, "pt_accumulate_temporal needs a pt_render_motion since the last accumulate or reset");
+    PT_HIP(hipSetDevice(c->device));
+    if (const int rc = device_storage(Y.temporal, temporal_bytes(c), "temporal history")) return rc;
+    const int next = 1 - Y.temporal_cur;
+    PT_HIP(hipEventRecord(c->ev0, c->stream));
+    PT_HIP(pt::launch_temporal_merge(c->width, c->height, c->d_m, c->d_v, c->d_n, pt::motion_of(Y.motion_out.ptr, c->width, c->height),
+                                     temporal_set(c, Y.temporal_cur), Y.have_history, max_history, sigma_depth, temporal_set(c, next),
+                                     temporal_status_array(c), c->stream));
+    PT_HIP(hipEventRecord(c->ev1, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    Y.temporal_cur = next;
+    Y.have_history = true;
+    Y.have_temporal = true;
+    Y.motion_fresh = false;
+    return kernel_ms(c, out_kernel_ms);
+}
+
+int pt_read_temporal(void* ctx, double* m, double* v, int32_t* n, int32_t* status) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->dyn.have_temporal) return fail(PT_ERR_INVALID_ARG, "pt_read_temporal before any pt_accumulate_temporal on this scene");
+    PT_HIP(hipSetDevice(c->device));
+    const size_t P = (size_t)c->width * (size_t)c->height;
+    const pt::TemporalSet R = temporal_set(c, c->dyn.temporal_cur);
+    if (m) PT_HIP(hipMemcpyAsync(m, R.m, 3 * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (v) PT_HIP(hipMemcpyAsync(v, R.v, 3 * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n) PT_HIP(hipMemcpyAsync(n, R.n, P * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (status) PT_HIP(hipMemcpyAsync(status, temporal_status_array(c), P * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_denoise_temporal(void* ctx, const pt_denoise_params* plain, const pt_denoise_guided_params* guided, double* out_kernel_ms) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    if (plain && guided) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal: plain or guided, not both");
+    if (!c->dyn.have_temporal) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal before any pt_accumulate_temporal on this scene");
+    const pt::TemporalSet R = temporal_set(c, c->dyn.temporal_cur);
+    if (guided) return denoise_guided_on(c, guided, R.m, R.v, R.n, out_kernel_ms);
+    return denoise_on(c, plain, R.m, R.v, R.n, out_kernel_ms);
+}
+
+int pt_reset_temporal(void* ctx) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx is NULL");
+    SceneDyn& Y = c->dyn;
+    Y.have_history = Y.have_temporal = Y.have_motion = Y.motion_fresh = false;
     return PT_OK;
 }
 

@@ -142,6 +142,8 @@ class Renderer:
         self.DenoiseGuided = False   # with Denoise: RenderFeatures() once, then pt_denoise_guided instead of pt_denoise
         # iterations (1..8), reserved, sigma_colour, sigma_normal, sigma_albedo, sigma_depth (0 = term off)
         self.DenoiseGuidedParams = _abi.pt_denoise_guided_params(5, 0, 4.0, 0.3, 0.3, 0.1)
+        # AccumulateTemporal: max_history (0..2^20), reserved, sigma_depth (0 = depth test off); design defaults, not tuned
+        self.TemporalParams = _abi.pt_temporal_params(32, 0, 0.1)
         self.NumCPU = 1
         # MI355X extensions (no reference counterpart)
         self.Seed = 0            # Random.Shared is unseedable; this keys the counter-based stream
@@ -339,6 +341,73 @@ class Renderer:
     def DenoisedVariance(self) -> np.ndarray:
         """The variance of the mean the filter propagated to its output, [H,W,3] float64."""
         return self._read_denoised(_abi.DENOISED_VARIANCE_F64, np.empty((self.H, self.W, 3), np.float64))
+
+    # ------------------------------------------------------------- motion vectors, temporal accumulation
+    def MotionSnapshot(self) -> None:
+        """Record the camera and the geometry as the device holds it as "the previous frame" (pt_motion_snapshot)."""
+        self._ensure_scene()
+        cam = self.Camera.to_c()
+        _abi.check(self._lib.pt_motion_snapshot(self._ctx, C.byref(cam)), "pt_motion_snapshot")
+
+    def RenderMotion(self) -> float:
+        """One ray through each pixel's centre, the lens ignored, and where its hit point was in the snapshot's frame
+        (pt_render_motion).  The Buffer and the pass state are unchanged.  Returns the device time of the kernel in ms."""
+        self._ensure_scene()
+        cam = self.Camera.to_c()
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_render_motion(self._ctx, C.byref(cam), C.byref(ms)), "pt_render_motion")
+        return float(ms.value)
+
+    def Motion(self) -> dict:
+        """The last RenderMotion()'s arrays (pt_read_motion): shape, prim, prev_pixel, status [H,W] int32; depth,
+        prev_depth [H,W] float64; prev_xy [H,W,2] float64."""
+        hw = (self.H, self.W)
+        out = {"shape": (_abi.MOTION_SHAPE_I32, np.empty(hw, np.int32)), "prim": (_abi.MOTION_PRIM_I32, np.empty(hw, np.int32)),
+               "depth": (_abi.MOTION_DEPTH_F64, np.empty(hw, np.float64)),
+               "prev_xy": (_abi.MOTION_PREV_XY_F64, np.empty(hw + (2,), np.float64)),
+               "prev_depth": (_abi.MOTION_PREV_DEPTH_F64, np.empty(hw, np.float64)),
+               "prev_pixel": (_abi.MOTION_PREV_PIXEL_I32, np.empty(hw, np.int32)),
+               "status": (_abi.MOTION_STATUS_I32, np.empty(hw, np.int32))}
+        for what, a in out.values():
+            _abi.check(self._lib.pt_read_motion(self._ctx, what, a.ctypes.data_as(C.c_void_p)), "pt_read_motion")
+        return {k: a for k, (_, a) in out.items()}
+
+    def AccumulateTemporal(self) -> float:
+        """Merge the history into the Buffer's statistics through the last RenderMotion() (pt_accumulate_temporal,
+        TemporalParams); the Buffer is unchanged.  Returns the device time of the kernel in ms."""
+        ms = C.c_double(0.0)
+        _abi.check(self._lib.pt_accumulate_temporal(self._ctx, C.byref(self.TemporalParams), C.byref(ms)),
+                   "pt_accumulate_temporal")
+        return float(ms.value)
+
+    def Temporal(self):
+        """The last AccumulateTemporal()'s result (pt_read_temporal): a Buffer of its own and the status [H,W] int32."""
+        b = Buffer(self.W, self.H)
+        status = np.empty((self.H, self.W), np.int32)
+        _abi.check(self._lib.pt_read_temporal(self._ctx, b.M.ctypes.data_as(C.POINTER(C.c_double)),
+                                              b.V.ctypes.data_as(C.POINTER(C.c_double)),
+                                              b.N.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              status.ctypes.data_as(C.POINTER(C.c_int32))), "pt_read_temporal")
+        return b, status
+
+    def DenoiseTemporal(self, guided: bool = False) -> float:
+        """DenoiseBuffer() on the temporal result instead of the Buffer (pt_denoise_temporal); read it with Denoised()."""
+        ms = C.c_double(0.0)
+        plain = None if guided else C.byref(self.DenoiseParams)
+        gd = C.byref(self.DenoiseGuidedParams) if guided else None
+        _abi.check(self._lib.pt_denoise_temporal(self._ctx, plain, gd, C.byref(ms)), "pt_denoise_temporal")
+        return float(ms.value)
+
+    def ResetTemporal(self) -> None:
+        """Drop the history and the temporal and motion results, keep the snapshot (pt_reset_temporal): after a cut, or
+        after a change of materials or lights, which nothing detects."""
+        _abi.check(self._lib.pt_reset_temporal(self._ctx), "pt_reset_temporal")
+
+    def TemporalFrame(self) -> None:
+        """The temporal half of one animated frame, after its passes: RenderMotion, AccumulateTemporal, MotionSnapshot."""
+        self.RenderMotion()
+        self.AccumulateTemporal()
+        self.MotionSnapshot()
 
     def LoadBuffer(self, buf: Buffer, passes_done: int) -> None:
         """Resume an IterativeRender from a saved Buffer (pt_write_buffer): later passes keep adding
